@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- Mcell-updates/s of the MeshBlock finite-volume update on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1 runs one rank per GPU.  Started by a launcher (`python -m torch.distributed.run --nproc-per-node N
 bench.py --gpus N ...`: RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment) the process is one of the
@@ -15,10 +15,19 @@ A "step" is one full RK2 cycle (two stages) of every cell = one cell-update per 
 (the reference's zone-cycle, src/driver/driver.cpp:513-522).  Data are synthetic: the
 closed-form Orszag-Tang initial condition, resident in HBM before the timed region.
 
-One JSON line is printed by rank 0 (see the contract in the task description), including
+One JSON line is printed by rank 0: metric, value (Mcell-updates/s of the timed cycles), unit, higher_is_better,
+dtype, ms_per_step (milliseconds per timed cycle), the workload and the build (lib_sha16, src_sha16).  At N = 1 a
+plain run times the C++ host alone: set-up, W warm-up cycles, K timed cycles, the line.  --full adds, at N = 1,
+  other_host   -- the Python host over the same W + K cycles; the C++ host heads the line only when both end at
+                  the same (time, dt) (config.host_check)
   roofline     -- achieved algorithmic HBM GB/s of the dominant kernel group, from HIP events
-  cpu_baseline -- the CPU oracle ("port" of the reference's split-kernel sequence) timed on a
-                  bounded sample of the same workload on this box's host cores (N=1 only)
+  other_configs, cpu_baseline -- the side measurements of the default workload and the CPU oracle ("port" of the
+                  reference's split-kernel sequence) timed on a bounded sample of the same workload on the host cores
+At N > 1 the line always carries the Python host's check and the roofline.
+--dump-outputs DIR (N = 1) writes what the headline host computed in its last timed cycle as float64 .npy files:
+u0.npy (conserved variables, cells x variables) and, for MHD, b0x1f/b0x2f/b0x3f.npy (the face fields on the lower
+faces of the same cells), on the interior cells or, where these would pass OUTPUT_BUDGET bytes, on a fixed seeded
+sample of them; time.npy holds (time, dt) after that cycle.
 """
 import argparse
 import json
@@ -35,6 +44,8 @@ HBM_PEAK_GBS = 8000.0          # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8
 #   pass B (c2p[+dt]):              read u0 5 + b0 3, write w0 5 + bcc0 3
 BYTES_PASS_A = {"mhd": 32*8, "hydro": 20*8}
 BYTES_PASS_B = {"mhd": 16*8, "hydro": 10*8}
+OUTPUT_BUDGET = 48 << 20       # bytes of --dump-outputs samples (u0 + face fields)
+OUTPUT_SEED = 0
 
 
 def parse():
@@ -47,9 +58,15 @@ def parse():
                     help="MeshBlock size per dimension (default: --nx, one MeshBlock per GPU); "
                          "smaller blocks put (nx/mb)^3 MeshBlocks into each GPU's pack")
     ap.add_argument("--problem", default="orszag_tang", choices=["orszag_tang", "sod", "linear_wave", "linear_wave_mhd"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: also run the Python host over the same cycles (other_host, host_check), the roofline, "
+                         "the side measurements (other_configs) and the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the state after the last timed cycle to DIR/<name>.npy (float64; N = 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the side measurements of the default run (configs[1] and configs[4]'s mesh on one GPU)")
+                    help="--full without the side measurements of the default run (configs[1] and configs[4]'s mesh on "
+                         "one GPU)")
     ap.add_argument("--cpu-sample-nx", type=int, default=128)
     ap.add_argument("--recon", default=None, choices=["dc", "plm", "ppm4", "ppmx", "wenoz"],
                     help="reconstruction (default: the deck's plm); ppm4 = the numerics of BASELINE config 5")
@@ -123,6 +140,37 @@ def src_sha16():
             h.update(os.path.basename(path).encode())
             h.update(open(path, "rb").read())
     return h.hexdigest()[:16]
+
+
+def output_sample(sim):
+    """--dump-outputs: the state a caller of the host receives after the last cycle (main.Simulation and
+    native.NativeSimulation alias the same arrays), as float64 numpy arrays on the interior cells -- all of them, or a
+    sample drawn with OUTPUT_SEED when they would pass OUTPUT_BUDGET: the same cells for the same arguments"""
+    import numpy as np
+    import torch
+    torch.cuda.synchronize()
+    ph, ind = sim.phys, sim.pmesh.mb_indcs
+    is_mhd = hasattr(ph, "b0")
+    shape = (ph.u0.shape[0], ind.nx3, ind.nx2, ind.nx1)
+    ncell = int(np.prod(shape))
+    n = min(ncell, OUTPUT_BUDGET//(8*(ph.u0.shape[1] + (3 if is_mhd else 0))))
+    idx = np.arange(ncell) if n == ncell else np.sort(np.random.default_rng(OUTPUT_SEED).choice(ncell, n, replace=False))
+    m, k, j, i = (torch.from_numpy(np.ascontiguousarray(a)).to(ph.u0.device)
+                  for a in np.unravel_index(idx, shape))
+    k, j, i = k + ind.ks, j + ind.js, i + ind.is_
+    out = {"u0": ph.u0[m, :, k, j, i]}
+    if is_mhd:
+        out.update(b0x1f=ph.b0.x1f[m, k, j, i], b0x2f=ph.b0.x2f[m, k, j, i], b0x3f=ph.b0.x3f[m, k, j, i])
+    out = {name: a.to(torch.float64).cpu().numpy() for name, a in out.items()}
+    out["time"] = np.array([sim.pmesh.time, sim.pmesh.dt], dtype=np.float64)
+    return out
+
+
+def write_outputs(directory, arrays):
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def cpu_baseline(args, blk):
@@ -259,6 +307,8 @@ class PythonHost:
         info.update(el=el, steps=args.steps, value=info["ncell_total"]*args.steps/el/1e6,
                     ms_per_step=el/args.steps*1e3, group_ms=group_ms, group_calls=len(evs), time=float(pm.time),
                     dt=float(pm.dt), ncycle=int(pm.ncycle))
+        if args.dump_outputs:
+            info["outputs"] = output_sample(sim)
         return info
 
     def close(self):
@@ -327,6 +377,8 @@ def run_cpp_host(args, pin):
                 el=el, steps=done,
                 value=info["ncell_total"]*done/el/1e6, ms_per_step=el/max(done, 1)*1e3, group_ms=ms.value,
                 group_calls=calls.value, time=sim.time, dt=sim.dt, ncycle=sim.ncycle)
+    if args.dump_outputs:
+        info["outputs"] = output_sample(sim)
     sim.close()
     if self_ex:
         native.finalize_comm()
@@ -393,6 +445,8 @@ def main():
         local = 0
     torch.cuda.set_device(local)
 
+    if args.dump_outputs and world > 1:
+        sys.exit("bench.py: --dump-outputs writes the state of one GPU's run (--gpus 1)")
     nblk = block_grid(world)
     pin, blk = make_pin(args, nblk)
     if args.native_child:
@@ -409,10 +463,10 @@ def main():
 
     # ---- the two hosts ------------------------------------------------------------------------------------
     # The C++ host is the path north_star names ("host code stays C++ ... RCCL"): it is the headline whenever it
-    # completed the K cycles and its (time, dt) agree with the Python host's at the same cycle -- a wrong or skipped
-    # halo exchange cannot win the line by being faster.
-    #   N = 1: both hosts run the same W + K cycles in this process, the C++ host first; the Python host is reported as
-    #          other_host.
+    # completed the K cycles and, where the Python host runs too (--full, N > 1), its (time, dt) agree with the Python
+    # host's at the same cycle -- a wrong or skipped halo exchange cannot win the line by being faster.
+    #   N = 1: the C++ host runs the W + K cycles in this process; the Python host runs them after it only with --full
+    #          (reported as other_host) or in its place when the C++ host gave no complete result.
     #   N > 1: the C++ host + RCCL is measured FIRST (one child process per rank, so that neither an abort nor a
     #          stall inside a transport that could only be exercised to self where it was built costs the bench);
     #          the Python host then runs its W warm-up cycles, and if the C++ host stood at the same (time, dt)
@@ -430,20 +484,23 @@ def main():
                 why = "C++ host failed: %r" % (e,)
         else:
             why = "C++ host switched off (AKMI_BENCH_NATIVE_CHECK=0)"
-        host = PythonHost(args, pin, rank, world)
-        host.warm()
-        py = host.timed()
-        host.close()
-        if cpp is not None:
-            if cpp.get("steps") != args.steps:
-                why = "C++ host completed %s of %d cycles" % (cpp.get("steps"), args.steps)
-            elif cpp["time"] != py["time"] or cpp["dt"] != py["dt"]:
+        cpp_done = cpp is not None and cpp.get("steps") == args.steps
+        if cpp is not None and not cpp_done:
+            why = "C++ host completed %s of %d cycles" % (cpp.get("steps"), args.steps)
+        py, check = None, None
+        if args.full or not cpp_done:
+            host = PythonHost(args, pin, rank, world)
+            host.warm()
+            py = host.timed()
+            host.close()
+            check = "both hosts ended at t = %r, dt = %r after %d + %d cycles" % (
+                py["time"], py["dt"], args.warmup, args.steps)
+        if cpp_done:
+            if py is not None and (cpp["time"] != py["time"] or cpp["dt"] != py["dt"]):
                 why = ("C++ host ended at (t, dt) = (%r, %r), the Python host at (%r, %r): not accepted"
                        % (cpp["time"], cpp["dt"], py["time"], py["dt"]))
             else:
                 cpp_ok = True
-        check = "both hosts ended at t = %r, dt = %r after %d + %d cycles" % (
-            py["time"], py["dt"], args.warmup, args.steps)
     else:
         import torch.distributed as dist
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
@@ -497,72 +554,78 @@ def main():
     head, other = (cpp, py) if cpp_ok else (py, cpp)
     if "value" not in (other or {}):
         other = None                                       # the Python host stopped after confirming the C++ host
-    for k in ("ncell_rank", "ncell_total", "nstage", "ng"):
-        head.setdefault(k, py[k])
+    if py is not None:
+        for k in ("ncell_rank", "ncell_total", "nstage", "ng"):
+            head.setdefault(k, py[k])
+    fused = py["fused"] if py is not None else bool(head.get("group_calls"))
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, head["outputs"])
+    nst = args.steps*head["nstage"]
+    plain = not (args.recon or args.ng or args.set or args.split or args.mb) and args.problem in ("orszag_tang", "sod")
 
     # ---- roofline of the dominant launch group: HIP events of the headline host's timed loop ----------------
     # akmi_*_stage_fused / _stage_phase = the whole stage except the halo exchange, the BCs and the ghost-shell
     # c2p: algorithmic bytes = SURVEY 8(d)'s per-cell-stage figure (MHD 384 B, hydro 240 B).
-    nst = args.steps*py["nstage"]
-    stage_bytes = BYTES_PASS_A[blk] + BYTES_PASS_B[blk]
-    ncell_rank = py["ncell_rank"]
-    plain = not (args.recon or args.ng or args.set or args.split or args.mb) and args.problem in ("orszag_tang", "sod")
-    if head.get("group_calls"):
-        tS = head["group_ms"]*1e-3/nst                        # seconds per stage in the launch group
-        rest_ms = head["ms_per_step"]/py["nstage"] - tS*1e3
-        kname = ("the stage's kernel calls akmi_%s_stage_phase (sweeps + update%s) + akmi_%s_c2p_newdt (ConsToPrim of all "
-                 "cells + CFL scan), i.e. the stage without ghost fill and boundary conditions" % (
-                     blk, " + CornerE + CT" if blk == "mhd" else "", blk)) if world == 1 else \
-                "akmi_%s_stage_phase x3 of a rank (the halo messages travel between the phases)" % blk
-    else:
-        # no launch-group events: the hosts took the task-granular chain (small 3-D pack, --split) -- the roofline is
-        # then the whole stage of a rank (every task, ghost fill and BCs included), and the fused kernels' VALU floor
-        # does not apply
-        tS, rest_ms = head["ms_per_step"]*1e-3/py["nstage"], None
-        kname = "whole stage of a rank (task-granular chain: one kernel per reference task, incl. ghost exchange and BCs)"
-    ach = stage_bytes*ncell_rank/tS/1e9
-    traffic, tsrc = None, None
-    tfile = os.path.join(ROOT, "profiles", "pmc_traffic_latest.json" if blk == "mhd" else
-                         "pmc_traffic_hydro_latest.json")
-    if os.path.exists(tfile) and args.nx == 256 and plain:
-        # HBM-side bytes per stage from rocprofv3 PMC counters (FETCH_SIZE / WRITE_SIZE in separate passes,
-        # calibrated on a copy of known size; tools/pmc.sh), recorded for this workload in a separate run
-        t = json.load(open(tfile))
-        stage_kernels = [k for k in t["kernels"] if k.startswith("akmi::k_sweep") or
-                         k.startswith("akmi::k_corner") or k.startswith("akmi::k_ct_copy") or
-                         k.startswith("akmi::k_hydro_stage3d") or k.startswith("akmi::k_c2p_newdt")]
-        same_lib = t.get("lib_sha16") == lib_sha16()
-        same_src = t.get("src_sha16") is not None and t.get("src_sha16") == src_sha16()
-        if same_lib or same_src:
-            # (the counter run does 2 RK2 cycles = 4 stages: a kernel launched once per stage has 4 launches, 5 with the
-            #  conversion of Driver::Initialize; a kernel that only runs there -- the hydro path converts inside its stage
-            #  kernel -- does not belong to a stage)
-            traffic = round(sum(t["kernels"][k]["hbm_bytes_per_launch"]*round(t["kernels"][k].get("launches", 4)/4.0)
-                                for k in stage_kernels))
-            tsrc = "profiles/%s (%s, %s)" % (os.path.basename(tfile), t.get("tag", ""),
-                                              ("lib %s" % t["lib_sha16"]) if same_lib else
-                                              ("same sources %s, rebuilt library" % t["src_sha16"]))
+    roofline = None
+    if args.full or world > 1:
+        stage_bytes = BYTES_PASS_A[blk] + BYTES_PASS_B[blk]
+        ncell_rank = head["ncell_rank"]
+        if head.get("group_calls"):
+            tS = head["group_ms"]*1e-3/nst                        # seconds per stage in the launch group
+            rest_ms = head["ms_per_step"]/head["nstage"] - tS*1e3
+            kname = ("the stage's kernel calls akmi_%s_stage_phase (sweeps + update%s) + akmi_%s_c2p_newdt (ConsToPrim of all "
+                     "cells + CFL scan), i.e. the stage without ghost fill and boundary conditions" % (
+                         blk, " + CornerE + CT" if blk == "mhd" else "", blk)) if world == 1 else \
+                    "akmi_%s_stage_phase x3 of a rank (the halo messages travel between the phases)" % blk
         else:
-            tsrc = "profiles/%s is of another build (lib %s / sources %s, this run %s / %s): traffic not reported" % (
-                os.path.basename(tfile), t.get("lib_sha16"), t.get("src_sha16"), lib_sha16(), src_sha16())
-    whole = stage_bytes*ncell_rank*nst/head["el"]/1e9
-    roofline = {"bound": "hbm", "kernel": kname,
-                "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(ach/HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": tsrc,
-                "algorithmic_bytes_per_cell_stage": stage_bytes,
-                "algorithmic_bytes_per_launch": stage_bytes*ncell_rank,
-                "ms_per_launch": round(tS*1e3, 4),
-                "timing": "HIP event pairs on the launch stream around every call of the group inside the timed "
-                          "loop of the headline host (%d calls)" % (head.get("group_calls") or 0),
-                "halo_bcs_shell_c2p_ms": None if rest_ms is None else round(rest_ms, 4),
-                # N > 1 (or AKMI_SELF_EXCHANGE=1): the exchange of the C++ host taken apart -- pack, exposed wait, unpack per
-                # stage, dt all-reduce per cycle, bytes and peers, the ranks RCCL reports (akmi_comm_profile)
-                "halo": (head.get("halo") if (head.get("halo") or {}).get("posts_per_stage") else None),
-                "valu_floor": valu_floor(blk, args.nx, plain) if head.get("group_calls") else None,
-                "whole_stage": {"achieved": round(whole, 1), "frac": round(whole/HBM_PEAK_GBS, 4)},
-                "note": "two roofs: HBM (algorithmic bytes / 8 TB/s) and fp64 issue (valu_floor.ms)%s: DESIGN.md 3" % (
-                    "; the measured traffic is %.2fx the algorithmic bytes (intermediates between the kernels of the stage, "
-                    "tile halos counted per XCD)" % (traffic/float(stage_bytes*ncell_rank)) if traffic else "")}
+            # no launch-group events: the hosts took the task-granular chain (small 3-D pack, --split) -- the roofline is
+            # then the whole stage of a rank (every task, ghost fill and BCs included), and the fused kernels' VALU floor
+            # does not apply
+            tS, rest_ms = head["ms_per_step"]*1e-3/head["nstage"], None
+            kname = "whole stage of a rank (task-granular chain: one kernel per reference task, incl. ghost exchange and BCs)"
+        ach = stage_bytes*ncell_rank/tS/1e9
+        traffic, tsrc = None, None
+        tfile = os.path.join(ROOT, "profiles", "pmc_traffic_latest.json" if blk == "mhd" else
+                             "pmc_traffic_hydro_latest.json")
+        if os.path.exists(tfile) and args.nx == 256 and plain:
+            # HBM-side bytes per stage from rocprofv3 PMC counters (FETCH_SIZE / WRITE_SIZE in separate passes,
+            # calibrated on a copy of known size; tools/pmc.sh), recorded for this workload in a separate run
+            t = json.load(open(tfile))
+            stage_kernels = [k for k in t["kernels"] if k.startswith("akmi::k_sweep") or
+                             k.startswith("akmi::k_corner") or k.startswith("akmi::k_ct_copy") or
+                             k.startswith("akmi::k_hydro_stage3d") or k.startswith("akmi::k_c2p_newdt")]
+            same_lib = t.get("lib_sha16") == lib_sha16()
+            same_src = t.get("src_sha16") is not None and t.get("src_sha16") == src_sha16()
+            if same_lib or same_src:
+                # (the counter run does 2 RK2 cycles = 4 stages: a kernel launched once per stage has 4 launches, 5 with the
+                #  conversion of Driver::Initialize; a kernel that only runs there -- the hydro path converts inside its stage
+                #  kernel -- does not belong to a stage)
+                traffic = round(sum(t["kernels"][k]["hbm_bytes_per_launch"]*round(t["kernels"][k].get("launches", 4)/4.0)
+                                    for k in stage_kernels))
+                tsrc = "profiles/%s (%s, %s)" % (os.path.basename(tfile), t.get("tag", ""),
+                                                  ("lib %s" % t["lib_sha16"]) if same_lib else
+                                                  ("same sources %s, rebuilt library" % t["src_sha16"]))
+            else:
+                tsrc = "profiles/%s is of another build (lib %s / sources %s, this run %s / %s): traffic not reported" % (
+                    os.path.basename(tfile), t.get("lib_sha16"), t.get("src_sha16"), lib_sha16(), src_sha16())
+        whole = stage_bytes*ncell_rank*nst/head["el"]/1e9
+        roofline = {"bound": "hbm", "kernel": kname,
+                    "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(ach/HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": tsrc,
+                    "algorithmic_bytes_per_cell_stage": stage_bytes,
+                    "algorithmic_bytes_per_launch": stage_bytes*ncell_rank,
+                    "ms_per_launch": round(tS*1e3, 4),
+                    "timing": "HIP event pairs on the launch stream around every call of the group inside the timed "
+                              "loop of the headline host (%d calls)" % (head.get("group_calls") or 0),
+                    "halo_bcs_shell_c2p_ms": None if rest_ms is None else round(rest_ms, 4),
+                    # N > 1 (or AKMI_SELF_EXCHANGE=1): the exchange of the C++ host taken apart -- pack, exposed wait, unpack per
+                    # stage, dt all-reduce per cycle, bytes and peers, the ranks RCCL reports (akmi_comm_profile)
+                    "halo": (head.get("halo") if (head.get("halo") or {}).get("posts_per_stage") else None),
+                    "valu_floor": valu_floor(blk, args.nx, plain) if head.get("group_calls") else None,
+                    "whole_stage": {"achieved": round(whole, 1), "frac": round(whole/HBM_PEAK_GBS, 4)},
+                    "note": "two roofs: HBM (algorithmic bytes / 8 TB/s) and fp64 issue (valu_floor.ms)%s: DESIGN.md 3" % (
+                        "; the measured traffic is %.2fx the algorithmic bytes (intermediates between the kernels of the stage, "
+                        "tile halos counted per XCD)" % (traffic/float(stage_bytes*ncell_rank)) if traffic else "")}
 
     rname = (args.recon or "plm").upper()
     halo = "none (single periodic block: same-rank gather)" if world == 1 else (
@@ -582,17 +645,18 @@ def main():
                                       args.problem, ("ideal MHD %s+HLLD+CT" % rname) if blk == "mhd" else
                                       ("ideal hydro %s+HLLC" % rname), args.nx, args.nx*nblk[0],
                                       args.nx*nblk[1], args.nx*nblk[2],
-                                      *[b*args.nx//(args.mb or args.nx) for b in nblk], py["ng"]),
-                      "path": "fused stage" if py["fused"] else
+                                      *[b*args.nx//(args.mb or args.nx) for b in nblk], head["ng"]),
+                      "path": "fused stage" if fused else
                               ("task-granular" if args.split else
                                "task-granular (chosen by the hosts for a small 3-D pack: one thread per face beats the "
                                "marching kernels there)"),
                       "host": head["host"] + ("" if world == 1 or not cpp_ok else ", one child process per rank"),
-                      "halo": halo},
-           "roofline": roofline}
+                      "halo": halo}}
+    if roofline is not None:
+        out["roofline"] = roofline
     if why:
         out["config"]["host_note"] = why
-    if cpp_ok:
+    if cpp_ok and check:
         out["config"]["host_check"] = check
     elif why:
         out["config"]["host_check"] = "C++ host not the headline: " + why
@@ -601,10 +665,10 @@ def main():
         "stage_group_ms": round(other["group_ms"]/nst, 4) if other.get("group_calls") else None}
     if args.set:
         out["config"]["workload"] += " + " + " ".join(args.set)
-    if world == 1 and plain and args.nx == 256 and args.problem == "orszag_tang" and not args.no_other_configs \
-            and not args.no_cpu_baseline:        # (the profiling tools run with --no-cpu-baseline: headline kernels only)
+    if args.full and world == 1 and plain and args.nx == 256 and args.problem == "orszag_tang" \
+            and not args.no_other_configs and not args.no_cpu_baseline:   # (--no-cpu-baseline: headline kernels only)
         out["other_configs"] = other_configs(args)
-    if world == 1 and not args.no_cpu_baseline and not args.set:
+    if args.full and world == 1 and not args.no_cpu_baseline and not args.set:
         out["cpu_baseline"] = cpu_baseline(args, blk)
     print(json.dumps(out), flush=True)
 
@@ -815,6 +879,8 @@ def main_native(args, pin, blk, nblk, rank, world):
         el = float(t.item())
     stage_bytes = BYTES_PASS_A[blk] + BYTES_PASS_B[blk]
     ach = stage_bytes*ncell_rank*nstage*args.steps/el/1e9
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, output_sample(sim))
     if rank == 0:
         rname = (args.recon or "plm").upper()
         out = {"metric": "Mcell-updates/s (3D MHD %s+HLLD+CT RK2, %d^3 cells per GPU)" % (rname, args.nx)
@@ -836,7 +902,7 @@ def main_native(args, pin, blk, nblk, rank, world):
                             "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                             "frac": round(ach/HBM_PEAK_GBS, 4), "traffic": None,
                             "algorithmic_bytes_per_cell_stage": stage_bytes}}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args, blk)
         print(json.dumps(out))
     sim.close()

@@ -3,15 +3,16 @@
 not gpu:
   * the writers, driven by the CPU oracle through the product's host logic, reproduce the
     committed fixtures tests/golden/outputs/ byte for byte;
-  * (only where /root/reference exists, i.e. in the build container) the fixtures are parsed
-    with the REFERENCE's own readers -- vis/python/athena_read.py tab()/hst()/error_dat() and
-    bin_convert.read_binary() -- and the parsed numbers are compared with the oracle's arrays.
-    This pins the formats on the reference's tools.
+  * what the REFERENCE's own readers -- vis/python/athena_read.py tab()/hst()/error_dat() and
+    bin_convert.read_binary() -- return for the fixtures, recorded in tests/golden/reference_readers.npz
+    (tests/golden/make_output_fixtures.py --reference-readers) with the sha256 of every file they read,
+    is compared with the oracle's arrays.  This pins the formats on the reference's tools.
 gpu:
   * the same cases through the HIP path (python -m athenak_amd ...) give byte-identical tab, bin
     and -errs.dat files and the same history numbers (device reduction: round-off).
 """
 import filecmp
+import hashlib
 import os
 import sys
 import tempfile
@@ -28,7 +29,7 @@ import output_cases as oc  # noqa: E402
 
 GOLD = os.path.join(ROOT, "tests", "golden", "outputs")
 CASES = ["sod", "ot", "lwave_hydro", "lwave_mhd"]
-REF_PY = "/root/reference/vis/python"
+REF_RECORD = os.path.join(ROOT, "tests", "golden", "reference_readers.npz")
 
 
 def _golden_files(case):
@@ -68,19 +69,28 @@ def _oracle_sod():
     return s
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_PY), reason="reference readers only exist in the build container")
+def _reference_readers():
+    """the results of the reference's readers for the fixtures, as they returned them (dicts in their key order, string
+    lists as lists, scalars as scalars), once the fixtures are shown to be the very files they read"""
+    z = np.load(REF_RECORD, allow_pickle=False)
+    rec = {k: z[k] for k in z.files}
+    for k, digest in rec.items():
+        if k.startswith("sha256/"):
+            path = os.path.join(GOLD, k[len("sha256/"):])
+            assert hashlib.sha256(open(path, "rb").read()).hexdigest() == str(digest), path
+
+    def parsed(prefix):
+        if prefix + "/keys" in rec:
+            return {str(k): parsed("%s/%s" % (prefix, k)) for k in rec[prefix + "/keys"]}
+        v = rec[prefix]
+        return v.item() if v.ndim == 0 else (v.tolist() if v.dtype.kind == "U" else v)
+    return parsed
+
+
 def test_reference_readers_parse_the_files():
-    sys.path.insert(0, REF_PY)
-    import types
-    import athena_read
-    if "h5py" not in sys.modules:            # bin_convert imports h5py for its athdf writer only;
-        try:                                 # read_binary() does not use it (not installed here)
-            import h5py  # noqa: F401
-        except ImportError:
-            sys.modules["h5py"] = types.ModuleType("h5py")
-    import bin_convert
+    parsed = _reference_readers()
     # --- tab: final Sod primitives, columns as athena_read.tab names them
-    t = athena_read.tab(os.path.join(GOLD, "sod", "tab", "Sod.hydro_w.00002.tab"))
+    t = parsed("tab_sod")
     o = _oracle_sod()
     w = o.array("w0")
     assert t["cycle"] == o.ncycle and abs(t["time"] - 0.1) < 1e-6
@@ -91,19 +101,19 @@ def test_reference_readers_parse_the_files():
     x = -0.5 + (np.arange(64) + 0.5)/64
     assert np.allclose(t["x1v"], x, atol=1e-6) and set(t) >= {"dens", "velx", "vely", "velz", "eint", "x1v"}
     # --- hst: names and conservation
-    h = athena_read.hst(os.path.join(GOLD, "sod", "Sod.hydro.hst"))
+    h = parsed("hst_sod")
     assert list(h)[:5] == ["time", "dt", "mass", "1-mom", "2-mom"] and "3-KE" in h
     assert np.all(h["mass"] == h["mass"][0]) and np.all(h["tot-E"] == h["tot-E"][0])
     assert h["time"][-1] == pytest.approx(0.1, rel=1e-5) and len(h["time"]) == 5
-    hm = athena_read.hst(os.path.join(GOLD, "ot", "OrszagTang.mhd.hst"))
+    hm = parsed("hst_ot")
     assert "3-ME" in hm and len(hm["time"]) == 4 and np.allclose(hm["mass"], hm["mass"][0], rtol=1e-12)
     # --- errs.dat: column 4 = RMS-L1 (testutils.py:273-276), pinned numbers of the oracle tests
-    e = athena_read.error_dat(os.path.join(GOLD, "lwave_hydro", "LinWave-errs.dat"))
+    e = parsed("errs_lwave_hydro")
     assert e.shape == (1, 11) and "%.6e" % e[0][4] == "7.390252e-08" and int(e[0][0]) == 32
-    e = athena_read.error_dat(os.path.join(GOLD, "lwave_mhd", "LinWave-errs.dat"))
+    e = parsed("errs_lwave_mhd")
     assert e.shape == (1, 14) and "%.6e" % e[0][4] == "8.812266e-08"
     # --- bin: the reference's reader returns per-MeshBlock float32 arrays
-    b = bin_convert.read_binary(os.path.join(GOLD, "ot", "bin", "OrszagTang.mhd_bcc.00000.bin"))
+    b = parsed("bin_ot")
     assert b["var_names"] == ["bcc1", "bcc2", "bcc3"] and b["n_mbs"] == 4 and b["cycle"] == 0
     assert (b["Nx1"], b["Nx2"], b["Nx3"], b["nx1_mb"], b["nx3_mb"]) == (16, 16, 8, 8, 8)
     assert b["mb_data"]["bcc1"][0].shape == (8, 8, 8)
@@ -118,7 +128,7 @@ def test_reference_readers_parse_the_files():
         for q, name in enumerate(("bcc1", "bcc2", "bcc3")):
             assert np.array_equal(b["mb_data"][name][m], bcc[m, q, 2:10, 2:10, 2:10].astype(np.float32))
     assert np.array_equal(b["mb_logical"][:, :3], np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0], [1, 1, 0]]))
-    bs = bin_convert.read_binary(os.path.join(GOLD, "sod", "bin", "Sod.hydro_u.00001.bin"))
+    bs = parsed("bin_sod")
     assert bs["var_names"] == ["dens", "mom1", "mom2", "mom3", "ener"] and bs["n_mbs"] == 2
 
 
@@ -316,18 +326,13 @@ def test_refined_mesh_bin_and_rst_carry_block_levels(cpu_oracle_backend):
         for g, h in enumerate(hdrs):
             assert tuple(h[6:9]) == tuple(pm.lloc_eachmb[g][:3])
             assert h[9] == levels[g] - pm.root_level, (g, h[9], levels[g], pm.root_level)
-        if os.path.isdir(REF_PY):                  # the reference's own reader (build container only)
-            sys.path.insert(0, REF_PY)
-            import types
-            if "h5py" not in sys.modules:
-                try:
-                    import h5py  # noqa: F401
-                except ImportError:
-                    sys.modules["h5py"] = types.ModuleType("h5py")
-            import bin_convert
-            b = bin_convert.read_binary(os.path.join(d, "bin", "LinWave.hydro_u.00001.bin"))
-            assert b["n_mbs"] == pm.nmb_total
-            assert [int(x) for x in b["mb_logical"][:, 3]] == [l - pm.root_level for l in levels]
+        # the reference's own reader on this very file (recorded with its sha256 in tests/golden/reference_readers.npz)
+        parsed = _reference_readers()
+        raw = open(os.path.join(d, "bin", "LinWave.hydro_u.00001.bin"), "rb").read()
+        assert hashlib.sha256(raw).hexdigest() == parsed("generated_sha256/bin_smr")
+        b = parsed("bin_smr")
+        assert b["n_mbs"] == pm.nmb_total
+        assert [int(x) for x in b["mb_logical"][:, 3]] == [l - pm.root_level for l in levels]
         _, hdr, _ = outputs.read_restart(os.path.join(d, "rst", "LinWave.00001.rst"))
         assert hdr["root_level"] == pm.root_level
         assert [int(x) for x in hdr["lloc"][:, 3]] == levels

@@ -8,7 +8,7 @@ for r in $(seq 1 $rounds); do
     (
       if [ "$v" != "-" ]; then export AKMI_LIB=$root/athenak_amd/lib/variants/libakmi_$v.so; fi
       IFS=',' read -ra kv <<< "$envs"; for e in "${kv[@]}"; do [ -n "$e" ] && export "$e"; done
-      python $root/bench.py --no-cpu-baseline --steps ${STEPS:-20} $BENCH_ARGS 2>/dev/null | grep '^{"metric"' | python -c 'import sys,json; d=json.loads(sys.stdin.read()); print("'"$spec"'", d["value"], d["roofline"]["ms_per_launch"], d["other_host"]["value"] if d.get("other_host") else "")'
+      python $root/bench.py --full --no-cpu-baseline --steps ${STEPS:-20} $BENCH_ARGS 2>/dev/null | grep '^{"metric"' | python -c 'import sys,json; d=json.loads(sys.stdin.read()); print("'"$spec"'", d["value"], d["roofline"]["ms_per_launch"], d["other_host"]["value"] if d.get("other_host") else "")'
     )
   done
 done

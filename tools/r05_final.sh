@@ -18,14 +18,15 @@ cp gpurun_out/${tag}_hydro_valu_counters.json profiles/valu_counters_hydro_lates
 tail -4 gpurun_out/${tag}_hydro_valu_counters.txt
 unset AKMI_PMC_PROBLEM
 for f in pmc_traffic_latest pmc_traffic_hydro_latest valu_counters_latest valu_counters_hydro_latest; do cp profiles/$f.json gpurun_out/${tag}_$f.json; done
-python bench.py > gpurun_out/${tag}_bench_full.log 2>&1
-grep '^{"metric"' gpurun_out/${tag}_bench_full.log | tail -1 > gpurun_out/${tag}_bench_full.json
-cut -c1-3000 gpurun_out/${tag}_bench_full.json
+res=${BENCH_RESULTS:-bench_results}; mkdir -p $res     # the bench records of this script
+python bench.py --full > $res/${tag}_bench_full.log 2>&1
+grep '^{"metric"' $res/${tag}_bench_full.log | tail -1 > $res/${tag}_bench_full.json
+cut -c1-3000 $res/${tag}_bench_full.json
 bash tools/prof.sh $tag --steps 10 | head -12
 bash tools/prof.sh ${tag}_hydro256 --problem sod --nx 256 --no-other-configs | head -6
 bash tools/prof.sh ${tag}_hydro128 --problem sod --nx 128 --no-other-configs | head -6
-python bench.py --problem sod --nx 256 --no-other-configs --no-cpu-baseline 2>/dev/null | grep '^{"metric"' > gpurun_out/${tag}_hydro256_bench_full.json
-python bench.py --problem sod --nx 128 --no-other-configs --no-cpu-baseline 2>/dev/null | grep '^{"metric"' > gpurun_out/${tag}_hydro128_bench_full.json
-python bench.py --recon ppm4 --no-other-configs --no-cpu-baseline 2>/dev/null | grep '^{"metric"' > gpurun_out/${tag}_bench_ppm4.json
-cut -c1-330 gpurun_out/${tag}_hydro256_bench_full.json gpurun_out/${tag}_hydro128_bench_full.json gpurun_out/${tag}_bench_ppm4.json
+python bench.py --full --problem sod --nx 256 --no-other-configs --no-cpu-baseline 2>/dev/null | grep '^{"metric"' > $res/${tag}_hydro256_bench_full.json
+python bench.py --full --problem sod --nx 128 --no-other-configs --no-cpu-baseline 2>/dev/null | grep '^{"metric"' > $res/${tag}_hydro128_bench_full.json
+python bench.py --full --recon ppm4 --no-other-configs --no-cpu-baseline 2>/dev/null | grep '^{"metric"' > $res/${tag}_bench_ppm4.json
+cut -c1-330 $res/${tag}_hydro256_bench_full.json $res/${tag}_hydro128_bench_full.json $res/${tag}_bench_ppm4.json
 bash tools/config5_prof.sh ${tag} > /dev/null 2>&1; head -12 gpurun_out/${tag}_config5.txt

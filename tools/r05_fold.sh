@@ -7,7 +7,7 @@ for r in 1 2 3; do
   for f in 0 1; do
     for nx in 128 256; do
       echo "== fold=$f nx=$nx" >> $out
-      AKMI_FOLD_BCS=$f timeout 300 python bench.py --no-cpu-baseline --problem sod --nx $nx --no-other-configs 2>/dev/null | grep '^{"metric"' | python -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["value"], d["ms_per_step"], d["roofline"]["ms_per_launch"], d["other_host"]["value"] if d.get("other_host") else "", d["config"]["host_check"])' >> $out
+      AKMI_FOLD_BCS=$f timeout 300 python bench.py --full --no-cpu-baseline --problem sod --nx $nx --no-other-configs 2>/dev/null | grep '^{"metric"' | python -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["value"], d["ms_per_step"], d["roofline"]["ms_per_launch"], d["other_host"]["value"] if d.get("other_host") else "", d["config"]["host_check"])' >> $out
     done
   done
 done

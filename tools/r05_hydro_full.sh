@@ -11,6 +11,7 @@ tail -5 gpurun_out/r05_hydro_valu_counters.txt
 unset AKMI_PMC_PROBLEM
 bash tools/prof.sh r05_hydro256 --problem sod --nx 256 --no-other-configs | head -8
 bash tools/prof.sh r05_hydro128 --problem sod --nx 128 --no-other-configs | head -8
-python bench.py --problem sod --nx 256 --no-other-configs --no-cpu-baseline 2>/dev/null | grep '^{"metric"' > gpurun_out/r05_hydro256_bench_full.json
-python bench.py --problem sod --nx 128 --no-other-configs --no-cpu-baseline 2>/dev/null | grep '^{"metric"' > gpurun_out/r05_hydro128_bench_full.json
-cut -c1-400 gpurun_out/r05_hydro256_bench_full.json gpurun_out/r05_hydro128_bench_full.json
+res=${BENCH_RESULTS:-bench_results}; mkdir -p $res     # the bench records of this script
+python bench.py --full --problem sod --nx 256 --no-other-configs --no-cpu-baseline 2>/dev/null | grep '^{"metric"' > $res/r05_hydro256_bench_full.json
+python bench.py --full --problem sod --nx 128 --no-other-configs --no-cpu-baseline 2>/dev/null | grep '^{"metric"' > $res/r05_hydro128_bench_full.json
+cut -c1-400 $res/r05_hydro256_bench_full.json $res/r05_hydro128_bench_full.json

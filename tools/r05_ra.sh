@@ -8,10 +8,10 @@ for r in 1 2 3; do
     for spec in "sod 128" "sod 256"; do
       set -- $spec
       echo "== run_ahead=$ra $1 nx=$2" >> $out
-      AKMI_RUN_AHEAD=$ra timeout 300 python bench.py --no-cpu-baseline --problem $1 --nx $2 --no-other-configs 2>/dev/null | grep '^{"metric"' | python -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["value"], d["ms_per_step"], d["roofline"]["ms_per_launch"], d["other_host"]["value"] if d.get("other_host") else "", d["config"]["host_check"])' >> $out
+      AKMI_RUN_AHEAD=$ra timeout 300 python bench.py --full --no-cpu-baseline --problem $1 --nx $2 --no-other-configs 2>/dev/null | grep '^{"metric"' | python -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["value"], d["ms_per_step"], d["roofline"]["ms_per_launch"], d["other_host"]["value"] if d.get("other_host") else "", d["config"]["host_check"])' >> $out
     done
     echo "== run_ahead=$ra headline" >> $out
-    AKMI_RUN_AHEAD=$ra timeout 300 python bench.py --no-cpu-baseline --no-other-configs 2>/dev/null | grep '^{"metric"' | python -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["value"], d["ms_per_step"], d["roofline"]["ms_per_launch"], d["other_host"]["value"] if d.get("other_host") else "", d["config"]["host_check"])' >> $out
+    AKMI_RUN_AHEAD=$ra timeout 300 python bench.py --full --no-cpu-baseline --no-other-configs 2>/dev/null | grep '^{"metric"' | python -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["value"], d["ms_per_step"], d["roofline"]["ms_per_launch"], d["other_host"]["value"] if d.get("other_host") else "", d["config"]["host_check"])' >> $out
   done
 done
 cat $out
