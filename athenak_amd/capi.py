@@ -51,6 +51,9 @@ SYMBOLS = [
     "akmi_selftest_fp64",
     "akmi_smr_fc_map", "akmi_smr_fc_copy", "akmi_smr_cc_map", "akmi_smr_cc_copy",
     "akmi_smr_unpack_fc", "akmi_smr_pack_flux_cc", "akmi_smr_unpack_flux_cc", "akmi_smr_pack_emf", "akmi_smr_unpack_emf",
+    "akmi_rng_uniform", "akmi_rng_gaussian", "akmi_rng_state_bytes", "akmi_turb_mode_count", "akmi_turb_amplitudes",
+    "akmi_turb_tables", "akmi_turb_workspace_bytes", "akmi_turb_synthesize", "akmi_turb_moments", "akmi_turb_add_forcing",
+    "akmi_turb_remove_net_mom",
 ]
 
 _LIB = None
@@ -63,6 +66,12 @@ class Smr(C.Structure):
                 ("ndat", C.c_void_p), ("slot_ox", C.c_void_p), ("layout", C.c_void_p),
                 ("soff", C.c_void_p), ("roff", C.c_void_p), ("direct_same", C.c_int), ("needs_coarse", C.c_void_p),
                 ("lists", C.c_void_p), ("list_cnt", C.c_int*6)]
+
+
+class RngState(C.Structure):
+    """struct akmi_rng_state (RNG_State, src/utils/random.hpp:26-34): 296 bytes"""
+    _fields_ = [("idum", C.c_longlong), ("idum2", C.c_longlong), ("iy", C.c_longlong),
+                ("iv", C.c_longlong*32), ("iset", C.c_int), ("gset", C.c_double)]
 
 
 class AkmiError(RuntimeError):
@@ -90,6 +99,10 @@ def lib():
         L.akmi_host_exchange_plan.restype = C.c_longlong
         L.akmi_host_exchange_plan.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                               C.c_longlong]
+        for f in ("akmi_rng_uniform", "akmi_rng_gaussian"):
+            getattr(L, f).restype = C.c_double
+            getattr(L, f).argtypes = [C.POINTER(RngState)]
+        L.akmi_turb_workspace_bytes.restype = C.c_longlong
         for f in ("akmi_sim_time", "akmi_sim_dt", "akmi_sim_tlim"):
             getattr(L, f).restype = C.c_double
         _LIB = L

@@ -1565,6 +1565,11 @@ void *akmi_sim_create(const char *deck_text, void *stream) {
   try {
     s = new Sim;
     s->pin.LoadFromString(deck_text);
+    // <turb_driving> (TurbulenceDriver, src/srcterms/turb_driver.cpp) runs on the Python host only: said here, before
+    // anything is allocated, rather than ignoring the block and leaving the fluid at rest
+    if (s->pin.DoesBlockExist("turb_driving"))
+      AKMI_FATAL("<turb_driving> is not on the C++ host's path: run a driven deck with the Python host "
+                 "(python -m athenak_amd)");
     s->pmesh = new Mesh(&s->pin, Comm::World().rank, Comm::World().nranks);
     s->pmesh->pmb_pack->AddPhysics(&s->pin);
     if (!stream) {

@@ -142,6 +142,12 @@ class FluidBase:
         from .diffusion import make_diffusion
         if make_diffusion(self, pin, blk):
             self.fused = False       # the flux adders work on the flux arrays of the task path
+        # <turb_driving>: AddForcing changes u0 between the fluxes and the RK update, after stage 1 has copied u0 into
+        # the second register; the fused stage kernels and the out-of-place first stage fold that copy into the
+        # update, so a driven run takes the task-granular chain with an explicit CopyCons (see _oop_first)
+        self.turb_driving = pin.DoesBlockExist("turb_driving")
+        if self.turb_driving:
+            self.fused = False
         self.counters = torch.zeros(3, dtype=torch.int32, device=device)
         self.dt3 = torch.zeros(3, dtype=torch.float64, device=device)
         self.dtnew = FLT_MAX
@@ -199,7 +205,7 @@ class FluidBase:
         (akmi_rk_update_oop, akmi_mhd_ct_oop) and the registers swapped -- no copy traffic.  Not with FOFC (its
         trial update reads u1/b1 before RKUpdate), RK4 (CopyCons updates the second register itself), or the
         update-in-the-sweeps option."""
-        return (stage == 1 and not self.fused and not self.use_fofc
+        return (stage == 1 and not self.fused and not self.use_fofc and not self.turb_driving
                 and pdrive.integrator != "rk4" and _TASK_OOP)
 
     @staticmethod

@@ -199,6 +199,7 @@ class MeshBlockPack:
         self.pmb = None
         self.phydro = None
         self.pmhd = None
+        self.pturb = None
         self.tl_map = {}
         for name in ("before_timeintegrator", "after_timeintegrator", "before_stagen",
                      "stagen", "after_stagen"):
@@ -211,6 +212,8 @@ class MeshBlockPack:
         """MeshBlockPack::AddPhysics (src/meshblock_pack.cpp:102-262): <hydro> / <mhd>."""
         from .hydro import Hydro
         from .mhd import MHD
+        from .turb_driver import turb_deck_checks
+        turb_deck_checks(pin)
         nphys = 0
         if pin.DoesBlockExist("hydro"):
             self.phydro = Hydro(self, pin)
@@ -225,6 +228,9 @@ class MeshBlockPack:
             self.phydro.AssembleHydroTasks(self.tl_map)
         if self.pmhd is not None:
             self.pmhd.AssembleMHDTasks(self.tl_map)
+        # (6) turbulence driver, meshblock_pack.cpp:177-189
+        from .turb_driver import add_turbulence_driver
+        self.pturb = add_turbulence_driver(self, pin)
 
 
 class Mesh:

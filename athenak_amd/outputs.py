@@ -70,7 +70,7 @@ class OutputMeshBlockInfo:
 
 # variable groups of basetype_output.cpp:196-520 for Newtonian hydro/MHD without scalars:
 # name -> list of (label, component, array)
-def _outvars(variable, is_mhd, is_ideal=True):
+def _outvars(variable, is_mhd, is_ideal=True, turb=False):
     blk = "mhd" if is_mhd else "hydro"
     u = [("dens", 0, "u0"), ("mom1", 1, "u0"), ("mom2", 2, "u0"), ("mom3", 3, "u0"), ("ener", 4, "u0")]
     w = [("dens", 0, "w0"), ("velx", 1, "w0"), ("vely", 2, "w0"), ("velz", 3, "w0"), ("eint", 4, "w0")]
@@ -85,6 +85,8 @@ def _outvars(variable, is_mhd, is_ideal=True):
     if is_mhd:
         table.update({"mhd_bcc": b, "mhd_u_bcc": u + b, "mhd_w_bcc": w + b, "mhd_bcc1": b[0:1],
                       "mhd_bcc2": b[1:2], "mhd_bcc3": b[2:3]})
+    if turb:                               # basetype_output.cpp:614-617: TurbulenceDriver::force
+        table["turb_force"] = [("force1", 0, "force"), ("force2", 1, "force"), ("force3", 2, "force")]
     if variable not in table:
         _fatal("Output variable '%s' not implemented on this path (choices: %s)"
                % (variable, ", ".join(sorted(table))))
@@ -100,7 +102,8 @@ class BaseTypeOutput:
         pk = pm.pmb_pack
         if op.file_type not in ("hst", "rst"):
             phys = pk.pmhd if pk.pmhd is not None else pk.phydro
-            self.outvars = _outvars(op.variable, pk.pmhd is not None, phys.peos.eos_data.is_ideal)
+            self.outvars = _outvars(op.variable, pk.pmhd is not None, phys.peos.eos_data.is_ideal,
+                                    getattr(pk, "pturb", None) is not None)
 
     def LoadOutputData(self, pm):
         """basetype_output.cpp:729-862: per-block index ranges (ghost zones, slices) and a
@@ -146,7 +149,8 @@ class BaseTypeOutput:
                 m = o.mb_gid - pk.gids
                 key = (arr, m, comp)
                 if key not in host:
-                    host[key] = _to_numpy(getattr(phys, arr)[m, comp])
+                    src = pk.pturb if arr == "force" else phys
+                    host[key] = _to_numpy(getattr(src, arr)[m, comp])
                 out[n, mi] = host[key][o.oks:o.oke + 1, o.ojs:o.oje + 1, o.ois:o.oie + 1]
         self.outarray = out
 
@@ -487,6 +491,14 @@ class Outputs:
                         _fatal("Slice at x%d=%g in output block '%s' is out of range of Mesh" % (q, x, name))
                     setattr(op, key, x)
                     setattr(op, "slice%d" % q, True)
+            if (op.file_type == "hst" and pin.DoesParameterExist("problem", "pgen_name")
+                    and pin.GetString("problem", "pgen_name") == "turb"):
+                # turb.cpp:247-396 adds its own history columns (TurbulentHistory); not built on this path
+                _fatal("hst output with <problem>/pgen_name = turb: the turbulence history columns are not on "
+                       "this path (output block '%s')" % name)
+            if op.file_type == "rst" and pin.DoesBlockExist("turb_driving"):
+                _fatal("rst output with <turb_driving>: restarting a driven run (force array and RNG state) is "
+                       "not on this path yet (output block '%s')" % name)
             if op.file_type == "hst":
                 op.user_hist_only = pin.GetOrAddBoolean(name, "user_hist_only", False)
                 if op.user_hist_only:

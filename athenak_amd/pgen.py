@@ -144,7 +144,7 @@ class ProblemGenerator:
         self.pgen_name = name
         table = {"linear_wave": self.LinearWave, "shock_tube": self.ShockTube,
                  "orszag_tang": self.OrszagTang, "blast": self.UserProblem, "diffusion": self.Diffusion,
-                 "cpaw": self.AlfvenWave}
+                 "cpaw": self.AlfvenWave, "turb": self.Turb}
         # user-defined boundary conditions (pgen.cpp:57-62): enrolled by the problem function
         self.user_bcs = any(b == capi.BC["user"] for b in pmesh.mesh_bcs)
         self.user_bcs_func = None
@@ -866,6 +866,68 @@ class ProblemGenerator:
         self._upload_cc(phys.b0.x1f, bf[0])
         self._upload_cc(phys.b0.x2f, bf[1])
         self._upload_cc(phys.b0.x3f, bf[2])
+
+    # ---- driven turbulence, src/pgen/fluids/turb.cpp:29-148 --------------------------
+    def Turb(self, pin, restart):
+        if restart:
+            return
+        pm = self.pmy_mesh_
+        pk = pm.pmb_pack
+        if pk.phydro is None and pk.pmhd is None:
+            raise RuntimeError("### FATAL ERROR Turbulence problem generator can only be run with Hydro and/or MHD")
+        cs = 1.0
+        if pk.phydro is not None:
+            cs = pin.GetOrAddReal("hydro", "iso_sound_speed", 1.0)
+        elif pk.pmhd is not None:
+            cs = pin.GetOrAddReal("mhd", "iso_sound_speed", 1.0)
+        beta = pin.GetOrAddReal("problem", "beta", 1.0)
+        n3, n2, n1 = pm.mb_indcs.ncells
+        nmb = pk.nmb_thispack
+        ks, js, is_ = self._active()
+        if pk.phydro is not None:
+            pin.GetOrAddReal("problem", "d_i", 1.0)
+            d_n = pin.GetOrAddReal("problem", "d_n", 1.0)
+            phys = pk.phydro
+            eos = phys.peos.eos_data
+            u = np.zeros((nmb, phys.nvars, n3, n2, n1))
+            u[:, IDN][:, ks, js, is_] = d_n
+            if eos.is_ideal:
+                gm1 = eos.gamma - 1.0
+                p0 = 1.0/eos.gamma
+                u[:, IEN][:, ks, js, is_] = p0/gm1 + 0.5*(0.0*0.0 + 0.0*0.0 + 0.0*0.0)/d_n
+            self._upload_cc(phys.u0, u)
+        if pk.pmhd is not None:
+            d_i = pin.GetOrAddReal("problem", "d_i", 1.0)
+            pin.GetOrAddReal("problem", "d_n", 1.0)
+            ifield = pin.GetOrAddInteger("problem", "ifield", 2)
+            if ifield not in (1, 2):
+                raise RuntimeError("### FATAL ERROR Invalid <problem>/ifield = %d, allowed values are 1 (zero-net-flux "
+                                   "Bz) or 2 (uniform Bz)." % ifield)
+            B0 = cs*math.sqrt(2.0*d_i/beta)
+            ms = pm.mesh_size
+            kx = 2.0*(math.pi/(ms.x1max - ms.x1min))
+            phys = pk.pmhd
+            eos = phys.peos.eos_data
+            gm1 = p0 = 0.0
+            if eos.is_ideal:
+                gm1 = eos.gamma - 1.0
+                p0 = d_i*(cs*cs)/eos.gamma
+                B0 = math.sqrt(2.0*p0/beta)
+            u = np.zeros((nmb, phys.nvars, n3, n2, n1))
+            _, bf = self._alloc_host()
+            kf = slice(ks.start, ks.stop + 1)
+            for m in range(nmb):
+                x1v = self._coords(m)[0]
+                bz = B0*np.sin(kx*x1v) if ifield == 1 else np.full_like(x1v, B0)
+                u[m, IDN][ks, js, is_] = d_i
+                bf[2][m][kf, js, is_] = bz                   # x1f, x2f stay zero
+                if eos.is_ideal:
+                    bz_cc = 0.5*(bz + bz)
+                    u[m, IEN][ks, js, is_] = p0/gm1 + 0.5*bz_cc*bz_cc + 0.5*(0.0*0.0 + 0.0*0.0 + 0.0*0.0)/d_i
+            self._upload_cc(phys.u0, u)
+            self._upload_cc(phys.b0.x1f, bf[0])
+            self._upload_cc(phys.b0.x2f, bf[1])
+            self._upload_cc(phys.b0.x3f, bf[2])
 
     # ---- blast (user problem in the reference: -D PROBLEM=fluids/blast) --------------
     def UserProblem(self, pin, restart):

@@ -715,6 +715,54 @@ int akmi_calib_copy(double *dst, const double *src, long long n, void *stream);
 int akmi_selftest_fp64(int mode, long long n, unsigned long long seed, long long *mismatch,
                        long long *shortform_waves, void *stream);
 
+/* ---- driven turbulence, <turb_driving> (src/srcterms/turb_driver.cpp) -------------------- *
+ * csrc/akmi_turb.hip.  Host-only entries (no GPU needed): the random generator, the mode list and
+ * amplitude table of InitializeModes, the sin/cos tables at cell centres.  Device entries, per cycle:
+ *   akmi_turb_synthesize      force_tmp = sum over modes (one pass), partial[m][4] = sum rho, sum rho*f1..3
+ *   akmi_turb_moments         force_tmp -= (t1,t2,t3)/t0, partial[m][2] = sum rho|f|^2, sum m.f
+ *   akmi_turb_add_forcing     force = fcorr*force + gcorr*(s*force_tmp); m += rho*f*dt (rho from u0);
+ *                             partial[m][4] = sum rho, sum m1..3 after the push
+ *   akmi_turb_remove_net_mom  m -= rho*t_c/t0
+ * force and force_tmp are (nmb, 3, N3, N2, N1) device arrays; only active cells are written.  partial[m][K]
+ * are per-MeshBlock sums over the active cells by a fixed-shape tree (no floating-point atomics); the caller
+ * sums them over all MeshBlocks in gid order.  work: akmi_turb_workspace_bytes() of device memory. */
+#define AKMI_RNG_NTAB 32
+/* RNG_State (src/utils/random.hpp:26-34); the cached second Gaussian deviate is iset/gset of the state */
+typedef struct akmi_rng_state {
+  long long idum, idum2, iy;
+  long long iv[AKMI_RNG_NTAB];
+  int iset;
+  double gset;
+} akmi_rng_state;
+/* ran2 (L'Ecuyer + Bays-Durham shuffle): uniform deviate in (0,1); idum < 0 (re)initialises */
+double akmi_rng_uniform(akmi_rng_state *st);
+/* Marsaglia polar Box-Muller on akmi_rng_uniform: standard normal deviate */
+double akmi_rng_gaussian(akmi_rng_state *st);
+int akmi_rng_state_bytes(void);            /* sizeof(akmi_rng_state): 296 */
+/* number of modes of (nlow, nhigh, driving_type 0|1), or AKMI_FAIL */
+int akmi_turb_mode_count(int nlow, int nhigh, int driving_type);
+/* one draw of InitializeModes (turb_driver.cpp:389-604): kvec[n][3] = (kx,ky,kz) and amp[n][24] (x, y, z
+ * components, each ccc ccs csc css scc scs ssc sss for the x-, y-, z-trig factors), normalised; either may be
+ * NULL (amp NULL: no deviates drawn).  lx, ly, lz: mesh extents.  Returns the mode count or AKMI_FAIL. */
+int akmi_turb_amplitudes(int nlow, int nhigh, int driving_type, double expo, double exp_prp, double exp_prl,
+                         double lx, double ly, double lz, akmi_rng_state *rstate, double *kvec, double *amp);
+/* host tables x?(m,n,i) [nmb][nmode][nx1], y? [..][nx2], z? [..][nx3] of sin/cos(k*x) at the cell centres of
+ * the active cells; bounds[m][6] = x1min x1max x2min x2max x3min x3max of each block; a collapsed dimension
+ * gets sin 0, cos 1 (turb_driver.cpp:226-270) */
+int akmi_turb_tables(int nmb, int nmode, int nx1, int nx2, int nx3, const double *kvec, const double *bounds,
+                     double *xs, double *xc, double *ys, double *yc, double *zs, double *zc);
+long long akmi_turb_workspace_bytes(const akmi_pack *p);
+int akmi_turb_synthesize(const akmi_pack *p, int nmode, const double *amp, const double *xs, const double *xc,
+                         const double *ys, const double *yc, const double *zs, const double *zc, const double *u0,
+                         double *force_tmp, double *partial, double *work, void *stream);
+int akmi_turb_moments(const akmi_pack *p, double t0, double t1, double t2, double t3, const double *u0,
+                      double *force_tmp, double *partial, double *work, void *stream);
+int akmi_turb_add_forcing(const akmi_pack *p, double fcorr, double gcorr, double s, double dt,
+                          const double *force_tmp, double *force, double *u0, double *partial, double *work,
+                          void *stream);
+int akmi_turb_remove_net_mom(const akmi_pack *p, double t0, double t1, double t2, double t3, double *u0,
+                             void *stream);
+
 #ifdef __cplusplus
 }
 #endif
