@@ -54,6 +54,7 @@ SYMBOLS = [
     "akmi_rng_uniform", "akmi_rng_gaussian", "akmi_rng_state_bytes", "akmi_turb_mode_count", "akmi_turb_amplitudes",
     "akmi_turb_tables", "akmi_turb_workspace_bytes", "akmi_turb_synthesize", "akmi_turb_moments", "akmi_turb_add_forcing",
     "akmi_turb_remove_net_mom",
+    "akmi_srcterms_apply", "akmi_srcterms_newdt", "akmi_srcterms_from_deck",
 ]
 
 _LIB = None
@@ -72,6 +73,14 @@ class RngState(C.Structure):
     """struct akmi_rng_state (RNG_State, src/utils/random.hpp:26-34): 296 bytes"""
     _fields_ = [("idum", C.c_longlong), ("idum2", C.c_longlong), ("iy", C.c_longlong),
                 ("iv", C.c_longlong*32), ("iset", C.c_int), ("gset", C.c_double)]
+
+
+class SrcTerms(C.Structure):
+    """struct akmi_srcterms (include/akmi.h)"""
+    _fields_ = [("const_accel", C.c_int), ("const_accel_dir", C.c_int), ("ism_cooling", C.c_int),
+                ("reserved", C.c_int), ("const_accel_val", C.c_double), ("hrate", C.c_double),
+                ("gamma", C.c_double), ("temp_unit", C.c_double), ("cooling_unit", C.c_double),
+                ("heating_unit", C.c_double)]
 
 
 class AkmiError(RuntimeError):

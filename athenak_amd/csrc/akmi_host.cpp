@@ -356,6 +356,7 @@ void Mesh::NewTimeStep(const Real tlim) {               // mesh.cpp:573-643
     if (f->has_visc) dt = std::min(dt, cfl_no*f->dt_visc);          // mesh.cpp:589-612
     if (f->has_resist) dt = std::min(dt, cfl_no*f->dt_resist);
     if (f->has_cond) dt = std::min(dt, cfl_no*f->dt_cond);
+    if (f->has_src) dt = std::min(dt, cfl_no*f->src_dtnew);         // mesh.cpp:597-598, :617-618
   }
   // minimum over all ranks (mesh.cpp:634-637): ncclAllReduce(ncclMin) on the compute stream
   // (already done on the device inside FinishNewDt when every physics module reports dt_reduced)
@@ -367,6 +368,85 @@ void Mesh::NewTimeStep(const Real tlim) {               // mesh.cpp:573-643
 }
 
 // ---- physics ----------------------------------------------------------------------------------
+// units::Units (src/units/units.hpp, units.cpp), the non-relativistic branch: the derived scales in the reference's
+// expressions and order of operations (they enter the cooling rate).  athenak_amd/units.py is the Python host's twin.
+namespace {
+struct Units {
+  static constexpr Real atomic_mass_unit_cgs = 1.660538921e-24, k_boltzmann_cgs = 1.3806488e-16;
+  Real length_cgs_, mass_cgs_, time_cgs_, mu_;
+  explicit Units(ParameterInput *pin)
+      : length_cgs_(pin->GetOrAddReal("units", "length_cgs", 1.0)), mass_cgs_(pin->GetOrAddReal("units", "mass_cgs", 1.0)),
+        time_cgs_(pin->GetOrAddReal("units", "time_cgs", 1.0)), mu_(pin->GetOrAddReal("units", "mu", 1.0)) {}
+  Real length_cgs() const { return length_cgs_; }
+  Real mass_cgs() const { return mass_cgs_; }
+  Real time_cgs() const { return time_cgs_; }
+  Real mu() const { return mu_; }
+  Real velocity_cgs() const { return length_cgs()/time_cgs(); }
+  Real density_cgs() const { return mass_cgs()/(length_cgs()*length_cgs()*length_cgs()); }
+  Real energy_cgs() const { return mass_cgs()*velocity_cgs()*velocity_cgs(); }
+  Real pressure_cgs() const { return energy_cgs()/(length_cgs()*length_cgs()*length_cgs()); }
+  Real temperature_cgs() const { return velocity_cgs()*velocity_cgs()*mu()*atomic_mass_unit_cgs/k_boltzmann_cgs; }
+};
+bool DeckTrue(const ParameterInput *pin, const std::string &b, const std::string &n) {
+  return pin->DoesParameterExist(b, n) && pin->GetBoolean(b, n);
+}
+}  // namespace
+
+// what a source-term block may not ask for (athenak_amd/srcterms.py srcterms_deck_checks says the same): called by
+// akmi_sim_create before anything is allocated
+void SrcTermsDeckChecks(const ParameterInput *pin) {
+  for (const std::string fluid : {"hydro", "mhd"}) {
+    const std::string blk = fluid + "_srcterms";
+    if (!pin->DoesBlockExist(fluid) || !pin->DoesBlockExist(blk)) continue;
+    for (const char *key : {"rel_cooling", "self_gravity", "rad_beam"})
+      if (DeckTrue(pin, blk, key))
+        AKMI_FATAL("<" + blk + ">/" + key + " = true is not on this path (const_accel and ism_cooling are)");
+    if (DeckTrue(pin, blk, "const_accel")) {
+      (void)pin->GetReal(blk, "const_accel_val");
+      const int dir = pin->GetInteger(blk, "const_accel_dir");
+      if (dir < 1 || dir > 3) AKMI_FATAL("<" + blk + ">/const_accel_dir must be 1, 2 or 3");
+    }
+    if (DeckTrue(pin, blk, "ism_cooling")) {
+      (void)pin->GetReal(blk, "hrate");
+      if (pin->GetString(fluid, "eos") != "ideal")
+        AKMI_FATAL("<" + blk + ">/ism_cooling = true needs the ideal-gas EOS (<" + fluid + ">/eos = " +
+                   pin->GetString(fluid, "eos") + ")");
+      if (!pin->DoesBlockExist("units"))      // (the reference dereferences the null punit here)
+        AKMI_FATAL("<" + blk + ">/ism_cooling = true needs a <units> block (length_cgs, mass_cgs, time_cgs, mu)");
+      if (DeckTrue(pin, "coord", "general_rel"))
+        AKMI_FATAL("<units> from a black-hole mass (<coord>/general_rel = true) is not on this path");
+    }
+  }
+}
+
+// SourceTerms::SourceTerms, srcterms.cpp:37-80: keys and defaults of <blk_srcterms>; false when the deck has no such block
+bool ParseSrcTerms(ParameterInput *pin, const std::string &blk, Real gamma, akmi_srcterms *c) {
+  *c = akmi_srcterms{};
+  c->const_accel_dir = 1;
+  c->gamma = gamma;
+  c->temp_unit = c->cooling_unit = c->heating_unit = 1.0;
+  const std::string sblk = blk + "_srcterms";
+  if (!pin->DoesBlockExist(sblk)) return false;
+  c->const_accel = pin->GetOrAddBoolean(sblk, "const_accel", false);
+  c->ism_cooling = pin->GetOrAddBoolean(sblk, "ism_cooling", false);
+  (void)pin->GetOrAddBoolean(sblk, "rel_cooling", false);
+  (void)pin->GetOrAddBoolean(sblk, "rad_beam", false);
+  (void)pin->GetOrAddBoolean(sblk, "self_gravity", false);
+  if (c->const_accel) {
+    c->const_accel_val = pin->GetReal(sblk, "const_accel_val");
+    c->const_accel_dir = pin->GetInteger(sblk, "const_accel_dir");
+  }
+  if (c->ism_cooling) {
+    c->hrate = pin->GetReal(sblk, "hrate");
+    const Units un(pin);                                    // srcterms.cpp:149-154
+    c->temp_unit = un.temperature_cgs();
+    const Real n_unit = un.density_cgs()/un.mu()/Units::atomic_mass_unit_cgs;
+    c->cooling_unit = un.pressure_cgs()/un.time_cgs()/n_unit/n_unit;
+    c->heating_unit = un.pressure_cgs()/un.time_cgs()/n_unit;
+  }
+  return true;
+}
+
 static int ReconFlag(const std::string &r) {
   if (r == "dc") return AKMI_RECON_DC;
   if (r == "plm") return AKMI_RECON_PLM;
@@ -487,8 +567,12 @@ FluidBase::FluidBase(MeshBlockPack *pp, ParameterInput *pin, const std::string &
     fofc.Realloc(static_cast<size_t>(pp->nmb_thispack)*n3*n2*n1);    // zero-filled
     nfofc.Realloc(1);
   }
+  // source terms, hydro.cpp:101-103 / mhd.cpp:137-139
+  has_src = ParseSrcTerms(pin, blk, e.gamma, &src_c);
+  if (has_src && src_c.ism_cooling) src_dt.Realloc(1);
 }
 FluidBase::~FluidBase() {
+  src_dt.Free();
   u0.Free(); w0.Free(); u1.Free(); w1.Free(); counters.Free(); dt3.Free(); ws.Free(); fofc.Free(); nfofc.Free();
   dtmin_cond.Free(); coarse_u0.Free(); coarse_w0.Free();
   delete psmr;
@@ -540,7 +624,7 @@ void FluidBase::FinishNewDt() {        // hydro_newdt.cpp:121-124
   dt_reduced = false;
   const bool several = pm->nranks > 1 || SelfExchange();
   if (several) Comm::World().ProfMark(Comm::kDtReduce, stream);
-  if (several && !has_visc && !has_cond && !has_resist)
+  if (several && !has_visc && !has_cond && !has_resist && !(has_src && src_c.ism_cooling))
     dt_reduced = Comm::World().AllReduceMinDevice(dt3.p, 3, stream);
   HIPCHK(hipMemcpyAsync(d, dt3.p, sizeof(d), hipMemcpyDeviceToHost, stream));
   if (several) Comm::World().ProfMark(Comm::kDtReduce, stream);
@@ -757,6 +841,9 @@ Driver::Driver(ParameterInput *pin, Mesh *pmesh) {       // driver.cpp:85-162
     if (!f) continue;
     ++nphys;
     if (!f->fused || f->multilevel || f->kinematic || f->stream == nullptr) use_graph = false;
+    // ism_cooling brings a second time-step constraint that is reduced on the host (like the diffusion time steps):
+    // neither a captured cycle nor run-ahead cycles; const_accel alone reads dt from device memory and keeps both
+    if (f->has_src && f->src_c.ism_cooling) use_graph = false;
   }
   if (pmesh->nranks > 1 || nphys != 1 || SelfExchange()) use_graph = false;
   // run-ahead cycles (akmi_host.hpp): the same eligibility, plus no diffusion time steps (they are reduced on the host)
@@ -766,7 +853,8 @@ Driver::Driver(ParameterInput *pin, Mesh *pmesh) {       // driver.cpp:85-162
   if (const char *e = std::getenv("AKMI_RUN_AHEAD")) run_ahead = std::atoi(e) != 0;
   for (FluidBase *f : phys) {
     if (!f) continue;
-    if (!f->fused || f->multilevel || f->kinematic || f->stream == nullptr || f->has_visc || f->has_cond || f->has_resist)
+    if (!f->fused || f->multilevel || f->kinematic || f->stream == nullptr || f->has_visc || f->has_cond || f->has_resist ||
+        (f->has_src && f->src_c.ism_cooling))
       run_ahead = false;
   }
   if (pmesh->nranks > 1 || nphys != 1 || SelfExchange() || use_graph) run_ahead = false;
@@ -994,6 +1082,25 @@ bool FluidBase::OopFirst(const Driver *d, int stage) const {
   return stage == 1 && !fused && !use_fofc && d->integrator != "rk4" && !off;
 }
 
+// HydroSrcTerms / MHDSrcTerms: psrc->ApplySrcTerms(w0, eos_data, beta*dt, u0) on the updated u0 (after an out-of-place
+// first stage: the register that carries the name now) and the old w0.  dt from device memory in run-ahead cycles and
+// captured cycle graphs, like every other task of those cycles.
+TaskStatus FluidBase::ApplySrcTerms(Driver *d, int stage) {
+  if (!SrcActive()) return TaskStatus::complete;
+  d->ProfMark(stream);
+  AKCHK(akmi_srcterms_apply(&pack_c, &src_c, d->beta[stage - 1], pmy_pack->pmesh->dt, dt_dev, w0.p, u0.p, stream));
+  d->ProfMark(stream);
+  return TaskStatus::complete;
+}
+void FluidBase::SrcNewDt() {            // srcterms_newdt.cpp:25-72
+  if (!has_src) return;
+  src_dtnew = static_cast<Real>(FLT_MAX);
+  if (!src_c.ism_cooling) return;
+  AKCHK(akmi_srcterms_newdt(&pack_c, &src_c, w0.p, src_dt.p, stream));
+  HIPCHK(hipMemcpyAsync(&src_dtnew, src_dt.p, sizeof(Real), hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+}
+
 void FluidBase::RestoreRegisters() {
   if (w_swapped) {             // the primitives back into the buffer akmi_sim_array handed out
     HIPCHK(hipMemcpyAsync(w1.p, w0.p, w0.n*sizeof(Real), hipMemcpyDeviceToDevice, stream));
@@ -1056,7 +1163,7 @@ TaskStatus Hydro::RKUpdate(Driver *d, int stage) {         // hydro_update.cpp:2
     // off-rank neighbours: only the sweeps + update here, so that SendU can post the halo messages
     // before the c2p of the active cells is enqueued
     StagePhase(d, stage, AKMI_PHASE_SWEEPS);
-  } else if (fused && !d->use_graph && FuseC2P() && BcsCommuteWithC2P() &&
+  } else if (fused && !d->use_graph && FuseC2P() && BcsCommuteWithC2P() && !SrcActive() &&
              akmi_hydro_stage_w_eligible(&pack_c, recon_method, rsolver_method)) {
     // the stage kernel converts the cells it finishes (their new state is in its registers) into the second primitive
     // array; ConToPrim then only has the ghost shell left (after the ghost fill): no pass that reads u0 back
@@ -1073,9 +1180,10 @@ TaskStatus Hydro::RKUpdate(Driver *d, int stage) {         // hydro_update.cpp:2
     if (wrote) { SwapArr(w0, w1); w_swapped = !w_swapped; }
     interior_done_ = true; dt_ready_ = do_dt;
     want_ghost_c2p_ = true;
-  } else if (fused && !d->use_graph && MergeC2P()) {
+  } else if (fused && ((!d->use_graph && MergeC2P()) || SrcActive())) {
     // no off-rank neighbour: ONE ConsToPrim over all cells after the ghost fill (ConToPrim) instead of c2p of the
-    // active cells here + c2p of the ghost shell there (thin slabs): 512 blocks of 32^3 1518 -> 1726 Mcell-updates/s
+    // active cells here + c2p of the ghost shell there (thin slabs): 512 blocks of 32^3 1518 -> 1726 Mcell-updates/s.
+    // With source terms always (captured cycles too): they change u0 after this call and before it is converted.
     StagePhase(d, stage, AKMI_PHASE_SWEEPS);
   } else if (fused) {
     int do_dt = (stage == d->nexp_stages);
@@ -1227,6 +1335,7 @@ TaskStatus Hydro::NewTimeStep(Driver *d, int stage) {      // hydro_newdt.cpp:30
   if (d->ra_active) { d->EnqueueMeshNewDt(this); return TaskStatus::complete; }
   FinishNewDt();
   DiffusionNewDt();
+  SrcNewDt();
   return TaskStatus::complete;
 }
 }  // namespace hydro
@@ -1271,8 +1380,10 @@ TaskStatus MHD::RKUpdate(Driver *d, int stage) {           // mhd_update.cpp:24-
   Real beta_dt = d->beta[stage - 1]*pmy_pack->pmesh->dt;
   if (fused && peers()) {
     StagePhase(d, stage, AKMI_PHASE_SWEEPS);
-  } else if (fused && !d->use_graph && MergeC2P()) {
-    StagePhase(d, stage, AKMI_PHASE_SWEEPS | AKMI_PHASE_EMF_CT);      // see Hydro::RKUpdate
+  } else if (fused && ((!d->use_graph && MergeC2P()) || SrcActive())) {
+    // see Hydro::RKUpdate.  Source terms run after this call: CornerE and CT neither read nor write u0, so that gives the
+    // bits of applying them between the two phases.
+    StagePhase(d, stage, AKMI_PHASE_SWEEPS | AKMI_PHASE_EMF_CT);
   } else if (fused) {
     int do_dt = (stage == d->nexp_stages);
     const int copy = CopyFlag(d, stage, AKMI_PHASE_ALL);
@@ -1537,6 +1648,7 @@ TaskStatus MHD::NewTimeStep(Driver *d, int stage) {        // mhd_newdt.cpp:31-1
   if (d->ra_active) { d->EnqueueMeshNewDt(this); return TaskStatus::complete; }
   FinishNewDt();
   DiffusionNewDt();
+  SrcNewDt();
   return TaskStatus::complete;
 }
 }  // namespace mhd
@@ -1570,6 +1682,7 @@ void *akmi_sim_create(const char *deck_text, void *stream) {
     if (s->pin.DoesBlockExist("turb_driving"))
       AKMI_FATAL("<turb_driving> is not on the C++ host's path: run a driven deck with the Python host "
                  "(python -m athenak_amd)");
+    SrcTermsDeckChecks(&s->pin);
     s->pmesh = new Mesh(&s->pin, Comm::World().rank, Comm::World().nranks);
     s->pmesh->pmb_pack->AddPhysics(&s->pin);
     if (!stream) {
@@ -1618,6 +1731,18 @@ int akmi_sim_execute(void *h, int max_cycles) {
 /* live timing of the fused-stage launch group: on != 0 starts recording a HIP event pair on the launch stream
  * around every akmi_*_stage_fused / akmi_*_stage_phase call; akmi_sim_profile_read waits for the recorded
  * events, returns their summed duration and count, and clears the record */
+/* host-only: the C++ host's reading of the source-term block of `fluid` ("hydro" | "mhd") */
+int akmi_srcterms_from_deck(const char *deck_text, const char *fluid, akmi_srcterms *out) {
+  AKMI_C_ENTRY("akmi_srcterms_from_deck", AKMI_FAIL,
+    ParameterInput pin;
+    pin.LoadFromString(deck_text);
+    SrcTermsDeckChecks(&pin);
+    const std::string blk(fluid);
+    const Real gamma = (pin.DoesBlockExist(blk) && pin.GetString(blk, "eos") == "ideal") ? pin.GetReal(blk, "gamma") : 0.0;
+    return ParseSrcTerms(&pin, blk, gamma, out) ? 1 : 0;
+  )
+}
+
 int akmi_sim_profile(void *h, int on) {
   Sim *s = static_cast<Sim *>(h);
   if (!s->pdriver) { akmi::set_error("akmi_sim_profile: call akmi_sim_initialize first"); return AKMI_FAIL; }

@@ -73,6 +73,8 @@ struct HostError : std::runtime_error { using std::runtime_error::runtime_error;
 #define AKMI_THROW(msg) ::akmi::host::Throw(__FILE__, __LINE__, (msg))
 // the body of a C entry point: what it returns on an exception, then the statements
 void NoteException(const char *entry) noexcept;      // message of the exception in flight -> akmi_last_error()
+bool ParseSrcTerms(ParameterInput *pin, const std::string &blk, Real gamma, akmi_srcterms *c);   // srcterms.cpp:37-80
+void SrcTermsDeckChecks(const ParameterInput *pin);  // refusals of <hydro_srcterms> / <mhd_srcterms>, before anything is allocated
 #define AKMI_C_ENTRY(entry, on_error, ...)                               \
   try { __VA_ARGS__ }                                                    \
   catch (...) { ::akmi::host::NoteException(entry); return on_error; }
@@ -394,6 +396,15 @@ class FluidBase {
   Real dt_visc = static_cast<Real>(FLT_MAX), dt_cond = static_cast<Real>(FLT_MAX),
        dt_resist = static_cast<Real>(FLT_MAX);
   DvceArray<Real> dtmin_cond;
+  // physical source terms (src/srcterms/srcterms.cpp): psrc of the reference exists iff the deck holds <blk_srcterms>;
+  // const_accel and ism_cooling are on this path (akmi_srcterms_apply / _newdt), the others stop in SrcTermsDeckChecks
+  bool has_src = false;
+  akmi_srcterms src_c{};
+  Real src_dtnew = static_cast<Real>(FLT_MAX);     // SourceTerms::dtnew
+  DvceArray<Real> src_dt;                          // its device copy (ism_cooling only)
+  bool SrcActive() const { return has_src && (src_c.const_accel || src_c.ism_cooling); }
+  TaskStatus ApplySrcTerms(Driver *d, int stage);  // the body of HydroSrcTerms / MHDSrcTerms
+  void SrcNewDt();                                 // hydro_newdt.cpp:135-137, mhd_newdt.cpp:169-171
   bool use_fofc = false;                // hydro.hpp:116-117, mhd.hpp
   bool OopFirst(const Driver *d, int stage) const;     // first stage of the task path out of place (akmi_host.cpp)
   bool dt_reduced = false;              // dtnew is already the minimum over all ranks (FinishNewDt)
@@ -452,7 +463,7 @@ class Hydro : public FluidBase {    // hydro.hpp:73-154
   TaskStatus SendFlux(Driver *d, int stage);
   TaskStatus RecvFlux(Driver *d, int stage);
   TaskStatus RKUpdate(Driver *d, int stage);
-  TaskStatus HydroSrcTerms(Driver *d, int stage) { return TaskStatus::complete; }
+  TaskStatus HydroSrcTerms(Driver *d, int stage) { return ApplySrcTerms(d, stage); }   // hydro_tasks.cpp:237-241
   TaskStatus RestrictU(Driver *d, int stage);
   TaskStatus SendU(Driver *d, int stage);
   TaskStatus RecvU(Driver *d, int stage);
@@ -484,7 +495,7 @@ class MHD : public FluidBase {      // mhd.hpp:93-199
   TaskStatus SendFlux(Driver *d, int stage);
   TaskStatus RecvFlux(Driver *d, int stage);
   TaskStatus RKUpdate(Driver *d, int stage);
-  TaskStatus MHDSrcTerms(Driver *d, int stage) { return TaskStatus::complete; }
+  TaskStatus MHDSrcTerms(Driver *d, int stage) { return ApplySrcTerms(d, stage); }     // mhd_tasks.cpp:254-258
   TaskStatus RestrictU(Driver *d, int stage);
   TaskStatus SendU(Driver *d, int stage);
   TaskStatus RecvU(Driver *d, int stage);

@@ -148,6 +148,11 @@ class FluidBase:
         self.turb_driving = pin.DoesBlockExist("turb_driving")
         if self.turb_driving:
             self.fused = False
+        # physical source terms, hydro.cpp:101-103 / mhd.cpp:137-139: psrc exists iff the fluid's block does
+        self.psrc = None
+        if pin.DoesBlockExist(blk + "_srcterms"):
+            from .srcterms import SourceTerms
+            self.psrc = SourceTerms(blk + "_srcterms", self, pin)
         self.counters = torch.zeros(3, dtype=torch.int32, device=device)
         self.dt3 = torch.zeros(3, dtype=torch.float64, device=device)
         self.dtnew = FLT_MAX
@@ -199,6 +204,22 @@ class FluidBase:
             dtnew = min(dtnew, float(d[2]))
         self.dtnew = dtnew
 
+
+    def _has_srcterms(self):
+        return self.psrc is not None and self.psrc.active
+
+    def _srcterms(self, pdrive, stage):
+        """HydroSrcTerms / MHDSrcTerms (hydro_tasks.cpp:237-241, mhd_tasks.cpp:254-258):
+        psrc->ApplySrcTerms(w0, eos_data, beta*dt, u0) on the updated u0 (after an out-of-place first stage: the register
+        that now carries that name) and the old w0, before u0 is packed, exchanged or converted"""
+        if self._has_srcterms():
+            self.psrc.ApplySrcTerms(self.w0, pdrive.beta[stage - 1], self.pmy_pack.pmesh.dt, self.u0)
+        return TaskStatus.complete
+
+    def _srcterms_newdt(self):
+        """hydro_newdt.cpp:135-137, mhd_newdt.cpp:169-171"""
+        if self.psrc is not None:
+            self.psrc.NewTimeStep(self.w0)
 
     def _oop_first(self, pdrive, stage):
         """task-granular path, first stage: CopyCons folded into an out-of-place RKUpdate / CT
@@ -291,8 +312,12 @@ class Hydro(FluidBase):
     def _noop(self, pdrive, stage):
         return TaskStatus.complete
 
-    InitRecv = HydroSrcTerms = SendU_OA = RecvU_OA = _noop
+    InitRecv = SendU_OA = RecvU_OA = _noop
     SendU_Shr = RecvU_Shr = ClearSend = ClearRecv = _noop
+
+    def HydroSrcTerms(self, pdrive, stage):
+        """hydro_tasks.cpp:237-241: if (psrc != nullptr) psrc->ApplySrcTerms(w0, peos->eos_data, beta_dt, u0)"""
+        return self._srcterms(pdrive, stage)
 
     def SendFlux(self, pdrive, stage):
         """hydro_tasks.cpp:206-215: restricted fluxes at fine/coarse boundaries (SMR only)"""
@@ -378,9 +403,9 @@ class Hydro(FluidBase):
             # the stage kernel converts the cells it finishes (their new state is in its registers) into the second
             # primitive array; ConToPrim then only has the ghost shell left (after the ghost fill)
             self._stage_w(pdrive, stage)
-        elif self.fused and _MERGE_C2P:
+        elif self.fused and (_MERGE_C2P or self._has_srcterms()):
             # no off-rank neighbour: ONE ConsToPrim over all cells after the ghost fill (ConToPrim below) instead of
-            # c2p(active cells) here + c2p(ghost shell) there
+            # c2p(active cells) here + c2p(ghost shell) there.  (With source terms always: they change u0 after this.)
             self._stage_phase(pdrive, stage, capi.PHASE_SWEEPS)
         elif self.fused:
             # pass A + ConsToPrim of the active cells (+ CFL scan on the last stage) in one
@@ -404,6 +429,8 @@ class Hydro(FluidBase):
         ConsToPrim (neighbour / periodic copies, outflow, reflect), no user boundary function"""
         fn = getattr(self.L, "akmi_hydro_stage_w_eligible", None) if not hasattr(self.L, "R") else None   # (the CPU stand-in
         if not fn or self.pbval_u.peers:                                                                    # of the tests has none)
+            return False
+        if self._has_srcterms():      # the source terms need the updated u0 before it is converted: separate ConsToPrim pass
             return False
         pgen = self.pmy_pack.pmesh.pgen
         if pgen is not None and pgen.user_bcs:
@@ -575,4 +602,5 @@ class Hydro(FluidBase):
         self._dt_ready = False
         self._finish_newdt()
         self._diffusion_newdt()
+        self._srcterms_newdt()
         return TaskStatus.complete

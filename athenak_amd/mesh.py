@@ -213,7 +213,14 @@ class MeshBlockPack:
         from .hydro import Hydro
         from .mhd import MHD
         from .turb_driver import turb_deck_checks
+        from .srcterms import srcterms_deck_checks
         turb_deck_checks(pin)
+        srcterms_deck_checks(pin)
+        # (1) units, meshblock_pack.cpp:108-112: created iff the block exists
+        self.punit = None
+        if pin.DoesBlockExist("units"):
+            from .units import Units
+            self.punit = Units(pin)
         nphys = 0
         if pin.DoesBlockExist("hydro"):
             self.phydro = Hydro(self, pin)
@@ -350,6 +357,8 @@ class Mesh:
             for d in (ph.pvisc, ph.presist, ph.pcond):
                 if d is not None:
                     self.dt = min(self.dt, self.cfl_no*d.dtnew)
+            if getattr(ph, "psrc", None) is not None:        # source terms: mesh.cpp:597-598, :617-618
+                self.dt = min(self.dt, self.cfl_no*ph.psrc.dtnew)
         if self.nranks > 1:
             # MPI_Allreduce(MIN) of one Real, mesh.cpp:634-637
             import torch

@@ -90,9 +90,13 @@ class MHD(FluidBase):
     def _noop(self, pdrive, stage):
         return TaskStatus.complete
 
-    SaveMHDState = InitRecv = MHDSrcTerms = SendU_OA = RecvU_OA = _noop
+    SaveMHDState = InitRecv = SendU_OA = RecvU_OA = _noop
     SendU_Shr = RecvU_Shr = SendB_OA = RecvB_OA = _noop
     SendB_Shr = RecvB_Shr = ClearSend = ClearRecv = _noop
+
+    def MHDSrcTerms(self, pdrive, stage):
+        """mhd_tasks.cpp:254-258: if (psrc != nullptr) psrc->ApplySrcTerms(w0, peos->eos_data, beta_dt, u0)"""
+        return self._srcterms(pdrive, stage)
 
     def SendE(self, pdrive, stage):
         """mhd_tasks.cpp:402-417 (PackAndSendFluxFC + RecvAndUnpackFluxFC).  On a uniform mesh every
@@ -207,7 +211,9 @@ class MHD(FluidBase):
             # remaining kernels:  sweeps+update | SendU | CornerE+CT | SendB | c2p of the
             # active cells | RecvU, RecvB | BCs | c2p of the ghost shell
             self._stage_phase(pdrive, stage, capi.PHASE_SWEEPS)
-        elif self.fused and _MERGE_C2P:
+        elif self.fused and (_MERGE_C2P or self._has_srcterms()):
+            # (source terms: they change u0 after this call -- CornerE and CT read neither u0 nor write it, so applying them
+            # after phase 2 gives the bits of applying them between phases 1 and 2 -- and ConsToPrim has to see the result)
             # no off-rank neighbour: nothing travels underneath an early conversion of the active cells, so the
             # stage ends with ONE ConsToPrim over all cells incl. the ghost zones, after the ghost fill
             # (ConToPrim below), instead of c2p(active) here + c2p(ghost shell, thin slabs) there
@@ -389,4 +395,5 @@ class MHD(FluidBase):
         self._dt_ready = False
         self._finish_newdt()
         self._diffusion_newdt()
+        self._srcterms_newdt()
         return TaskStatus.complete

@@ -144,7 +144,7 @@ class ProblemGenerator:
         self.pgen_name = name
         table = {"linear_wave": self.LinearWave, "shock_tube": self.ShockTube,
                  "orszag_tang": self.OrszagTang, "blast": self.UserProblem, "diffusion": self.Diffusion,
-                 "cpaw": self.AlfvenWave, "turb": self.Turb}
+                 "cpaw": self.AlfvenWave, "turb": self.Turb, "rt": self.RayleighTaylor}
         # user-defined boundary conditions (pgen.cpp:57-62): enrolled by the problem function
         self.user_bcs = any(b == capi.BC["user"] for b in pmesh.mesh_bcs)
         self.user_bcs_func = None
@@ -925,6 +925,86 @@ class ProblemGenerator:
                     bz_cc = 0.5*(bz + bz)
                     u[m, IEN][ks, js, is_] = p0/gm1 + 0.5*bz_cc*bz_cc + 0.5*(0.0*0.0 + 0.0*0.0 + 0.0*0.0)/d_i
             self._upload_cc(phys.u0, u)
+            self._upload_cc(phys.b0.x1f, bf[0])
+            self._upload_cc(phys.b0.x2f, bf[1])
+            self._upload_cc(phys.b0.x3f, bf[2])
+
+    # ---- Rayleigh-Taylor instability, src/pgen/fluids/rt.cpp:53-252 -------------------
+    def RayleighTaylor(self, pin, restart):
+        """iprob = 1 (single-mode velocity perturbation), 2-D (interface at x2 = 0, sharp or smooth) and 3-D (x3 = 0).
+        iprob = 2, 3 draw from a Kokkos random pool that cannot be restated and are refused.  The acceleration is read
+        from the source-term block of the fluid (the reference's generator asks <hydro> / <mhd> for const_accel_val,
+        a key its own deck holds in <hydro_srcterms>).  3-D MHD: the reference sets no field there; <problem>/b0
+        (default 0) gives a uniform B_x as in 2-D."""
+        if restart:
+            return
+        pm = self.pmy_mesh_
+        pk = pm.pmb_pack
+        if pm.one_d:
+            raise RuntimeError("### FATAL ERROR rti problem generator only works in 2D/3D")
+        ms = pm.mesh_size
+        kx = 2.0*(math.pi)/(ms.x1max - ms.x1min)
+        ky = 2.0*(math.pi)/(ms.x2max - ms.x2min)
+        kz = 2.0*(math.pi)/(ms.x3max - ms.x3min)
+        amp = pin.GetReal("problem", "amp")
+        iprob = pin.GetInteger("problem", "iprob")
+        drat = pin.GetOrAddReal("problem", "drat", 3.0)
+        smooth = pin.GetOrAddBoolean("problem", "smooth_interface", False)
+        if iprob != 1:
+            raise RuntimeError("### FATAL ERROR <problem>/iprob = %d of the rt problem draws from a random pool that "
+                               "is not on this path (iprob = 1: single mode)" % iprob)
+        is_mhd = pk.pmhd is not None
+        phys = self._phys()
+        blk = "mhd" if is_mhd else "hydro"
+        eos = phys.peos.eos_data
+        if not eos.is_ideal:
+            raise RuntimeError("### FATAL ERROR the rt problem needs the ideal-gas EOS")
+        sblk = blk + "_srcterms"
+        if not (pin.DoesBlockExist(sblk) and pin.DoesParameterExist(sblk, "const_accel_val")):
+            raise RuntimeError("### FATAL ERROR the rt problem needs <%s>/const_accel_val" % sblk)
+        grav_acc = pin.GetReal(sblk, "const_accel_val")
+        gm1 = eos.gamma - 1.0
+        p0 = 1.0/eos.gamma
+        p0 = pin.GetOrAddReal("problem", "p0", p0)
+        if pm.two_d:
+            p0 -= grav_acc*ms.x2max
+        else:
+            p0 -= grav_acc*ms.x3max
+        bx = 0.0
+        if is_mhd:
+            bx = pin.GetReal("problem", "b0") if pm.two_d else pin.GetOrAddReal("problem", "b0", 0.0)
+        n3, n2, n1 = pm.mb_indcs.ncells
+        nmb = pk.nmb_thispack
+        ks, js, is_ = self._active()
+        u = np.zeros((nmb, phys.nvars, n3, n2, n1))
+        _, bf = self._alloc_host()
+        for m in range(nmb):
+            x1v, x2v, x3v = self._coords(m)[:3]
+            X3, X2, X1 = np.meshgrid(x3v, x2v, x1v, indexing="ij")
+            den = np.ones_like(X1)
+            if pm.two_d:
+                sigma = 0.01
+                if smooth:
+                    den = 0.5*((drat + 1.0) + (drat - 1.0)*np.tanh(X2/sigma))
+                else:
+                    den = np.where(X2 > 0.0, den*drat, den)
+                mom = (1.0 + np.cos(kx*X1))*(1.0 + np.cos(ky*X2))/4.0
+                mom = mom*(den*amp)
+                xg, IMG = X2, IVY
+            else:
+                den = np.where(X3 > 0.0, den*drat, den)
+                mom = (1.0 + np.cos(kx*X1))*(1.0 + np.cos(ky*X2))*(1.0 + np.cos(kz*X3))/8.0
+                mom = mom*(den*amp)
+                xg, IMG = X3, IVZ
+            u[m, IDN][ks, js, is_] = den
+            u[m, IMG][ks, js, is_] = mom
+            en = (p0 + grav_acc*den*xg)/gm1 + 0.5*(mom*mom)/den
+            if is_mhd:
+                bf[0][m][ks, js, is_.start:is_.stop + 1] = bx
+                en = en + 0.5*bx*bx
+            u[m, IEN][ks, js, is_] = en
+        self._upload_cc(phys.u0, u)
+        if is_mhd:
             self._upload_cc(phys.b0.x1f, bf[0])
             self._upload_cc(phys.b0.x2f, bf[1])
             self._upload_cc(phys.b0.x3f, bf[2])

@@ -763,6 +763,39 @@ int akmi_turb_add_forcing(const akmi_pack *p, double fcorr, double gcorr, double
 int akmi_turb_remove_net_mom(const akmi_pack *p, double t0, double t1, double t2, double t3, double *u0,
                              void *stream);
 
+/* ---- physical source terms, <hydro_srcterms> / <mhd_srcterms> (src/srcterms/srcterms.cpp) ---------- *
+ * csrc/akmi_srcterms.hip.  The parameters of the enabled terms in one plain struct; the three unit factors are
+ * formed on the host with the reference's expressions (srcterms.cpp:149-154) from <units>:
+ *   temp_unit    = temperature_cgs()
+ *   cooling_unit = pressure_cgs()/time_cgs()/n_unit/n_unit,   n_unit = density_cgs()/mu()/atomic_mass_unit_cgs
+ *   heating_unit = pressure_cgs()/time_cgs()/n_unit
+ * They are read only with ism_cooling != 0. */
+typedef struct akmi_srcterms {
+  int const_accel;         /* constant acceleration on/off */
+  int const_accel_dir;     /* 1, 2 or 3 */
+  int ism_cooling;         /* optically thin ISM cooling + heating on/off (ideal gas only) */
+  int reserved;
+  double const_accel_val;  /* g */
+  double hrate;            /* heating rate [erg/s] */
+  double gamma;            /* adiabatic index of the EOS */
+  double temp_unit, cooling_unit, heating_unit;
+} akmi_srcterms;
+/* SourceTerms::ApplySrcTerms (srcterms.cpp:93-101): one launch applies the enabled terms to the active cells of all
+ * MeshBlocks, reading the OLD primitives w0 and updating u0 in place, constant acceleration first, then cooling, each
+ * value with the reference's sequence of roundings.  bdt = beta*dt with dt read from dt_dev[0] when dt_dev is not
+ * NULL (the form of akmi_*_stage_phase_dt: run-ahead cycles and captured cycle graphs), else the argument dt.
+ * Ghost zones are not touched.  Nothing enabled: no launch. */
+int akmi_srcterms_apply(const akmi_pack *p, const akmi_srcterms *s, double beta, double dt, const double *dt_dev,
+                        const double *w0, double *u0, void *stream);
+/* SourceTerms::NewTimeStep (srcterms_newdt.cpp:25-72): *dtmin (device) = min over the active cells of
+ * eint/(FLT_MIN + |rho*(rho*lambda - gamma_heating)|), starting from (double)FLT_MAX (which is what it stays at
+ * without ism_cooling). */
+int akmi_srcterms_newdt(const akmi_pack *p, const akmi_srcterms *s, const double *w0, double *dtmin, void *stream);
+/* Host-only (no GPU needed): how the C++ host reads the source-term block of `fluid` ("hydro" or "mhd") of a deck --
+ * keys, defaults and the unit factors from <units>.  Returns 1 and fills *out when the deck holds <fluid_srcterms>,
+ * 0 when it does not; a deck the host refuses ends the process with "### FATAL ERROR", as akmi_sim_create does. */
+int akmi_srcterms_from_deck(const char *deck_text, const char *fluid, akmi_srcterms *out);
+
 #ifdef __cplusplus
 }
 #endif
