@@ -55,7 +55,12 @@ SYMBOLS = [
     "akmi_turb_tables", "akmi_turb_workspace_bytes", "akmi_turb_synthesize", "akmi_turb_moments", "akmi_turb_add_forcing",
     "akmi_turb_remove_net_mom",
     "akmi_srcterms_apply", "akmi_srcterms_newdt", "akmi_srcterms_from_deck",
+    "akmi_derived_ncomp", "akmi_derived_var", "akmi_sim_derived",
 ]
+
+# AKMI_DV_* of include/akmi.h: `which` of akmi_derived_var
+DERIVED = {"temperature": 0, "wz": 1, "w2": 2, "jz": 3, "j2": 4, "curv": 5, "k_jxb": 6, "curv_perp": 7, "bmag": 8,
+           "divb": 9}
 
 _LIB = None
 

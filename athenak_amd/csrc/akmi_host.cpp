@@ -1789,6 +1789,24 @@ void *akmi_sim_array(void *h, const char *name, long long *count) {
   )
 }
 
+/* a derived output variable (AKMI_DV_*) of the present state into the caller's device array, on the stream of the
+ * simulation; after akmi_sim_execute the named registers hold the state (RestoreRegisters) */
+int akmi_sim_derived(void *h, int which, double *out) {
+  AKMI_C_ENTRY("akmi_sim_derived", AKMI_FAIL,
+    Sim *s = static_cast<Sim *>(h);
+    s->Enter();
+    MeshBlockPack *pk = s->pmesh->pmb_pack;
+    FluidBase *f = pk->phydro ? static_cast<FluidBase *>(pk->phydro) : static_cast<FluidBase *>(pk->pmhd);
+    auto *m = pk->pmhd;
+    const int rc = akmi_derived_var(&f->pack_c, which, f->w0.p, f->u0.p, m ? m->bcc0.p : nullptr, m ? m->b0.x1f.p : nullptr,
+                                    m ? m->b0.x2f.p : nullptr, m ? m->b0.x3f.p : nullptr, out, akmi_derived_ncomp(which),
+                                    f->stream);
+    if (rc != AKMI_COMPLETE) return rc;
+    HIPCHK(hipStreamSynchronize(f->stream));
+    return AKMI_COMPLETE;
+  )
+}
+
 const int *akmi_sim_lloc(void *h) { return static_cast<Sim *>(h)->pmesh->lloc_eachmb.data(); }
 int akmi_sim_gids(void *h) { return static_cast<Sim *>(h)->pmesh->pmb_pack->gids; }
 int akmi_sim_nmb_thisrank(void *h) { return static_cast<Sim *>(h)->pmesh->pmb_pack->nmb_thispack; }

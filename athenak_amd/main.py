@@ -62,6 +62,14 @@ class Simulation:
         pk = self.pmesh.pmb_pack
         return pk.phydro if pk.phydro is not None else pk.pmhd
 
+    def derived(self, name):
+        """a derived output variable of the present state ("mhd_j2", "hydro_wz", ... or "temperature") as a
+        (nmb, 1, N3, N2, N1) tensor, as NativeSimulation.derived"""
+        from .outputs import derived_array, derived_which
+        ph = self.phys
+        which, _, _ = derived_which(name, self.pmesh.pmb_pack.pmhd is not None, ph.peos.eos_data.is_ideal)
+        return derived_array(ph, which)
+
     def Execute(self, max_cycles=None):
         return self.pdriver.Execute(self.pmesh, self.pin, max_cycles)
 

@@ -113,6 +113,17 @@ class NativeSimulation:
         self.pmesh.ncycle = self.ncycle
         return n
 
+    def derived(self, name):
+        """a derived output variable of the present state ("mhd_j2", "hydro_wz", ... or "temperature") as a
+        (nmb, 1, N3, N2, N1) tensor: akmi_sim_derived runs the kernel of the outputs on the native arrays"""
+        from .outputs import derived_which
+        is_mhd, nmb, _, n3, n2, n1 = self._shape
+        which, ncomp, _ = derived_which(name, is_mhd, self._phys.peos.eos_data.is_ideal)
+        out = torch.empty((nmb, ncomp, n3, n2, n1), dtype=torch.float64, device="cuda")
+        torch.cuda.synchronize()
+        capi.check(self.L.akmi_sim_derived(self.h, which, capi._p(out)), "sim_derived")
+        return out
+
     time = property(lambda s: s.L.akmi_sim_time(s.h))
     dt = property(lambda s: s.L.akmi_sim_dt(s.h))
     tlim = property(lambda s: s.L.akmi_sim_tlim(s.h))

@@ -68,29 +68,98 @@ class OutputMeshBlockInfo:
         self.x3min, self.x3max = size.x3min, size.x3max
 
 
-# variable groups of basetype_output.cpp:196-520 for Newtonian hydro/MHD without scalars:
-# name -> list of (label, component, array)
-def _outvars(variable, is_mhd, is_ideal=True, turb=False):
+# derived variables of derived_variables.cpp that this path computes (akmi_derived_var, csrc/akmi_derived.hip):
+# output name -> (key of capi.DERIVED, label of basetype_output.cpp:486-559)
+_DERIVED = {"hydro_wz": ("wz", "vorz"), "hydro_w2": ("w2", "vor2"), "mhd_wz": ("wz", "vorz"), "mhd_w2": ("w2", "vor2"),
+            "mhd_jz": ("jz", "jz"), "mhd_j2": ("j2", "j2"), "mhd_curv": ("curv", "curv"),
+            "mhd_k_jxb": ("k_jxb", "k_jxb"), "mhd_curv_perp": ("curv_perp", "curv_perp"),
+            "mhd_bmag": ("bmag", "bmag"), "mhd_divb": ("divb", "divb")}
+
+# names of the reference that stay refused, each with what it would need
+_REFUSED = {"mhd_jcon": "it needs the saved state of SaveMHDState",
+            "hydro_sgs": "the sub-grid-scale tensors are not on this path",
+            "mhd_sgs": "the sub-grid-scale tensors are not on this path",
+            "mhd_dynamo_ks": "the dynamo wavenumber scales are not on this path",
+            "mhd_curv_alt": "the alternative curvature is not on this path",
+            "mhd_t": "the temperature array of DynGRMHD does not exist on this path"}
+
+
+def derived_which(name, is_mhd, is_ideal=True):
+    """(which, ncomp, label) of a derived variable by output name or by plain key ("temperature", "wz", ...);
+    the names this path does not compute stop here with a message that names them"""
+    if name in _REFUSED or name.endswith("_moments") or name.startswith(("rad", "prtcl")):
+        why = _REFUSED.get(name, "radiation, particle and moment outputs are not on this path")
+        _fatal("Output variable '%s' is not implemented on this path: %s" % (name, why))
+    if name in _DERIVED:
+        key, label = _DERIVED[name]
+        if name.startswith("mhd_" if not is_mhd else "hydro_"):
+            _fatal("Output of %s variable '%s' requested but no %s object has been constructed"
+                   % (("MHD", name, "MHD") if not is_mhd else ("Hydro", name, "Hydro")))
+    elif name in capi.DERIVED:
+        key, label = name, name
+    else:
+        _fatal("Derived variable '%s' is not a valid choice (%s)" % (name, ", ".join(sorted(_DERIVED))))
+    if not is_mhd and key not in ("temperature", "wz", "w2"):
+        _fatal("Derived variable '%s' needs the magnetic field: no MHD object has been constructed" % name)
+    if key == "temperature" and not is_ideal:
+        # derived_variables.cpp:98-115 divides w0(IEN) by w0(IDN); the block needs neither <units> nor gamma
+        _fatal("Derived variable 'temperature' (derived_variables.cpp:98, eint/dens) needs the ideal-gas EOS: "
+               "an isothermal fluid stores no internal energy")
+    return capi.DERIVED[key], 1, label
+
+
+def derived_array(phys, which):
+    """the derived variable over the whole pack: (nmb, 1, N3, N2, N1) on the device of the state arrays"""
+    import torch
+    nmb, _, n3, n2, n1 = phys.w0.shape
+    out = torch.empty((nmb, 1, n3, n2, n1), dtype=torch.float64, device=phys.w0.device)
+    L = capi.lib()
+    if not hasattr(L, "akmi_derived_var"):
+        _fatal("derived output variables need akmi_derived_var of libakmi.so (a GPU): this backend has none")
+    b0 = getattr(phys, "b0", None)
+    b = (capi._p(b0.x1f), capi._p(b0.x2f), capi._p(b0.x3f)) if b0 is not None else (None, None, None)
+    capi.check(L.akmi_derived_var(C.byref(phys.pack_c), which, capi._p(phys.w0), capi._p(phys.u0),
+                                  capi._p(getattr(phys, "bcc0", None)), *b, capi._p(out), 1, capi._stream()),
+               "derived_var")
+    return out
+
+
+def _scalars(nfluid, nscalars):
+    """basetype_output.cpp:275-307: r_NN in u0, s_NN in w0, after the fluid variables"""
+    us = [("r_%02d" % (n % 100), nfluid + n, "u0") for n in range(nscalars)]
+    ws = [("s_%02d" % (n % 100), nfluid + n, "w0") for n in range(nscalars)]
+    return us, ws
+
+
+# variable groups of basetype_output.cpp:196-620 for Newtonian hydro/MHD:
+# name -> list of (label, component, array); array "dv:<which>" is computed at output time
+def _outvars(variable, is_mhd, is_ideal=True, turb=False, nscalars=0):
     blk = "mhd" if is_mhd else "hydro"
     u = [("dens", 0, "u0"), ("mom1", 1, "u0"), ("mom2", 2, "u0"), ("mom3", 3, "u0"), ("ener", 4, "u0")]
     w = [("dens", 0, "w0"), ("velx", 1, "w0"), ("vely", 2, "w0"), ("velz", 3, "w0"), ("eint", 4, "w0")]
     if not is_ideal:                       # basetype_output.cpp:252-271: energies only if is_ideal
         u, w = u[:4], w[:4]
+    us, ws = _scalars(len(u), nscalars)
     b = [("bcc1", 0, "bcc0"), ("bcc2", 1, "bcc0"), ("bcc3", 2, "bcc0")]
-    table = {blk + "_u": u, blk + "_w": w}
+    table = {blk + "_u": u + us, blk + "_w": w + ws, blk + "_u_s": us, blk + "_w_s": ws}
     for sfx, (lab, n, arr) in zip(("d", "m1", "m2", "m3", "e"), u):
         table["%s_u_%s" % (blk, sfx)] = [(lab, n, arr)]
     for sfx, (lab, n, arr) in zip(("d", "vx", "vy", "vz", "e"), w):
         table["%s_w_%s" % (blk, sfx)] = [(lab, n, arr)]
     if is_mhd:
-        table.update({"mhd_bcc": b, "mhd_u_bcc": u + b, "mhd_w_bcc": w + b, "mhd_bcc1": b[0:1],
+        # the scalars precede the cell-centred field in the combined groups (basetype_output.cpp:409-477)
+        table.update({"mhd_bcc": b, "mhd_u_bcc": u + us + b, "mhd_w_bcc": w + ws + b, "mhd_bcc1": b[0:1],
                       "mhd_bcc2": b[1:2], "mhd_bcc3": b[2:3]})
     if turb:                               # basetype_output.cpp:614-617: TurbulenceDriver::force
         table["turb_force"] = [("force1", 0, "force"), ("force2", 1, "force"), ("force3", 2, "force")]
-    if variable not in table:
-        _fatal("Output variable '%s' not implemented on this path (choices: %s)"
-               % (variable, ", ".join(sorted(table))))
-    return table[variable]
+    if variable in table:
+        return table[variable]
+    if (variable in _DERIVED and variable.startswith(blk + "_")) or variable in _REFUSED \
+            or variable.endswith("_moments") or variable.startswith(("rad", "prtcl")):
+        which, _, label = derived_which(variable, is_mhd, is_ideal)
+        return [(label, 0, "dv:%d" % which)]
+    _fatal("Output variable '%s' not implemented on this path (choices: %s)"
+           % (variable, ", ".join(sorted(list(table) + [k for k in _DERIVED if k.startswith(blk + "_")]))))
 
 
 class BaseTypeOutput:
@@ -103,7 +172,7 @@ class BaseTypeOutput:
         if op.file_type not in ("hst", "rst"):
             phys = pk.pmhd if pk.pmhd is not None else pk.phydro
             self.outvars = _outvars(op.variable, pk.pmhd is not None, phys.peos.eos_data.is_ideal,
-                                    getattr(pk, "pturb", None) is not None)
+                                    getattr(pk, "pturb", None) is not None, getattr(phys, "nscalars", 0))
 
     def LoadOutputData(self, pm):
         """basetype_output.cpp:729-862: per-block index ranges (ghost zones, slices) and a
@@ -144,13 +213,19 @@ class BaseTypeOutput:
                  o.oie - o.ois + 1)
         out = np.empty(shape, dtype=np.float64)
         host = {}
+        derived = {}              # one launch per output and derived variable, over all MeshBlocks of the pack
         for n, (_, comp, arr) in enumerate(self.outvars):
+            if arr.startswith("dv:") and arr not in derived:
+                derived[arr] = derived_array(phys, int(arr[3:]))
             for mi, o in enumerate(self.outmbs):
                 m = o.mb_gid - pk.gids
                 key = (arr, m, comp)
                 if key not in host:
-                    src = pk.pturb if arr == "force" else phys
-                    host[key] = _to_numpy(getattr(src, arr)[m, comp])
+                    if arr in derived:
+                        host[key] = _to_numpy(derived[arr][m, comp])
+                    else:
+                        src = pk.pturb if arr == "force" else phys
+                        host[key] = _to_numpy(getattr(src, arr)[m, comp])
                 out[n, mi] = host[key][o.oks:o.oke + 1, o.ojs:o.oje + 1, o.ois:o.oie + 1]
         self.outarray = out
 

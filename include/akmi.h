@@ -796,6 +796,34 @@ int akmi_srcterms_newdt(const akmi_pack *p, const akmi_srcterms *s, const double
  * 0 when it does not; a deck the host refuses ends the process with "### FATAL ERROR", as akmi_sim_create does. */
 int akmi_srcterms_from_deck(const char *deck_text, const char *fluid, akmi_srcterms *out);
 
+/* ---- derived output variables (BaseTypeOutput::ComputeDerivedVariable, src/outputs/derived_variables.cpp) ---- *
+ * csrc/akmi_derived.hip.  `which` selects the variable; every one of them has one component.  Centred differences of
+ * w0 (vorticity) or bcc0 (current, curvature), face differences of the field (div B). */
+enum { AKMI_DV_TEMPERATURE = 0,  /* eint/dens of w0 (ideal gas only)                        derived_variables.cpp:98   */
+       AKMI_DV_WZ = 1,           /* hydro_wz, mhd_wz       z-vorticity                                          :119  */
+       AKMI_DV_W2 = 2,           /* hydro_w2, mhd_w2       vorticity squared                                    :139  */
+       AKMI_DV_JZ = 3,           /* mhd_jz                 z-current from bcc0                                  :167  */
+       AKMI_DV_J2 = 4,           /* mhd_j2                 current squared                                      :185  */
+       AKMI_DV_CURV = 5,         /* mhd_curv               |(B.grad B).(I - bb)|/B^2                            :212  */
+       AKMI_DV_K_JXB = 6,        /* mhd_k_jxb              |j x B|/B^2                                          :781  */
+       AKMI_DV_CURV_PERP = 7,    /* mhd_curv_perp          |j x B/B^2 - b.grad b|                               :819  */
+       AKMI_DV_BMAG = 8,         /* mhd_bmag               |bcc0|                                               :929  */
+       AKMI_DV_DIVB = 9 };       /* mhd_divb               from the face fields, ghost cells included           :1046 */
+/* number of components of the variable (1 for all of the above), -1 for an unknown `which` */
+int akmi_derived_ncomp(int which);
+/* out = (nmb, ncomp_out, N3, N2, N1) in the pack's layout, ncomp_out = akmi_derived_ncomp(which).  One launch for all
+ * MeshBlocks writes EVERY element of out: the variable over the index range of the reference's loop (the active cells;
+ * the whole array for div B), zero elsewhere -- what the reference's freshly allocated array holds there.  Each value
+ * carries the reference's sequence of roundings.  The arrays a variable does not read may be NULL (w0 for 0-2, bcc0 for
+ * 3-8, the face fields for 9); u0 is not read by the present variables.  On 1-D / 2-D meshes the two curvature
+ * variables take the differences across the missing directions as zero (the reference reads out of bounds there). */
+int akmi_derived_var(const akmi_pack *p, int which, const double *w0, const double *u0, const double *bcc0,
+                     const double *bx1f, const double *bx2f, const double *bx3f, double *out, int ncomp_out,
+                     void *stream);
+/* the same on the arrays of a simulation of the C++ host, on its stream: `out` is a device array of
+ * nmb_thisrank * N3 * N2 * N1 doubles; the call returns when it is written. */
+int akmi_sim_derived(void *sim, int which, double *out);
+
 #ifdef __cplusplus
 }
 #endif
