@@ -56,6 +56,8 @@ SYMBOLS = [
     "akmi_turb_remove_net_mom",
     "akmi_srcterms_apply", "akmi_srcterms_newdt", "akmi_srcterms_from_deck",
     "akmi_derived_ncomp", "akmi_derived_var", "akmi_sim_derived",
+    "akmi_turb_history_workspace_bytes", "akmi_turb_history", "akmi_sim_turb_history", "akmi_pdf", "akmi_pdf_lds_bins",
+    "akmi_sim_pdf",
 ]
 
 # AKMI_DV_* of include/akmi.h: `which` of akmi_derived_var
@@ -88,6 +90,16 @@ class SrcTerms(C.Structure):
                 ("heating_unit", C.c_double)]
 
 
+class PdfAxis(C.Structure):
+    """struct akmi_pdf_axis (include/akmi.h)"""
+    _fields_ = [("array", C.c_void_p), ("nvar", C.c_int), ("comp", C.c_int), ("nbin", C.c_int), ("logscale", C.c_int),
+                ("bin_lo", C.c_double), ("bin_hi", C.c_double), ("step", C.c_double)]
+
+
+TURB_NHIST = 11                 # AKMI_TURB_NHIST of include/akmi.h
+TURB_HIST_LABELS = ["Bx", "By", "Bz", "B^2", "B^4", "dB^2", "BdB^2", "|BxJ|^2", "|B.J|^2", "U^2", "dU"]   # turb.cpp:249-259
+
+
 class AkmiError(RuntimeError):
     pass
 
@@ -117,6 +129,7 @@ def lib():
             getattr(L, f).restype = C.c_double
             getattr(L, f).argtypes = [C.POINTER(RngState)]
         L.akmi_turb_workspace_bytes.restype = C.c_longlong
+        L.akmi_turb_history_workspace_bytes.restype = C.c_longlong
         for f in ("akmi_sim_time", "akmi_sim_dt", "akmi_sim_tlim"):
             getattr(L, f).restype = C.c_double
         _LIB = L

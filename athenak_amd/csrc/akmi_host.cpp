@@ -1807,6 +1807,79 @@ int akmi_sim_derived(void *h, int which, double *out) {
   )
 }
 
+/* the eleven turbulence history sums (TurbulentHistory, turb.cpp:247-396) of the present state over the whole mesh: the
+ * per-MeshBlock partials of akmi_turb_history, placed at their gids in an 11 x nmb_total array that holds +inf elsewhere,
+ * reduced with all-reduce(min) (exact: min(x, +inf) = x) and added in gid order from 0.0 -- the order of
+ * turb_driver.gid_ordered_sums of the Python host, whatever the rank count */
+int akmi_sim_turb_history(void *h, double *sums) {
+  AKMI_C_ENTRY("akmi_sim_turb_history", AKMI_FAIL,
+    Sim *s = static_cast<Sim *>(h);
+    s->Enter();
+    Mesh *pm = s->pmesh;
+    MeshBlockPack *pk = pm->pmb_pack;
+    auto *m = pk->pmhd;
+    if (!m) { akmi::set_error("akmi_sim_turb_history: the turbulence history columns need an MHD run"); return AKMI_FAIL; }
+    const int nmb = pk->nmb_thispack, K = AKMI_TURB_NHIST;
+    DvceArray<Real> partial, work;
+    partial.Realloc(static_cast<size_t>(nmb)*K);
+    work.Realloc(static_cast<size_t>(akmi_turb_history_workspace_bytes(&m->pack_c)/sizeof(Real)) + 1);
+    const int rc = akmi_turb_history(&m->pack_c, m->w0.p, m->bcc0.p, m->b0.x1f.p, m->b0.x2f.p, m->b0.x3f.p, partial.p,
+                                     work.p, m->stream);
+    std::vector<Real> part(static_cast<size_t>(nmb)*K);
+    if (rc == AKMI_COMPLETE) {
+      HIPCHK(hipMemcpyAsync(part.data(), partial.p, sizeof(Real)*part.size(), hipMemcpyDeviceToHost, m->stream));
+      HIPCHK(hipStreamSynchronize(m->stream));
+    }
+    partial.Free();
+    work.Free();
+    // a rank whose launch failed still joins the reduction, with -inf in its places: min() carries the failure to every
+    // rank, so none is left waiting in the collective
+    const Real inf = std::numeric_limits<Real>::infinity();
+    std::vector<Real> full(static_cast<size_t>(K)*pm->nmb_total, inf);
+    for (int b = 0; b < nmb; ++b)
+      for (int q = 0; q < K; ++q)
+        full[static_cast<size_t>(q)*pm->nmb_total + pk->gids + b] = (rc == AKMI_COMPLETE) ? part[static_cast<size_t>(b)*K + q] : -inf;
+    if (pm->nranks > 1) Comm::World().AllReduceMin(full.data(), static_cast<int>(full.size()), m->stream);   // one collective
+    if (rc != AKMI_COMPLETE) return rc;
+    for (Real v : full)
+      if (v == -inf) { akmi::set_error("akmi_sim_turb_history: akmi_turb_history failed on another rank"); return AKMI_FAIL; }
+    for (int q = 0; q < K; ++q) {
+      Real t = 0.0;
+      for (int g = 0; g < pm->nmb_total; ++g) t += full[static_cast<size_t>(q)*pm->nmb_total + g];
+      sums[q] = t;
+    }
+    return AKMI_COMPLETE;
+  )
+}
+
+/* the histogram of akmi_pdf over this rank's MeshBlocks, on the stream of the simulation; an axis without an array names
+ * a stored one by nvar (0 = u0, 1 = w0, 2 = bcc0) */
+int akmi_sim_pdf(void *h, const akmi_pdf_axis *x, const akmi_pdf_axis *y, int mass_weighted, unsigned long long *counts,
+                 double *weights, unsigned long long *nan_count, int force_global) {
+  AKMI_C_ENTRY("akmi_sim_pdf", AKMI_FAIL,
+    Sim *s = static_cast<Sim *>(h);
+    s->Enter();
+    MeshBlockPack *pk = s->pmesh->pmb_pack;
+    FluidBase *f = pk->phydro ? static_cast<FluidBase *>(pk->phydro) : static_cast<FluidBase *>(pk->pmhd);
+    auto *m = pk->pmhd;
+    if (!x) { akmi::set_error("akmi_sim_pdf: null axis"); return AKMI_FAIL; }
+    akmi_pdf_axis ax[2] = {*x, y ? *y : *x};
+    for (int q = 0; q < (y ? 2 : 1); ++q) {
+      if (ax[q].array) continue;
+      const int sel = ax[q].nvar;
+      if (sel == 0) { ax[q].array = f->u0.p; ax[q].nvar = f->pack_c.nvar; }
+      else if (sel == 1) { ax[q].array = f->w0.p; ax[q].nvar = f->pack_c.nvar; }
+      else if (sel == 2 && m) { ax[q].array = m->bcc0.p; ax[q].nvar = 3; }
+      else { akmi::set_error("akmi_sim_pdf: stored array %d (0 = u0, 1 = w0, 2 = bcc0 of an MHD run)", sel); return AKMI_FAIL; }
+    }
+    const int rc = akmi_pdf(&f->pack_c, &ax[0], y ? &ax[1] : nullptr, mass_weighted ? f->u0.p : nullptr, counts, weights,
+                            nan_count, force_global, f->stream);
+    if (rc != AKMI_COMPLETE) return rc;
+    HIPCHK(hipStreamSynchronize(f->stream));
+    return AKMI_COMPLETE;
+  )
+}
+
 const int *akmi_sim_lloc(void *h) { return static_cast<Sim *>(h)->pmesh->lloc_eachmb.data(); }
 int akmi_sim_gids(void *h) { return static_cast<Sim *>(h)->pmesh->pmb_pack->gids; }
 int akmi_sim_nmb_thisrank(void *h) { return static_cast<Sim *>(h)->pmesh->pmb_pack->nmb_thispack; }

@@ -196,7 +196,8 @@ class Comm {
   void *nccl_ = nullptr;                 // ncclComm_t
   hipStream_t comm_stream_ = nullptr;
   hipEvent_t ready_[4] = {nullptr, nullptr, nullptr, nullptr}, done_[4] = {nullptr, nullptr, nullptr, nullptr};
-  Real *d_scratch_ = nullptr;            // device doubles for the dt reduction
+  Real *d_scratch_ = nullptr;            // device doubles for the reductions (scratch_n_ of them)
+  int scratch_n_ = 0;
   akmi_comm_exchange_fn ex_ = nullptr;
   akmi_comm_allreduce_min_fn ar_ = nullptr;
   void *user_ = nullptr;

@@ -114,6 +114,7 @@ void Comm::InitRCCL(int rank_, int nranks_, const char id[128]) {
     HIPCHK(hipEventCreateWithFlags(&done_[q], hipEventDisableTiming));
   }
   HIPCHK(hipMalloc(&d_scratch_, 8*sizeof(Real)));
+  scratch_n_ = 8;
 }
 
 void Comm::InitCallbacks(int rank_, int nranks_, akmi_comm_exchange_fn ex, akmi_comm_allreduce_min_fn ar,
@@ -255,7 +256,13 @@ void Comm::AllReduceMin(Real *v, int n, hipStream_t compute) {
     if (ar_(user_, v, n) != 0) AKMI_FATAL("the allreduce callback reported a failure");
     return;
   }
-  if (n > 8) AKMI_FATAL("Comm::AllReduceMin: at most 8 values");
+  if (n > scratch_n_) {          // the dt reduction takes 3 values; the history columns 11 x nmb_total: grow once
+    HIPCHK(hipStreamSynchronize(compute));
+    HIPCHK(hipFree(d_scratch_));
+    d_scratch_ = nullptr;
+    HIPCHK(hipMalloc(&d_scratch_, sizeof(Real)*n));
+    scratch_n_ = n;
+  }
   HIPCHK(hipMemcpyAsync(d_scratch_, v, sizeof(Real)*n, hipMemcpyHostToDevice, compute));
   NCCLCHK(rccl().AllReduce(d_scratch_, d_scratch_, static_cast<size_t>(n), ncclDouble, ncclMin,
                            static_cast<ncclComm_t>(nccl_), compute));

@@ -70,6 +70,24 @@ class Simulation:
         which, _, _ = derived_which(name, self.pmesh.pmb_pack.pmhd is not None, ph.peos.eos_data.is_ideal)
         return derived_array(ph, which)
 
+    def pdf(self, variable, bin_min, bin_max, nbin, logscale=True, mass_weighted=False, variable_2=None, bin2_min=0.0,
+            bin2_max=1.0, nbin2=0, logscale2=True, force_global=False):
+        """the histogram a pdf output block with these keys writes, of the present state over the whole mesh
+        (outputs.PdfResult: bins, counts, weights); force_global takes the global-atomic path of akmi_pdf"""
+        from .outputs import PdfResult, pdf_axes, pdf_histogram
+        pk = self.pmesh.pmb_pack
+        axes = pdf_axes(pk, variable, bin_min, bin_max, nbin, logscale, variable_2, bin2_min, bin2_max, nbin2, logscale2)
+        return PdfResult(axes, *pdf_histogram(pk, axes, mass_weighted, force_global))
+
+    def turb_history(self):
+        """the eleven sums of the turbulence history columns (capi.TURB_HIST_LABELS) of the present state of an MHD
+        run, over the whole mesh"""
+        from .outputs import turb_history_sums
+        pk = self.pmesh.pmb_pack
+        if pk.pmhd is None:
+            raise RuntimeError("### FATAL ERROR the turbulence history columns need an MHD run")
+        return turb_history_sums(pk.pmhd, pk)
+
     def Execute(self, max_cycles=None):
         return self.pdriver.Execute(self.pmesh, self.pin, max_cycles)
 

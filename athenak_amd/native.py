@@ -124,6 +124,44 @@ class NativeSimulation:
         capi.check(self.L.akmi_sim_derived(self.h, which, capi._p(out)), "sim_derived")
         return out
 
+    _STORED = {"u0": 0, "w0": 1, "bcc0": 2}          # akmi_sim_pdf: a stored array by number
+
+    def pdf(self, variable, bin_min, bin_max, nbin, logscale=True, mass_weighted=False, variable_2=None, bin2_min=0.0,
+            bin2_max=1.0, nbin2=0, logscale2=True, force_global=False):
+        """as Simulation.pdf: akmi_sim_pdf runs the kernel of the pdf outputs on the native arrays"""
+        from .outputs import PdfResult, pdf_axes, pdf_reduce_ranks
+        pk = self.pmesh.pmb_pack
+        axes = pdf_axes(pk, variable, bin_min, bin_max, nbin, logscale, variable_2, bin2_min, bin2_max, nbin2, logscale2)
+        keep, cax = [], []
+        for (label, comp, arr), edges, step, log in axes:
+            if arr.startswith("dv:"):
+                name = variable if len(cax) == 0 else variable_2
+                t = self.derived(name)
+                keep.append(t)
+                ptr, nv, comp = t.data_ptr(), 1, 0
+            else:
+                ptr, nv = None, self._STORED[arr]
+            cax.append(capi.PdfAxis(ptr, nv, comp, len(edges) - 1, 1 if log else 0, float(edges[0]), float(edges[-1]),
+                                    float(step)))
+        shape = ((cax[1].nbin + 2) if len(cax) == 2 else 1, cax[0].nbin + 2)
+        counts = torch.zeros(shape, dtype=torch.int64, device="cuda")
+        weights = torch.zeros(shape, dtype=torch.float64, device="cuda")
+        nan = torch.zeros(1, dtype=torch.int64, device="cuda")
+        torch.cuda.synchronize()
+        capi.check(self.L.akmi_sim_pdf(self.h, C.byref(cax[0]), C.byref(cax[1]) if len(cax) == 2 else None,
+                                       1 if mass_weighted else 0, capi._p(counts), capi._p(weights), capi._p(nan),
+                                       1 if force_global else 0), "sim_pdf")
+        return PdfResult(axes, *pdf_reduce_ranks(self.pmesh, counts, weights, nan))
+
+    def turb_history(self):
+        """as Simulation.turb_history: akmi_sim_turb_history, the sums over the whole mesh in gid order"""
+        if not self._shape[0]:
+            raise RuntimeError("### FATAL ERROR the turbulence history columns need an MHD run")
+        out = (C.c_double*capi.TURB_NHIST)()
+        torch.cuda.synchronize()
+        capi.check(self.L.akmi_sim_turb_history(self.h, out), "sim_turb_history")
+        return [float(v) for v in out]
+
     time = property(lambda s: s.L.akmi_sim_time(s.h))
     dt = property(lambda s: s.L.akmi_sim_dt(s.h))
     tlim = property(lambda s: s.L.akmi_sim_tlim(s.h))

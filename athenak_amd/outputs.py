@@ -6,12 +6,14 @@ Mirrors, for the file types a hydro/MHD run of this path uses:
   Outputs                src/outputs/outputs.cpp:47-304      (<outputN> blocks -> pout_list)
   BaseTypeOutput         src/outputs/basetype_output.cpp     (variable groups, slices, gather)
   FormattedTableOutput   src/outputs/formatted_table.cpp     (tab/<basename>.<id>.NNNNN.tab)
-  HistoryOutput          src/outputs/history.cpp             (<basename>.hydro|mhd.hst)
+  HistoryOutput          src/outputs/history.cpp             (<basename>.hydro|mhd.hst, <basename>.user.hst)
+  PDFOutput              src/outputs/pdf.cpp                 (pdf_<id>[_<variable_2>]/<basename>.bins.pdf, .NNNNN.pdf)
   MeshBinaryOutput       src/outputs/binary.cpp              (bin/<basename>.<id>.NNNNN.bin)
   RestartOutput          src/outputs/restart.cpp             (rst/<basename>.NNNNN.rst) + read_restart()
-The volume sums of the history file are reduced on the device (akmi_history_sums); everything
-else here is host-side formatting of arrays copied from the device.  Other file types of the
-reference (vtk, pdf, cart, sph, log, trk, cbin) are rejected loudly.
+The volume sums of the history file (akmi_history_sums), the turbulence history columns of a driven MHD run with
+<problem>/user_hist = true (akmi_turb_history) and the histograms of the pdf outputs (akmi_pdf) are reduced on the
+device; everything else here is host-side formatting of arrays copied from the device.  Other file types of the
+reference (vtk, cart, sph, log, trk, cbin) are rejected loudly.
 """
 import ctypes as C
 import os
@@ -57,6 +59,15 @@ class OutputParameters:
         self.slice_x1 = self.slice_x2 = self.slice_x3 = 0.0
         self.data_format = " %12.5e"
         self.user_hist_only = False
+        # pdf (outputs.cpp:252-271)
+        self.bin_min = self.bin_max = 0.0
+        self.nbin = 0
+        self.logscale = True
+        self.mass_weighted = False
+        self.variable_2 = ""
+        self.bin2_min, self.bin2_max = 0.0, 1.0
+        self.nbin2 = 0
+        self.logscale2 = True
 
 
 class OutputMeshBlockInfo:
@@ -169,7 +180,7 @@ class BaseTypeOutput:
         self.outmbs = []
         self.outarray = None
         pk = pm.pmb_pack
-        if op.file_type not in ("hst", "rst"):
+        if op.file_type not in ("hst", "rst", "pdf"):
             phys = pk.pmhd if pk.pmhd is not None else pk.phydro
             self.outvars = _outvars(op.variable, pk.pmhd is not None, phys.peos.eos_data.is_ideal,
                                     getattr(pk, "pturb", None) is not None, getattr(phys, "nscalars", 0))
@@ -314,17 +325,31 @@ class HistoryOutput(BaseTypeOutput):
         self.is_mhd = pk.pmhd is not None
         self.labels = ["mass", "1-mom", "2-mom", "3-mom", "tot-E", "1-KE", "2-KE", "3-KE"]
         phys = pk.pmhd if self.is_mhd else pk.phydro
+        if phys is None:
+            # history.cpp:32-52 would build an empty list and write nothing; here a history block needs a fluid to sum
+            _fatal("hst output block '%s': no Hydro or MHD object has been constructed on this Mesh, so neither the "
+                   "history sums nor the turbulence history columns can be formed" % op.block_name)
         if not phys.peos.eos_data.is_ideal:
             self.labels.remove("tot-E")
         if self.is_mhd:
             self.labels += ["1-ME", "2-ME", "3-ME"]
         self.hdata = None
         self.header_written = False
+        # history.cpp:35-47: the user-defined columns after the physics', or alone with user_hist_only
+        self.user_hist = user_hist_of(pin)
+        self.physics_hist = not (self.user_hist and op.user_hist_only)
+        self.udata = None
+        self.user_header_written = False
 
     def LoadOutputData(self, pm):
-        """history.cpp:78-160,272-374: the sums run on the device (akmi_history_sums)"""
+        """history.cpp:78-160,272-374: the sums run on the device (akmi_history_sums); the user columns of a turbulence
+        run are TurbulentHistory (turb.cpp:247-396, akmi_turb_history)"""
         import torch
         pk = pm.pmb_pack
+        if self.user_hist:
+            self.udata = turb_history_sums(pk.pmhd, pk)
+        if not self.physics_hist:
+            return
         phys = pk.pmhd if self.is_mhd else pk.phydro
         out = torch.zeros(len(self.labels), dtype=torch.float64, device=phys.u0.device)
         L = capi.lib()
@@ -339,30 +364,256 @@ class HistoryOutput(BaseTypeOutput):
     def WriteOutputFile(self, pm, pin):
         """history.cpp:381-457"""
         op = self.out_params
-        h = self.hdata
-        if pm.nranks > 1:
-            import torch.distributed as dist
-            if dist.get_backend() != "nccl":
-                h = h.cpu()
-            dist.all_reduce(h, op=dist.ReduceOp.SUM)      # MPI_Reduce(MPI_SUM) to rank 0
-        h = h.cpu().numpy()
-        if pm.my_rank == 0:
-            fname = "%s.%s.hst" % (op.file_basename, "mhd" if self.is_mhd else "hydro")
-            with open(fname, "a") as f:
-                if not self.header_written:
-                    f.write("# Athena++ history data\n")
-                    f.write("#  [%d]=time      " % 1)
-                    f.write("[%d]=dt       " % 2)
-                    for n, lab in enumerate(self.labels):
-                        f.write("[%d]=%.10s    " % (n + 3, lab))
-                    f.write("\n")
-                    self.header_written = True
-                f.write(_cfmt(op.data_format, pm.time))
-                f.write(_cfmt(op.data_format, pm.dt))
-                for v in h:
-                    f.write(_cfmt(op.data_format, float(v)))
-                f.write("\n")
+        if self.physics_hist:
+            h = self.hdata
+            if pm.nranks > 1:
+                import torch.distributed as dist
+                if dist.get_backend() != "nccl":
+                    h = h.cpu()
+                dist.all_reduce(h, op=dist.ReduceOp.SUM)      # MPI_Reduce(MPI_SUM) to rank 0
+            h = h.cpu().numpy()
+            if pm.my_rank == 0:
+                fname = "%s.%s.hst" % (op.file_basename, "mhd" if self.is_mhd else "hydro")
+                self.header_written = self._append(fname, pm, self.labels, h, self.header_written)
+        if self.user_hist and pm.my_rank == 0:
+            # the sums are already those of the whole mesh on every rank (turb_history_sums)
+            self.user_header_written = self._append("%s.user.hst" % op.file_basename, pm, capi.TURB_HIST_LABELS,
+                                                    self.udata, self.user_header_written)
         self._advance(pm, pin, numbered=False)
+
+    def _append(self, fname, pm, labels, values, header_written):
+        """history.cpp:418-445: one line of one history file, after its header the first time"""
+        op = self.out_params
+        with open(fname, "a") as f:
+            if not header_written:
+                f.write("# Athena++ history data\n")
+                f.write("#  [%d]=time      " % 1)
+                f.write("[%d]=dt       " % 2)
+                for n, lab in enumerate(labels):
+                    f.write("[%d]=%.10s    " % (n + 3, lab))
+                f.write("\n")
+            f.write(_cfmt(op.data_format, pm.time))
+            f.write(_cfmt(op.data_format, pm.dt))
+            for v in values:
+                f.write(_cfmt(op.data_format, float(v)))
+            f.write("\n")
+        return True
+
+
+def user_hist_of(pin):
+    """<problem>/user_hist (pgen.cpp:49; default false, read without adding it to the deck) and what this path enrols for it:
+    TurbulentHistory of pgen_name = turb on an MHD run (turb.cpp:42)"""
+    if not (pin.DoesParameterExist("problem", "user_hist") and pin.GetBoolean("problem", "user_hist")):
+        return False
+    name = pin.GetString("problem", "pgen_name") if pin.DoesParameterExist("problem", "pgen_name") else "none"
+    if name != "turb":
+        # pgen.cpp:86-92 exits with "user history function not enrolled"; the other generators' functions are not on this path
+        _fatal("<problem>/user_hist = true, but the user history function of pgen_name = '%s' is not enrolled on this "
+               "path (only the turbulence history columns of pgen_name = turb are)" % name)
+    if not pin.DoesBlockExist("mhd"):
+        # the reference dereferences a null pmhd here (turb.cpp:262)
+        _fatal("<problem>/user_hist = true with pgen_name = turb needs an MHD run: the turbulence history columns "
+               "(turb.cpp:247-396) are sums of the magnetic field")
+    return True
+
+
+def turb_history_sums(phys, pack):
+    """the eleven sums of TurbulentHistory over the whole mesh as Python floats: per-MeshBlock partials of akmi_turb_history,
+    added in gid order (turb_driver.gid_ordered_sums), so that they do not depend on the rank count"""
+    import torch
+    from .turb_driver import gid_ordered_sums
+    L = capi.lib()
+    if not hasattr(L, "akmi_turb_history"):
+        _fatal("the turbulence history columns need akmi_turb_history of libakmi.so (a GPU): this backend has none")
+    if getattr(phys, "bcc0", None) is None:
+        _fatal("the turbulence history columns need an MHD run")
+    nmb = phys.w0.shape[0]
+    partial = torch.zeros((nmb, capi.TURB_NHIST), dtype=torch.float64, device=phys.w0.device)
+    nbytes = int(L.akmi_turb_history_workspace_bytes(C.byref(phys.pack_c)))
+    work = torch.empty(nbytes//8 + 1, dtype=torch.float64, device=phys.w0.device)
+    capi.check(L.akmi_turb_history(C.byref(phys.pack_c), capi._p(phys.w0), capi._p(phys.bcc0), capi._p(phys.b0.x1f),
+                                   capi._p(phys.b0.x2f), capi._p(phys.b0.x3f), capi._p(partial), capi._p(work),
+                                   capi._stream()), "turb_history")
+    return gid_ordered_sums(partial.cpu().numpy(), pack)
+
+
+def pdf_bins(bin_min, bin_max, nbin, logscale):
+    """(edges[nbin+1], step) with the expressions of pdf.cpp:82-102"""
+    import math
+    if logscale:
+        lmin, lmax = math.log10(bin_min), math.log10(bin_max)
+        edges = [math.pow(10.0, lmin + i*(lmax - lmin)/nbin) for i in range(nbin + 1)]
+        step = (math.log10(bin_max) - math.log10(bin_min))/nbin
+    else:
+        bin_step = (bin_max - bin_min)/nbin
+        edges = [bin_min + i*bin_step for i in range(nbin + 1)]
+        step = (bin_max - bin_min)/nbin
+    return np.array(edges, dtype=np.float64), step
+
+
+_PDF_GROUPS = ("mhd_w", "mhd_u", "hydro_w", "hydro_u")
+
+
+def _pdf_group_check(block, variable):
+    """outputs.cpp:190-203"""
+    if variable in _PDF_GROUPS:
+        _fatal("PDF output block '%s' cannot output variable '%s'. The variable must be a single variable not a "
+               "variable group" % (block, variable))
+
+
+def pdf_checks(block, variable, bin_min, bin_max, nbin, logscale, variable_2="", bin2_min=0.0, bin2_max=1.0, nbin2=0,
+               logscale2=True):
+    """what a pdf block may not ask for (outputs.cpp:190-203, pdf.cpp:62-74, and what this path refuses)"""
+    _pdf_group_check(block, variable)
+    if nbin < 1:
+        _fatal("PDF output block '%s': nbin = %d, at least one bin is needed" % (block, nbin))
+    if logscale and bin_min <= 0.0:
+        _fatal("logscale is true but bin_min <= 0.0")
+    if not bin_max > bin_min:
+        _fatal("PDF output block '%s': bin_max = %g is not above bin_min = %g" % (block, bin_max, bin_min))
+    if variable_2:
+        if nbin2 == 1:
+            # basetype_output.cpp:187-190 loads the second variable only if nbin2 > 1, pdf.cpp:47 makes the histogram 2-D
+            # for every nbin2 != 0: with nbin2 = 1 the reference reads an array that was never loaded
+            _fatal("PDF output block '%s': nbin2 = 1 is not on this path (the reference builds a 2-D histogram there "
+                   "without loading the second variable)" % block)
+        if nbin2 < 0:
+            _fatal("PDF output block '%s': nbin2 = %d" % (block, nbin2))
+        if nbin2 > 0:
+            _pdf_group_check(block, variable_2)
+            if logscale2 and bin2_min <= 0.0:
+                _fatal("logscale2 is true but bin2_min <= 0.0")
+            if not bin2_max > bin2_min:
+                _fatal("PDF output block '%s': bin2_max = %g is not above bin2_min = %g" % (block, bin2_max, bin2_min))
+
+
+def _single_var(variable, is_mhd, is_ideal, turb, nscalars):
+    ov = _outvars(variable, is_mhd, is_ideal, turb, nscalars)
+    if len(ov) != 1:
+        _fatal("PDF output cannot output variable '%s'. The variable must be a single variable not a variable group"
+               % variable)
+    return ov[0]
+
+
+def pdf_histogram(pack, axes, mass_weighted, force_global=False):
+    """counts (int64), weights (float64) of shape [(nbin2+2)|1][nbin+2] and the number of NaN cells dropped, over the
+    whole mesh (all-reduce(sum) with ranks).  axes: one or two of ((label, comp, arr), edges, step, logscale) with arr as in
+    _outvars."""
+    import torch
+    phys = pack.pmhd if pack.pmhd is not None else pack.phydro
+    L = capi.lib()
+    if not hasattr(L, "akmi_pdf"):
+        _fatal("pdf outputs need akmi_pdf of libakmi.so (a GPU): this backend has none")
+    keep, cax = [], []
+    for (label, comp, arr), edges, step, logscale in axes:
+        if arr.startswith("dv:"):
+            t, comp = derived_array(phys, int(arr[3:])), 0
+        else:
+            t = getattr(pack.pturb if arr == "force" else phys, arr)
+        keep.append(t)
+        cax.append(capi.PdfAxis(t.data_ptr(), t.shape[1], comp, len(edges) - 1, 1 if logscale else 0,
+                                float(edges[0]), float(edges[-1]), float(step)))
+    shape = ((cax[1].nbin + 2) if len(cax) == 2 else 1, cax[0].nbin + 2)
+    dev = phys.u0.device
+    counts = torch.zeros(shape, dtype=torch.int64, device=dev)        # the entry counts in uint64; the bits are the same
+    weights = torch.zeros(shape, dtype=torch.float64, device=dev)
+    nan = torch.zeros(1, dtype=torch.int64, device=dev)
+    capi.check(L.akmi_pdf(C.byref(phys.pack_c), C.byref(cax[0]), C.byref(cax[1]) if len(cax) == 2 else None,
+                          capi._p(phys.u0) if mass_weighted else None, capi._p(counts), capi._p(weights), capi._p(nan),
+                          1 if force_global else 0, capi._stream()), "pdf")
+    return pdf_reduce_ranks(pack.pmesh, counts, weights, nan)
+
+
+def pdf_reduce_ranks(pm, counts, weights, nan):
+    """pdf.cpp:296-304: sum over ranks (every rank gets it); numpy arrays and the NaN count"""
+    if pm.nranks > 1:
+        import torch.distributed as dist
+        if dist.get_backend() != "nccl":
+            counts, weights, nan = counts.cpu(), weights.cpu(), nan.cpu()
+        for t in (counts, weights, nan):
+            dist.all_reduce(t, op=dist.ReduceOp.SUM)
+    return counts.cpu().numpy(), weights.cpu().numpy(), int(nan.cpu()[0])
+
+
+def pdf_axes(pack, variable, bin_min, bin_max, nbin, logscale=True, variable_2=None, bin2_min=0.0, bin2_max=1.0, nbin2=0,
+             logscale2=True):
+    """the axes of pdf_histogram for one or two output variables by name, after the checks of a pdf block"""
+    pdf_checks("(accessor)", variable, bin_min, bin_max, nbin, logscale, variable_2 or "", bin2_min, bin2_max, nbin2,
+               logscale2)
+    phys = pack.pmhd if pack.pmhd is not None else pack.phydro
+    args = (pack.pmhd is not None, phys.peos.eos_data.is_ideal, getattr(pack, "pturb", None) is not None,
+            getattr(phys, "nscalars", 0))
+    axes = [(_single_var(variable, *args),) + pdf_bins(bin_min, bin_max, nbin, logscale) + (logscale,)]
+    if variable_2 and nbin2 > 0:
+        axes.append((_single_var(variable_2, *args),) + pdf_bins(bin2_min, bin2_max, nbin2, logscale2) + (logscale2,))
+    return axes
+
+
+class PdfResult:
+    """what Simulation.pdf / NativeSimulation.pdf return: bins (edges[nbin+1]), bins2 (or None), counts and weights of
+    shape [(nbin2+2)|1][nbin+2] (row 0 / column 0 below the first edge, the last at or above the last edge), and the
+    number of cells dropped because a value is NaN"""
+
+    def __init__(self, axes, counts, weights, nan_dropped):
+        self.bins = axes[0][1]
+        self.bins2 = axes[1][1] if len(axes) == 2 else None
+        self.counts, self.weights, self.nan_dropped = counts, weights, nan_dropped
+
+
+class PDFOutput(BaseTypeOutput):
+    """pdf.cpp: volume- or mass-weighted 1-D / 2-D histogram of one (two) single output variable(s) over the active cells
+    of the whole mesh; the bin edges once in <basename>.bins.pdf, the weights of every output in <basename>.NNNNN.pdf"""
+
+    def __init__(self, pin, pm, op):
+        pdf_checks(op.block_name, op.variable, op.bin_min, op.bin_max, op.nbin, op.logscale, op.variable_2, op.bin2_min,
+                   op.bin2_max, op.nbin2, op.logscale2)
+        super().__init__(pin, pm, op)
+        pk = pm.pmb_pack
+        phys = pk.pmhd if pk.pmhd is not None else pk.phydro
+        args = (pk.pmhd is not None, phys.peos.eos_data.is_ideal, getattr(pk, "pturb", None) is not None,
+                getattr(phys, "nscalars", 0))
+        self.outvars = [_single_var(op.variable, *args)]
+        self.pdf_dimension = 1 if op.nbin2 == 0 else 2
+        self.bins, self.step_size = pdf_bins(op.bin_min, op.bin_max, op.nbin, op.logscale)
+        self.axes = [(self.outvars[0], self.bins, self.step_size, op.logscale)]
+        self.dir_name = "pdf_" + op.file_id
+        if self.pdf_dimension == 2:
+            self.outvars.append(_single_var(op.variable_2, *args))
+            self.bins2, self.step_size2 = pdf_bins(op.bin2_min, op.bin2_max, op.nbin2, op.logscale2)
+            self.axes.append((self.outvars[1], self.bins2, self.step_size2, op.logscale2))
+            self.dir_name += "_" + op.variable_2
+        if pm.my_rank == 0:
+            os.makedirs(self.dir_name, exist_ok=True)
+        self.bins_written = False
+        self.counts = self.result = None
+        self.nan_dropped = 0
+
+    def LoadOutputData(self, pm):
+        """pdf.cpp:162-305"""
+        self.counts, self.result, self.nan_dropped = pdf_histogram(pm.pmb_pack, self.axes, self.out_params.mass_weighted)
+
+    def WriteOutputFile(self, pm, pin):
+        """pdf.cpp:311-423"""
+        op = self.out_params
+        if pm.my_rank == 0:
+            if not self.bins_written:
+                with open("%s/%s.bins.pdf" % (self.dir_name, op.file_basename), "a") as f:
+                    f.write("# pdf bins \n")
+                    f.write("# [1]= %.20s \n" % self.outvars[0][0])
+                    if self.pdf_dimension == 2:
+                        f.write("# [2]= %.20s \n" % self.outvars[1][0])
+                    f.write("".join(_cfmt(op.data_format, float(b)) for b in self.bins) + "\n")
+                    if self.pdf_dimension == 2:
+                        f.write("".join(_cfmt(op.data_format, float(b)) for b in self.bins2) + "\n")
+                self.bins_written = True
+            with open("%s/%s.%05d.pdf" % (self.dir_name, op.file_basename, op.file_number), "a") as f:
+                f.write("# time= ")
+                f.write(_cfmt(op.data_format, pm.time))
+                f.write("\n")
+                for row in self.result:
+                    f.write("".join(_cfmt(op.data_format, float(v)) for v in row) + "\n")
+                f.write("\n")
+        self._advance(pm, pin)
 
 
 class MeshBinaryOutput(BaseTypeOutput):
@@ -529,6 +780,7 @@ class Outputs:
     def __init__(self, pin, pm):
         self.pout_list = []
         num_hst = num_rst = 0
+        user_hist_of(pin)          # a user history function this path cannot enrol stops the run, hst block or not
         for name in list(pin.blocks):
             if not name.startswith("output"):
                 continue
@@ -566,24 +818,35 @@ class Outputs:
                         _fatal("Slice at x%d=%g in output block '%s' is out of range of Mesh" % (q, x, name))
                     setattr(op, key, x)
                     setattr(op, "slice%d" % q, True)
-            if (op.file_type == "hst" and pin.DoesParameterExist("problem", "pgen_name")
-                    and pin.GetString("problem", "pgen_name") == "turb"):
-                # turb.cpp:247-396 adds its own history columns (TurbulentHistory); not built on this path
-                _fatal("hst output with <problem>/pgen_name = turb: the turbulence history columns are not on "
-                       "this path (output block '%s')" % name)
+            if op.file_type == "pdf":
+                _pdf_group_check(name, op.variable)
             if op.file_type == "rst" and pin.DoesBlockExist("turb_driving"):
                 _fatal("rst output with <turb_driving>: restarting a driven run (force array and RNG state) is "
                        "not on this path yet (output block '%s')" % name)
             if op.file_type == "hst":
                 op.user_hist_only = pin.GetOrAddBoolean(name, "user_hist_only", False)
-                if op.user_hist_only:
-                    _fatal("user history functions are not on this path")
+                if op.user_hist_only and not user_hist_of(pin):                  # outputs.cpp:209-213
+                    _fatal("User-history file requested in output block '%s', but <problem>/user_hist is not true"
+                           % name)
             op.data_format = " " + pin.GetOrAddString(name, "data_format", "%12.5e")
             if op.file_type == "tab":
                 self.pout_list.insert(0, FormattedTableOutput(pin, pm, op))
             elif op.file_type == "hst":
                 self.pout_list.insert(0, HistoryOutput(pin, pm, op))
                 num_hst += 1
+            elif op.file_type == "pdf":                                          # outputs.cpp:252-273
+                op.bin_min = pin.GetReal(name, "bin_min")
+                op.bin_max = pin.GetReal(name, "bin_max")
+                op.nbin = pin.GetInteger(name, "nbin")
+                op.logscale = pin.GetOrAddBoolean(name, "logscale", True)
+                op.mass_weighted = pin.GetOrAddBoolean(name, "mass_weighted", False)
+                if pin.DoesParameterExist(name, "variable_2"):
+                    op.variable_2 = pin.GetString(name, "variable_2")
+                    op.bin2_min = pin.GetOrAddReal(name, "bin2_min", 0.0)
+                    op.bin2_max = pin.GetOrAddReal(name, "bin2_max", 1.0)
+                    op.nbin2 = pin.GetOrAddInteger(name, "nbin2", 0)
+                    op.logscale2 = pin.GetOrAddBoolean(name, "logscale2", True)
+                self.pout_list.insert(0, PDFOutput(pin, pm, op))
             elif op.file_type == "bin":
                 self.pout_list.insert(0, MeshBinaryOutput(pin, pm, op))
             elif op.file_type == "rst":
@@ -593,7 +856,7 @@ class Outputs:
                 num_rst += 1
             else:
                 _fatal("Unrecognized or unsupported file format = '%s' in output block '%s' "
-                       "(tab, hst, bin, rst on this path)" % (op.file_type, name))
+                       "(tab, hst, bin, pdf, rst on this path)" % (op.file_type, name))
         if num_hst > 1 or num_rst > 1:
             _fatal("More than one history or restart output block found in input file")
 

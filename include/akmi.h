@@ -824,6 +824,55 @@ int akmi_derived_var(const akmi_pack *p, int which, const double *w0, const doub
  * nmb_thisrank * N3 * N2 * N1 doubles; the call returns when it is written. */
 int akmi_sim_derived(void *sim, int which, double *out);
 
+/* ---- run-time statistics: turbulence history columns and pdf outputs -------------------------------------------- *
+ * csrc/akmi_stats.hip; the per-cell arithmetic in csrc/akmi_stats.hpp.
+ *
+ * akmi_turb_history: the eleven sums of TurbulentHistory (src/pgen/fluids/turb.cpp:247-396) over the active cells of an
+ * MHD pack, as per-MeshBlock partials partial[m][11] in the order
+ *   Bx By Bz B^2 B^4 dB^2 BdB^2 |BxJ|^2 |B.J|^2 U^2 dU
+ * (the first three are sums of the bare components, NOT weighted by the cell volume: turb.cpp:294-296).  The sums are
+ * deterministic: fixed-shape trees over tiles of 1024 cells and over the tiles of a MeshBlock, no atomics; the caller adds
+ * the partials over all MeshBlocks in gid order.  Reads one ghost layer of bcc0 and w0 (filled by ConToPrim, the last task
+ * of a stage).  On 1-D / 2-D meshes the cell-centred neighbour in a direction the mesh does not have is the cell itself.
+ * work: akmi_turb_history_workspace_bytes() of device memory. */
+#define AKMI_TURB_NHIST 11
+long long akmi_turb_history_workspace_bytes(const akmi_pack *p);
+int akmi_turb_history(const akmi_pack *p, const double *w0, const double *bcc0, const double *bx1f, const double *bx2f,
+                      const double *bx3f, double *partial, double *work, void *stream);
+/* the same on the arrays of a simulation of the C++ host (MHD only), on its stream: sums[11] (host) are the sums over ALL
+ * MeshBlocks of the mesh in gid order; with ranks, the partials travel as an 11 x nmb_total array reduced with
+ * all-reduce(min) against +inf, so every rank adds the same numbers in the same order. */
+int akmi_sim_turb_history(void *sim, double *sums);
+
+/* akmi_pdf: volume- or mass-weighted 1-D / 2-D histogram of the active cells (PDFOutput::LoadOutputData,
+ * src/outputs/pdf.cpp:244-287).  One axis: the variable as (device array of nvar variables per MeshBlock in the pack's
+ * layout, component), nbin bins, the first and the last edge bins(0), bins(nbin) as the host formed them (pdf.cpp:82-93) and
+ * the step (pdf.cpp:100-102).  A value below bin_lo goes to bin 0, one >= bin_hi to bin nbin+1, any other to
+ * int((x - bin_lo)/step) + 1, or int(log10(x/bin_lo)/step) + 1 with logscale. */
+typedef struct akmi_pdf_axis {
+  const double *array;
+  int nvar, comp;
+  int nbin, logscale;
+  double bin_lo, bin_hi, step;
+} akmi_pdf_axis;
+/* y may be NULL (1-D).  counts and weights: device arrays [(y->nbin+2) | 1][x->nbin+2], cleared by the call; the weight of
+ * a cell is dx1*dx2*dx3 of its MeshBlock, times u0_mass(m, IDN, k, j, i) when u0_mass (the conserved array of the pack,
+ * nvar variables) is not NULL.  A cell with a NaN value belongs to no bin: it is dropped and counted in *nan_count (device).
+ * While the histogram has at most AKMI_PDF_LDS_BINS entries every workgroup accumulates a private copy in LDS and adds its
+ * non-zero bins to the result at the end; larger histograms, or force_global != 0 (or AKMI_PDF_FORCE_GLOBAL=1 in the
+ * environment, for A/B runs), add every cell to the result in global memory.  Counts are exact; the fp64 weights are sums
+ * in arrival order and can differ in their last bits from run to run. */
+#define AKMI_PDF_LDS_BINS 4096
+int akmi_pdf(const akmi_pack *p, const akmi_pdf_axis *x, const akmi_pdf_axis *y, const double *u0_mass,
+             unsigned long long *counts, double *weights, unsigned long long *nan_count, int force_global,
+             void *stream);
+int akmi_pdf_lds_bins(void);      /* AKMI_PDF_LDS_BINS of the library */
+/* the same on the arrays of a simulation of the C++ host, on its stream, for THIS rank's MeshBlocks.  An axis with
+ * array == NULL names a stored array by nvar: 0 = u0, 1 = w0, 2 = bcc0 (comp the variable); mass_weighted != 0 weights
+ * with u0(IDN).  The call returns when the three outputs are written. */
+int akmi_sim_pdf(void *sim, const akmi_pdf_axis *x, const akmi_pdf_axis *y, int mass_weighted,
+                 unsigned long long *counts, double *weights, unsigned long long *nan_count, int force_global);
+
 #ifdef __cplusplus
 }
 #endif
