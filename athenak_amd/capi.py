@@ -58,6 +58,7 @@ SYMBOLS = [
     "akmi_derived_ncomp", "akmi_derived_var", "akmi_sim_derived",
     "akmi_turb_history_workspace_bytes", "akmi_turb_history", "akmi_sim_turb_history", "akmi_pdf", "akmi_pdf_lds_bins",
     "akmi_sim_pdf",
+    "akmi_coarsen", "akmi_coarsen_default_staged", "akmi_sim_coarsen",
 ]
 
 # AKMI_DV_* of include/akmi.h: `which` of akmi_derived_var
@@ -94,6 +95,11 @@ class PdfAxis(C.Structure):
     """struct akmi_pdf_axis (include/akmi.h)"""
     _fields_ = [("array", C.c_void_p), ("nvar", C.c_int), ("comp", C.c_int), ("nbin", C.c_int), ("logscale", C.c_int),
                 ("bin_lo", C.c_double), ("bin_hi", C.c_double), ("step", C.c_double)]
+
+
+class CoarsenVar(C.Structure):
+    """struct akmi_coarsen_var (include/akmi.h)"""
+    _fields_ = [("array", C.c_void_p), ("nvar", C.c_int), ("comp", C.c_int)]
 
 
 TURB_NHIST = 11                 # AKMI_TURB_NHIST of include/akmi.h

@@ -1880,6 +1880,33 @@ int akmi_sim_pdf(void *h, const akmi_pdf_axis *x, const akmi_pdf_axis *y, int ma
   )
 }
 
+/* akmi_coarsen over this rank's MeshBlocks, on the stream of the simulation (after akmi_sim_execute the named registers
+ * hold the state: RestoreRegisters); a variable without an array names a stored one by nvar (0 = u0, 1 = w0, 2 = bcc0) */
+int akmi_sim_coarsen(void *h, const akmi_coarsen_var *vars, int nvars, int factor, int moments, const int *lo,
+                     const int *nc, double *out, int staged) {
+  AKMI_C_ENTRY("akmi_sim_coarsen", AKMI_FAIL,
+    Sim *s = static_cast<Sim *>(h);
+    s->Enter();
+    MeshBlockPack *pk = s->pmesh->pmb_pack;
+    FluidBase *f = pk->phydro ? static_cast<FluidBase *>(pk->phydro) : static_cast<FluidBase *>(pk->pmhd);
+    auto *m = pk->pmhd;
+    if (!vars || nvars < 1) { akmi::set_error("akmi_sim_coarsen: empty variable table"); return AKMI_FAIL; }
+    std::vector<akmi_coarsen_var> tab(vars, vars + nvars);
+    for (auto &v : tab) {
+      if (v.array) continue;
+      const int sel = v.nvar;
+      if (sel == 0) { v.array = f->u0.p; v.nvar = f->pack_c.nvar; }
+      else if (sel == 1) { v.array = f->w0.p; v.nvar = f->pack_c.nvar; }
+      else if (sel == 2 && m) { v.array = m->bcc0.p; v.nvar = 3; }
+      else { akmi::set_error("akmi_sim_coarsen: stored array %d (0 = u0, 1 = w0, 2 = bcc0 of an MHD run)", sel); return AKMI_FAIL; }
+    }
+    const int rc = akmi_coarsen(&f->pack_c, tab.data(), nvars, factor, moments, lo, nc, out, staged, f->stream);
+    if (rc != AKMI_COMPLETE) return rc;
+    HIPCHK(hipStreamSynchronize(f->stream));
+    return AKMI_COMPLETE;
+  )
+}
+
 const int *akmi_sim_lloc(void *h) { return static_cast<Sim *>(h)->pmesh->lloc_eachmb.data(); }
 int akmi_sim_gids(void *h) { return static_cast<Sim *>(h)->pmesh->pmb_pack->gids; }
 int akmi_sim_nmb_thisrank(void *h) { return static_cast<Sim *>(h)->pmesh->pmb_pack->nmb_thispack; }

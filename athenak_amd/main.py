@@ -88,6 +88,14 @@ class Simulation:
             raise RuntimeError("### FATAL ERROR the turbulence history columns need an MHD run")
         return turb_history_sums(pk.pmhd, pk)
 
+    def coarsen(self, variable, factor, moments=False, ghost_zones=False, staged=None):
+        """(labels, tensor) a cbin output block with these keys holds of the present state, for this rank's MeshBlocks:
+        the tensor is (nvars*nmom, nmb, nc3, nc2, nc1), the mean over factor^3 cells of every variable of the group and,
+        with moments, of its 2nd to 4th power (nmom = 4, adjacent).  staged picks the form of akmi_coarsen (None: the
+        library's default); both give the same bits."""
+        from .outputs import coarsen_variable
+        return coarsen_variable(self.pmesh.pmb_pack, variable, factor, moments, ghost_zones, staged)
+
     def Execute(self, max_cycles=None):
         return self.pdriver.Execute(self.pmesh, self.pin, max_cycles)
 

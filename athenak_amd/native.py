@@ -61,6 +61,7 @@ class NativeSimulation:
         ph.nvars = nv = ph.nfluid + ph.nscalars
         self._shape = (is_mhd, nmb, nv, n3, n2, n1)
         self._phys = ph
+        ph.native_sim = self          # outputs.coarsen_pack goes through akmi_sim_coarsen (close() drops the reference)
         self._refresh()
         if is_mhd:
             self.pmesh.pmb_pack.pmhd = ph
@@ -119,10 +120,20 @@ class NativeSimulation:
         from .outputs import derived_which
         is_mhd, nmb, _, n3, n2, n1 = self._shape
         which, ncomp, _ = derived_which(name, is_mhd, self._phys.peos.eos_data.is_ideal)
+        return self.derived_by_number(which, ncomp)
+
+    def derived_by_number(self, which, ncomp=1):
+        """the derived variable AKMI_DV_<which> as derived() returns it"""
+        _, nmb, _, n3, n2, n1 = self._shape
         out = torch.empty((nmb, ncomp, n3, n2, n1), dtype=torch.float64, device="cuda")
         torch.cuda.synchronize()
         capi.check(self.L.akmi_sim_derived(self.h, which, capi._p(out)), "sim_derived")
         return out
+
+    def coarsen(self, variable, factor, moments=False, ghost_zones=False, staged=None):
+        """as Simulation.coarsen: akmi_sim_coarsen runs the kernel of the cbin outputs on the native arrays"""
+        from .outputs import coarsen_variable
+        return coarsen_variable(self.pmesh.pmb_pack, variable, factor, moments, ghost_zones, staged)
 
     _STORED = {"u0": 0, "w0": 1, "bcc0": 2}          # akmi_sim_pdf: a stored array by number
 
@@ -171,6 +182,7 @@ class NativeSimulation:
         if self.h:
             self.L.akmi_sim_destroy(self.h)
             self.h = None
+            self._phys.native_sim = None
 
     def __del__(self):
         try:

@@ -9,11 +9,12 @@ Mirrors, for the file types a hydro/MHD run of this path uses:
   HistoryOutput          src/outputs/history.cpp             (<basename>.hydro|mhd.hst, <basename>.user.hst)
   PDFOutput              src/outputs/pdf.cpp                 (pdf_<id>[_<variable_2>]/<basename>.bins.pdf, .NNNNN.pdf)
   MeshBinaryOutput       src/outputs/binary.cpp              (bin/<basename>.<id>.NNNNN.bin)
+  CoarsenedBinaryOutput  src/outputs/coarsened_binary.cpp    (cbin_<id>_<f>/<basename>.<id>.NNNNN.cbin)
   RestartOutput          src/outputs/restart.cpp             (rst/<basename>.NNNNN.rst) + read_restart()
 The volume sums of the history file (akmi_history_sums), the turbulence history columns of a driven MHD run with
-<problem>/user_hist = true (akmi_turb_history) and the histograms of the pdf outputs (akmi_pdf) are reduced on the
-device; everything else here is host-side formatting of arrays copied from the device.  Other file types of the
-reference (vtk, cart, sph, log, trk, cbin) are rejected loudly.
+<problem>/user_hist = true (akmi_turb_history), the histograms of the pdf outputs (akmi_pdf) and the cell averages and
+moments of the cbin outputs (akmi_coarsen) are reduced on the device; everything else here is host-side formatting of
+arrays copied from the device.  Other file types of the reference (vtk, cart, sph, log, trk) are rejected loudly.
 """
 import ctypes as C
 import os
@@ -68,6 +69,9 @@ class OutputParameters:
         self.bin2_min, self.bin2_max = 0.0, 1.0
         self.nbin2 = 0
         self.logscale2 = True
+        # cbin (outputs.cpp:247-249)
+        self.coarsen_factor = 1
+        self.compute_moments = False
 
 
 class OutputMeshBlockInfo:
@@ -188,10 +192,16 @@ class BaseTypeOutput:
     def LoadOutputData(self, pm):
         """basetype_output.cpp:729-862: per-block index ranges (ghost zones, slices) and a
         host copy of the selected components"""
+        pk = pm.pmb_pack
+        phys = pk.pmhd if pk.pmhd is not None else pk.phydro
+        self._load_ranges(pm)
+        self._load_outarray(pm, pk, phys)
+
+    def _load_ranges(self, pm):
+        """basetype_output.cpp:729-805: outmbs, the index ranges of the MeshBlocks this output writes"""
         op = self.out_params
         ind = pm.mb_indcs
         pk = pm.pmb_pack
-        phys = pk.pmhd if pk.pmhd is not None else pk.phydro
         self.outmbs = []
         for m in range(pk.nmb_thispack):
             if op.gid >= 0 and (m + pk.gids) != op.gid:
@@ -216,6 +226,9 @@ class BaseTypeOutput:
                 oks = oke = CellCenterIndex(op.slice_x3, ind.nx3, size.x3min, size.x3max) + ind.ks
             self.outmbs.append(OutputMeshBlockInfo(int(pk.pmb.mb_gid[m]), ois, oie, ojs, oje, oks,
                                                    oke, size))
+
+    def _load_outarray(self, pm, pk, phys):
+        """basetype_output.cpp:807-862: a host copy of the selected components"""
         if not self.outmbs or not self.outvars:
             self.outarray = None
             return
@@ -653,6 +666,158 @@ class MeshBinaryOutput(BaseTypeOutput):
         self._advance(pm, pin)
 
 
+# ---- coarsened binary outputs -------------------------------------------------------------------------------------
+_MOMENT_SUFFIX = ("_1st", "_2nd", "_3rd", "_4th")          # coarsened_binary.cpp:354-357
+_NATIVE_STORED = {"u0": 0, "w0": 1, "bcc0": 2}            # akmi_sim_coarsen / akmi_sim_pdf: a stored array by number
+
+
+def coarsen_extents(ind, include_gzs, slices=(False, False, False)):
+    """(n1, n2, n3): the fine cells per MeshBlock and direction of an output with these keys (the ranges of
+    BaseTypeOutput._load_ranges: the active cells, the whole array with ghost_zones, one cell across a slice)"""
+    n3, n2, n1 = ind.ncells if include_gzs else (ind.nx3, ind.nx2, ind.nx1)
+    return tuple(1 if sl else n for sl, n in zip(slices, (n1, n2, n3)))
+
+
+def coarsen_checks(block, factor, extents):
+    """what a cbin block may not ask for, before anything is allocated: the reference exits at the first output
+    (coarsened_binary.cpp:213-218), a missing dimension or a slice (extent 1) included"""
+    if factor < 1:
+        _fatal("cbin output block '%s': coarsen_factor = %d, at least 1 is needed" % (block, factor))
+    for q, n in enumerate(extents):
+        if n % factor != 0:
+            _fatal("Full data dimensions are not divisible by coarsen_factor (output block '%s': %d cells in x%d, "
+                   "coarsen_factor = %d)" % (block, n, q + 1, factor))
+
+
+def coarsen_labels(outvars, moments):
+    if not moments:
+        return [lab for (lab, _, _) in outvars]
+    return [lab + sfx for (lab, _, _) in outvars for sfx in _MOMENT_SUFFIX]
+
+
+def coarsen_pack(pack, outvars, factor, moments, lo, nc, staged=None):
+    """akmi_coarsen over every MeshBlock of the pack: (len(outvars)*nmom, nmb, nc3, nc2, nc1) in fp64 on the device of the
+    state arrays.  outvars as in _outvars; lo = (ois, ojs, oks), nc = (nc1, nc2, nc3).  A derived variable is computed into
+    its scratch array first.  staged: None (the library's default), False or True."""
+    import torch
+    phys = pack.pmhd if pack.pmhd is not None else pack.phydro
+    native = getattr(phys, "native_sim", None)          # the C++ host names its stored arrays itself
+    L = capi.lib()
+    if not hasattr(L, "akmi_coarsen"):
+        _fatal("cbin outputs need akmi_coarsen of libakmi.so (a GPU): this backend has none")
+    keep = {}
+    tab = (capi.CoarsenVar*len(outvars))()
+    for n, (_, comp, arr) in enumerate(outvars):
+        if arr.startswith("dv:"):
+            if arr not in keep:
+                keep[arr] = native.derived_by_number(int(arr[3:])) if native else derived_array(phys, int(arr[3:]))
+            tab[n] = capi.CoarsenVar(keep[arr].data_ptr(), 1, 0)
+        elif native is not None:
+            tab[n] = capi.CoarsenVar(None, _NATIVE_STORED[arr], comp)
+        else:
+            t = getattr(pack.pturb if arr == "force" else phys, arr)
+            tab[n] = capi.CoarsenVar(t.data_ptr(), t.shape[1], comp)
+    nmb = phys.w0.shape[0]
+    out = torch.empty((len(outvars)*(4 if moments else 1), nmb, nc[2], nc[1], nc[0]), dtype=torch.float64,
+                      device=phys.w0.device)
+    clo, cnc = (C.c_int*3)(*lo), (C.c_int*3)(*nc)
+    st = -1 if staged is None else int(bool(staged))
+    if native is not None:
+        torch.cuda.synchronize()
+        capi.check(L.akmi_sim_coarsen(native.h, tab, len(outvars), factor, 1 if moments else 0, clo, cnc, capi._p(out), st),
+                   "sim_coarsen")
+    else:
+        capi.check(L.akmi_coarsen(C.byref(phys.pack_c), tab, len(outvars), factor, 1 if moments else 0, clo, cnc,
+                                  capi._p(out), st, capi._stream()), "coarsen")
+    return out
+
+
+def coarsen_variable(pack, variable, factor, moments=False, ghost_zones=False, staged=None):
+    """(labels, tensor) of Simulation.coarsen / NativeSimulation.coarsen: what a cbin block with these keys holds for this
+    rank's MeshBlocks"""
+    pm = pack.pmesh
+    phys = pack.pmhd if pack.pmhd is not None else pack.phydro
+    ind = pm.mb_indcs
+    ext = coarsen_extents(ind, ghost_zones)
+    coarsen_checks("(accessor)", factor, ext)
+    outvars = _outvars(variable, pack.pmhd is not None, phys.peos.eos_data.is_ideal,
+                       getattr(pack, "pturb", None) is not None, getattr(phys, "nscalars", 0))
+    lo = (0, 0, 0) if ghost_zones else (ind.is_, ind.js, ind.ks)
+    return coarsen_labels(outvars, moments), coarsen_pack(pack, outvars, factor, moments, lo,
+                                                          tuple(n//factor for n in ext), staged)
+
+
+class CoarsenedBinaryOutput(BaseTypeOutput):
+    """coarsened_binary.cpp: every output variable averaged over f x f x f cells per MeshBlock, with compute_moments also
+    <q^2>, <q^3>, <q^4>; the averages are formed on the device (akmi_coarsen, one launch for all variables and
+    MeshBlocks) and only the coarse array is copied to the host"""
+
+    def __init__(self, pin, pm, op):
+        coarsen_checks(op.block_name, op.coarsen_factor,
+                       coarsen_extents(pm.mb_indcs, op.include_gzs, (op.slice1, op.slice2, op.slice3)))
+        if pin.GetOrAddBoolean(op.block_name, "single_file_per_rank", False):
+            _fatal("cbin output: single_file_per_rank is not implemented on this path")
+        super().__init__(pin, pm, op)
+        self.dir_name = "cbin_%s_%d" % (op.file_id, op.coarsen_factor)
+        os.makedirs(self.dir_name, exist_ok=True)
+
+    def LoadOutputData(self, pm):
+        """coarsened_binary.cpp:60-291: the ranges of the base class, then the coarse array of the selected MeshBlocks"""
+        op = self.out_params
+        pk = pm.pmb_pack
+        f = op.coarsen_factor
+        self._load_ranges(pm)
+        self.outarray = None
+        if not self.outmbs:
+            return
+        o = self.outmbs[0]
+        nc = ((o.oie - o.ois + 1)//f, (o.oje - o.ojs + 1)//f, (o.oke - o.oks + 1)//f)
+        nout = len(self.outvars)*(4 if op.compute_moments else 1)
+        out = np.empty((nout, len(self.outmbs), nc[2], nc[1], nc[0]), dtype=np.float64)
+        # one launch over the pack per distinct first cell: one, unless a slice (f = 1) cuts MeshBlocks of different levels
+        by_lo = {}
+        for mi, o in enumerate(self.outmbs):
+            by_lo.setdefault((o.ois, o.ojs, o.oks), []).append((mi, o.mb_gid - pk.gids))
+        for lo, mbs in by_lo.items():
+            coarse = coarsen_pack(pk, self.outvars, f, op.compute_moments, lo, nc)
+            sel = coarse[:, [m for _, m in mbs]] if len(mbs) != coarse.shape[1] else coarse
+            out[:, [mi for mi, _ in mbs]] = _to_numpy(sel)
+        self.outarray = out
+
+    def WriteOutputFile(self, pm, pin):
+        """coarsened_binary.cpp:298-530: the pre-header of a bin file plus the number of moments and the factor, the
+        parameter dump, then per MeshBlock 10 int32, 6 Real and the coarse variables as float32 [n][k][j][i].  The six
+        indices are ois, ois+nc1-1, ... (:416-421): the reference's reader takes the coarse extents from them."""
+        op = self.out_params
+        f = op.coarsen_factor
+        fname = "%s/%s.%s.%05d.cbin" % (self.dir_name, op.file_basename, op.file_id, op.file_number)
+        labels = coarsen_labels(self.outvars, op.compute_moments)
+        msg = ("Athena binary output version=1.1\n  size of preheader=7\n  time=%.16e\n  cycle=%d\n"
+               "  number of moments=%d\n  coarsening factor=%d\n  size of location=8\n  size of variable=4\n"
+               "  number of variables=%d\n  variables:  "
+               % (pm.time, pm.ncycle, 4 if op.compute_moments else 1, f, len(labels)))
+        msg += "".join("%s  " % lab for lab in labels) + "\n"
+        dump = pin.ParameterDump()
+        hdr = (msg + "  header offset=%d\n" % len(dump) + dump).encode("ascii")
+        if pm.my_rank == 0:
+            with open(fname, "wb") as fp:
+                fp.write(hdr)
+        _barrier(pm)
+        for r in range(pm.nranks):
+            if r == pm.my_rank and self.outmbs:
+                nc3, nc2, nc1 = self.outarray.shape[2:]
+                with open(fname, "ab") as fp:
+                    for mi, o in enumerate(self.outmbs):
+                        l1, l2, l3 = pm.lloc_eachmb[o.mb_gid][:3]
+                        fp.write(struct.pack("<10i", o.ois, o.ois + nc1 - 1, o.ojs, o.ojs + nc2 - 1, o.oks, o.oks + nc3 - 1,
+                                             l1, l2, l3, pm.level_of(o.mb_gid) - pm.root_level))
+                        fp.write(struct.pack("<6d", o.x1min, o.x1max, o.x2min, o.x2max, o.x3min, o.x3max))
+                        with np.errstate(over="ignore"):          # a moment beyond float32 is written as inf
+                            fp.write(np.ascontiguousarray(self.outarray[:, mi]).astype("<f4").tobytes())
+            _barrier(pm)
+        self._advance(pm, pin)
+
+
 class RestartOutput(BaseTypeOutput):
     """restart.cpp:37-560: one file rst/<basename>.<NNNNN>.rst holding the parameter dump, the mesh
     header, the logical locations and costs of all MeshBlocks and, per MeshBlock (in gid order,
@@ -849,6 +1014,10 @@ class Outputs:
                 self.pout_list.insert(0, PDFOutput(pin, pm, op))
             elif op.file_type == "bin":
                 self.pout_list.insert(0, MeshBinaryOutput(pin, pm, op))
+            elif op.file_type == "cbin":                                         # outputs.cpp:247-249
+                op.coarsen_factor = pin.GetInteger(name, "coarsen_factor")
+                op.compute_moments = pin.GetOrAddBoolean(name, "compute_moments", False)
+                self.pout_list.insert(0, CoarsenedBinaryOutput(pin, pm, op))
             elif op.file_type == "rst":
                 # tail end of the list, so that the file counters of the other output types are
                 # up to date in the restart file (outputs.cpp:285-292)
@@ -856,7 +1025,7 @@ class Outputs:
                 num_rst += 1
             else:
                 _fatal("Unrecognized or unsupported file format = '%s' in output block '%s' "
-                       "(tab, hst, bin, pdf, rst on this path)" % (op.file_type, name))
+                       "(tab, hst, bin, cbin, pdf, rst on this path)" % (op.file_type, name))
         if num_hst > 1 or num_rst > 1:
             _fatal("More than one history or restart output block found in input file")
 

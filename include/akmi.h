@@ -873,6 +873,35 @@ int akmi_pdf_lds_bins(void);      /* AKMI_PDF_LDS_BINS of the library */
 int akmi_sim_pdf(void *sim, const akmi_pdf_axis *x, const akmi_pdf_axis *y, int mass_weighted,
                  unsigned long long *counts, double *weights, unsigned long long *nan_count, int force_global);
 
+/* ---- coarsened binary outputs (file_type = cbin) ------------------------------------------------------------------ *
+ * csrc/akmi_coarsen.hip; the per-cell arithmetic in csrc/akmi_coarsen.hpp.
+ *
+ * akmi_coarsen: the mean over factor^3 fine cells of every variable of the table, for every MeshBlock of the pack, in one
+ * launch (CoarsenedBinaryOutput::LoadOutputData, src/outputs/coarsened_binary.cpp:174-290); with moments != 0 also the
+ * means of x*x, (x*x)*x and ((x*x)*x)*x.  A variable is (device array of nvar variables per MeshBlock in the pack's
+ * layout (nmb, nvar, N3, N2, N1), component); a derived scratch array is nvar = 1. */
+typedef struct akmi_coarsen_var {
+  const double *array;
+  int nvar, comp;
+} akmi_coarsen_var;
+/* lo = {ois, ojs, oks}: the first fine cell of the output range in the array; nc = {nc1, nc2, nc3}: the coarse extents
+ * (lo[d] >= 0 and lo[d] + nc[d]*factor <= N[d] are checked).  out = (nvars*nmom, nmb, nc3, nc2, nc1) in fp64, nmom = 1 or
+ * 4: the moments of a variable are adjacent, then the MeshBlock (the reference's outarray).  Every element is written.
+ * The value of coarse cell (kc, jc, ic) is bit-defined: accumulators start at +0.0 and take the fine cells
+ * (lo3 + kc*f + kk, lo2 + jc*f + jj, lo1 + ic*f + ii) in ascending kk, then jj, then ii, and are divided by (double)(f*f*f).
+ * staged = 0: one thread per coarse cell reads global memory at stride f; 1: the workgroup stages fine row segments in LDS
+ * with contiguous loads; < 0: AKMI_COARSEN_STAGED of the environment (0|1, for A/B runs), else the library's default.
+ * Both forms give the same bits. */
+#define AKMI_COARSEN_DEFAULT_STAGED 1
+int akmi_coarsen(const akmi_pack *p, const akmi_coarsen_var *vars, int nvars, int factor, int moments, const int *lo,
+                 const int *nc, double *out, int staged, void *stream);
+int akmi_coarsen_default_staged(void);      /* AKMI_COARSEN_DEFAULT_STAGED of the library */
+/* the same on the arrays of a simulation of the C++ host, on its stream, for THIS rank's MeshBlocks.  A variable with
+ * array == NULL names a stored array by nvar: 0 = u0, 1 = w0, 2 = bcc0 (comp the variable).  The call returns when out is
+ * written. */
+int akmi_sim_coarsen(void *sim, const akmi_coarsen_var *vars, int nvars, int factor, int moments, const int *lo,
+                     const int *nc, double *out, int staged);
+
 #ifdef __cplusplus
 }
 #endif
