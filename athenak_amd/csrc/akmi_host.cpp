@@ -2,6 +2,7 @@
 #include "akmi_host.hpp"
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <cctype>
@@ -155,18 +156,21 @@ TaskListStatus TaskList::DoAvailable(Driver *d, int s) {
 }
 
 // ---- device arrays ------------------------------------------------------------------------
+static std::atomic<long long> device_bytes{0};      // held by the DvceArrays of the process (akmi_host_device_bytes)
 template <typename T> void DvceArray<T>::Realloc(size_t count) {
   Free();
   // AKMI_FAIL_ALLOC_AFTER=n (tests): the n-th device allocation of the process fails as an exhausted device would
   static const long fail_at = std::getenv("AKMI_FAIL_ALLOC_AFTER") ? std::atol(std::getenv("AKMI_FAIL_ALLOC_AFTER")) : -1;
   static long nalloc = 0;
   if (fail_at >= 0 && ++nalloc > fail_at) AKMI_THROW("device allocation of " + std::to_string(count*sizeof(T)) + " bytes failed (injected)");
-  n = count;
-  HIPCHK(hipMalloc(reinterpret_cast<void **>(&p), std::max<size_t>(count, 1)*sizeof(T)));
-  HIPCHK(hipMemset(p, 0, std::max<size_t>(count, 1)*sizeof(T)));
+  const size_t bytes = std::max<size_t>(count, 1)*sizeof(T);
+  HIPCHK(hipMalloc(reinterpret_cast<void **>(&p), bytes));
+  n = count; device_bytes += static_cast<long long>(bytes);
+  HIPCHK(hipMemset(p, 0, bytes));
+  HIPCHK(hipStreamSynchronize(nullptr));   // the fill runs on the null stream, which the caller's stream need not wait for
 }
 template <typename T> void DvceArray<T>::Free() {
-  if (p) (void)hipFree(p);
+  if (p) { (void)hipFree(p); device_bytes -= static_cast<long long>(std::max<size_t>(n, 1)*sizeof(T)); }
   p = nullptr; n = 0;
 }
 template struct DvceArray<Real>;
@@ -259,10 +263,9 @@ Mesh::Mesh(ParameterInput *pin, int my_rank_, int nranks_, bool host_only_)
   // every MeshBlock costs the same (build_tree.cpp:262-272); one pack per rank (mesh.cpp:205-215)
   LoadBalance(std::vector<float>(nmb_total, 1.0f));
   const int gs = gids_eachrank[my_rank], nb = nmb_eachrank[my_rank];
-  pmb_pack = new MeshBlockPack(this, gs, gs + nb - 1);
-  pmb_pack->pmb = new MeshBlock(pmb_pack, gs, nb);
+  pmb_pack = std::make_unique<MeshBlockPack>(this, gs, gs + nb - 1);      // (a throw below releases it: it is a member by now)
+  pmb_pack->pmb = std::make_unique<MeshBlock>(pmb_pack.get(), gs, nb);
 }
-Mesh::~Mesh() { delete pmb_pack; }
 
 MeshBlock::MeshBlock(MeshBlockPack *ppack, int igids, int nmb_) : nmb(nmb_) {
   Mesh *pm = ppack->pmesh;
@@ -326,7 +329,6 @@ MeshBlock::MeshBlock(MeshBlockPack *ppack, int igids, int nmb_) : nmb(nmb_) {
   HIPCHK(hipMemcpy(d_nghbr.p, plan.tab.data(), sizeof(int)*27*nmb, hipMemcpyHostToDevice));
   if (pm->multilevel) SetNeighborsSMR(pm);
 }
-MeshBlock::~MeshBlock() { d_dx.Free(); d_bcs.Free(); d_nghbr.Free(); }
 
 MeshBlockPack::MeshBlockPack(Mesh *pm, int igids, int igide)
     : pmesh(pm), gids(igids), gide(igide), nmb_thispack(igide - igids + 1) {
@@ -334,12 +336,12 @@ MeshBlockPack::MeshBlockPack(Mesh *pm, int igids, int igide)
                         "after_stagen"})
     tl_map[n] = std::make_shared<TaskList>();          // meshblock_pack.cpp:40-50
 }
-MeshBlockPack::~MeshBlockPack() { delete phydro; delete pmhd; delete pmb; }
+MeshBlockPack::~MeshBlockPack() = default;
 
 void MeshBlockPack::AddPhysics(ParameterInput *pin) {   // meshblock_pack.cpp:102-262
   int nphys = 0;
-  if (pin->DoesBlockExist("hydro")) { phydro = new hydro::Hydro(this, pin); ++nphys; }
-  if (pin->DoesBlockExist("mhd")) { pmhd = new mhd::MHD(this, pin); ++nphys; }
+  if (pin->DoesBlockExist("hydro")) { phydro = std::make_unique<hydro::Hydro>(this, pin); ++nphys; }
+  if (pin->DoesBlockExist("mhd")) { pmhd = std::make_unique<mhd::MHD>(this, pin); ++nphys; }
   if (nphys == 0) AKMI_FATAL("At least one physics module must be specified in input file");
   if (phydro) phydro->AssembleHydroTasks(tl_map);
   if (pmhd) pmhd->AssembleMHDTasks(tl_map);
@@ -349,7 +351,7 @@ void Mesh::NewTimeStep(const Real tlim) {               // mesh.cpp:573-643
   dtold = dt;
   if (dt == static_cast<Real>(FLT_MAX)) dtold = 0.;
   dt = 2.0*dt;
-  FluidBase *phys[2] = {pmb_pack->phydro, pmb_pack->pmhd};
+  FluidBase *phys[2] = {pmb_pack->phydro.get(), pmb_pack->pmhd.get()};
   for (FluidBase *f : phys) {
     if (!f) continue;
     dt = std::min(dt, cfl_no*f->dtnew);
@@ -458,7 +460,7 @@ static int ReconFlag(const std::string &r) {
 }
 
 FluidBase::FluidBase(MeshBlockPack *pp, ParameterInput *pin, const std::string &blk) : pmy_pack(pp) {
-  peos = new EquationOfState;
+  peos = std::make_unique<EquationOfState>();
   EOS_Data &e = peos->eos_data;
   const std::string eqn_of_state = pin->GetString(blk, "eos");     // hydro.cpp:52-72
   if (eqn_of_state == "ideal") {
@@ -543,13 +545,13 @@ FluidBase::FluidBase(MeshBlockPack *pp, ParameterInput *pin, const std::string &
     const size_t c1 = cpack_c.nx1 + 2*ind.ng, c2 = ind.nx2 > 1 ? cpack_c.nx2 + 2*ind.ng : 1,
                  c3 = ind.nx3 > 1 ? cpack_c.nx3 + 2*ind.ng : 1;
     coarse_u0.Realloc(static_cast<size_t>(pp->nmb_thispack)*nvars*c3*c2*c1);
-    psmr = new MeshBoundaryValuesSMR(pp, nvars);
+    psmr = std::make_unique<MeshBoundaryValuesSMR>(pp, nvars);
     psmr->BuildLists(&pack_c, stream);
     psmr->BuildCcMap(&pack_c, stream);
     if (blk == "mhd") psmr->BuildFcMaps(&pack_c, stream);
   }
   if (!multilevel && (pp->pmesh->nranks > 1 || SelfExchange()))
-    pbval = new MeshBoundaryValues(pp, &pack_c, nvars, blk == "mhd");
+    pbval = std::make_unique<MeshBoundaryValues>(pp, &pack_c, nvars, blk == "mhd");
   // <mesh_refinement>/prolong_primitives converts with SingleC2P_IdealHyd / _IdealMHD whatever the EOS of the run is
   // (prolong_prims.cpp:35-186); offered for the ideal gas only -- said at construction, not by the first Prolongate
   if (pp->pmesh->multilevel && pp->pmesh->prolong_prims && !e.is_ideal)
@@ -570,14 +572,6 @@ FluidBase::FluidBase(MeshBlockPack *pp, ParameterInput *pin, const std::string &
   // source terms, hydro.cpp:101-103 / mhd.cpp:137-139
   has_src = ParseSrcTerms(pin, blk, e.gamma, &src_c);
   if (has_src && src_c.ism_cooling) src_dt.Realloc(1);
-}
-FluidBase::~FluidBase() {
-  src_dt.Free();
-  u0.Free(); w0.Free(); u1.Free(); w1.Free(); counters.Free(); dt3.Free(); ws.Free(); fofc.Free(); nfofc.Free();
-  dtmin_cond.Free(); coarse_u0.Free(); coarse_w0.Free();
-  delete psmr;
-  delete pbval;
-  delete peos;
 }
 // may the ghost zones of the primitives be filled like those of the conserved variables (akmi_hydro_ghost_uw)?  Only where
 // every boundary's value rule commutes with ConsToPrim: neighbour / periodic copies, outflow, reflect
@@ -679,7 +673,11 @@ static void FaceAlloc(DvceFaceFld &f, size_t nmb, size_t nv, size_t n3, size_t n
   f.x1f.Realloc(nmb*nv*n3*n2*(n1 + fs)); f.x2f.Realloc(nmb*nv*n3*(n2 + fs)*n1);
   f.x3f.Realloc(nmb*nv*(n3 + fs)*n2*n1);
 }
-static void FaceFree(DvceFaceFld &f) { f.x1f.Free(); f.x2f.Free(); f.x3f.Free(); }
+// hydro: ConsToPrim of the active cells inside the stage kernel (akmi_hydro_stage_w); AKMI_FUSE_C2P=0: A/B switch
+static bool FuseC2P() {
+  static const bool on = !(std::getenv("AKMI_FUSE_C2P") && std::atoi(std::getenv("AKMI_FUSE_C2P")) == 0);
+  return on;
+}
 
 namespace hydro {
 Hydro::Hydro(MeshBlockPack *pp, ParameterInput *pin) : FluidBase(pp, pin, "hydro") {
@@ -699,8 +697,13 @@ Hydro::Hydro(MeshBlockPack *pp, ParameterInput *pin) : FluidBase(pp, pin, "hydro
                n3 = ind.nx3 > 1 ? ind.nx3 + 2*ind.ng : 1;
   if (fused) ws.Realloc(static_cast<size_t>(akmi_stage_workspace_bytes(&pack_c, 0)));
   else FaceAlloc(uflx, pp->nmb_thispack, nvars, n3, n2, n1, 0);  // hydro.cpp:290-292
+  if (StageWritesPrims()) w1.Realloc(w0.n);
 }
-Hydro::~Hydro() { FaceFree(uflx); }
+// nothing here changes after construction; RKUpdate adds what the Driver decides (no captured cycle graph)
+bool Hydro::StageWritesPrims() const {
+  return fused && !peers() && FuseC2P() && BcsCommuteWithC2P() && !SrcActive() &&
+         akmi_hydro_stage_w_eligible(&pack_c, recon_method, rsolver_method);
+}
 
 void Hydro::AssembleHydroTasks(std::map<std::string, std::shared_ptr<TaskList>> tl) {
   TaskID none(0);                                                  // hydro_tasks.cpp:48-80
@@ -758,11 +761,6 @@ MHD::MHD(MeshBlockPack *pp, ParameterInput *pin) : FluidBase(pp, pin, "mhd") {
     FaceAlloc(coarse_b0, nmb, 1, c3, c2, c1, 1);
   }
 }
-MHD::~MHD() {
-  bcc0.Free(); FaceFree(b0); FaceFree(b1); FaceFree(uflx); FaceFree(coarse_b0);
-  efld.x1e.Free(); efld.x2e.Free(); efld.x3e.Free();
-  for (DvceArray<Real> *a : {&e3x1, &e2x1, &e1x2, &e3x2, &e2x3, &e1x3}) a->Free();
-}
 
 void MHD::AssembleMHDTasks(std::map<std::string, std::shared_ptr<TaskList>> tl) {
   TaskID none(0);                                                  // mhd_tasks.cpp:38-84
@@ -795,6 +793,11 @@ void MHD::AssembleMHDTasks(std::map<std::string, std::shared_ptr<TaskList>> tl) 
 }  // namespace mhd
 
 // ---- Driver -----------------------------------------------------------------------------------
+static PinnedReals PinnedAlloc(size_t count) {
+  Real *q = nullptr;
+  HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&q), count*sizeof(Real)));
+  return PinnedReals(q);
+}
 Driver::Driver(ParameterInput *pin, Mesh *pmesh) {       // driver.cpp:85-162
   {
     const std::string ev = pin->GetOrAddString("time", "evolution", "dynamic");
@@ -835,7 +838,7 @@ Driver::Driver(ParameterInput *pin, Mesh *pmesh) {       // driver.cpp:85-162
   if (cg != "auto" && cg != "true" && cg != "false") AKMI_FATAL("<time>/cycle_graph = auto, true or false");
   use_graph = cg == "true" || (cg == "auto" && pmesh->one_d);
   if (const char *e = std::getenv("AKMI_CYCLE_GRAPH")) use_graph = std::atoi(e) != 0;
-  FluidBase *phys[2] = {pmesh->pmb_pack->phydro, pmesh->pmb_pack->pmhd};
+  FluidBase *phys[2] = {pmesh->pmb_pack->phydro.get(), pmesh->pmb_pack->pmhd.get()};
   int nphys = 0;
   for (FluidBase *f : phys) {
     if (!f) continue;
@@ -860,21 +863,13 @@ Driver::Driver(ParameterInput *pin, Mesh *pmesh) {       // driver.cpp:85-162
   if (pmesh->nranks > 1 || nphys != 1 || SelfExchange() || use_graph) run_ahead = false;
   if (use_graph || run_ahead) {
     d_dt.Realloc(2);
-    HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&h_dt), 5*sizeof(Real)));
+    h_dt = PinnedAlloc(5);
     for (FluidBase *f : phys) if (f) f->dt_dev = d_dt.p;
   }
   if (run_ahead) {
-    HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&ra_slot), 6*sizeof(Real)));
-    for (hipEvent_t &e : ra_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    ra_slot = PinnedAlloc(6);
+    for (auto &e : ra_ev) { hipEvent_t ev; HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming)); e.reset(ev); }
   }
-}
-Driver::~Driver() {
-  for (hipEvent_t e : prof_ev) (void)hipEventDestroy(e);
-  if (cycle_exec) (void)hipGraphExecDestroy(cycle_exec);
-  if (h_dt) (void)hipHostFree(h_dt);
-  if (ra_slot) (void)hipHostFree(ra_slot);
-  for (hipEvent_t e : ra_ev) if (e) (void)hipEventDestroy(e);
-  d_dt.Free();
 }
 
 // Mesh::NewTimeStep (mesh.cpp:573-643) for one physics module without diffusion, on the device: st = {dt, time}
@@ -898,9 +893,9 @@ void Driver::EnqueueMeshNewDt(FluidBase *f) {
   Mesh *pm = f->pmy_pack->pmesh;
   const int s = static_cast<int>(ra_cycle & 1);
   k_mesh_newdt<<<1, 64, 0, f->stream>>>(f->dt3.p, d_dt.p, tlim, pm->cfl_no, pm->multi_d ? 1 : 0, pm->three_d ? 1 : 0,
-                                        ra_slot + 3*s);
+                                        ra_slot.get() + 3*s);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(ra_ev[s], f->stream));
+  HIPCHK(hipEventRecord(ra_ev[s].get(), f->stream));
 }
 
 // event pair k = (prof_ev[2k], prof_ev[2k+1]); nothing is recorded while a cycle graph is captured or replayed
@@ -909,17 +904,17 @@ void Driver::ProfMark(hipStream_t st) {
   if (prof_used == prof_ev.size()) {
     hipEvent_t e;
     HIPCHK(hipEventCreate(&e));
-    prof_ev.push_back(e);
+    prof_ev.emplace_back(e);
   }
-  HIPCHK(hipEventRecord(prof_ev[prof_used++], st));
+  HIPCHK(hipEventRecord(prof_ev[prof_used++].get(), st));
 }
 int Driver::ProfRead(double *ms_total, long long *calls) {
   double tot = 0.0;
   const size_t np = prof_used/2;
   for (size_t k = 0; k < np; ++k) {
-    HIPCHK(hipEventSynchronize(prof_ev[2*k + 1]));
+    HIPCHK(hipEventSynchronize(prof_ev[2*k + 1].get()));
     float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, prof_ev[2*k], prof_ev[2*k + 1]));
+    HIPCHK(hipEventElapsedTime(&ms, prof_ev[2*k].get(), prof_ev[2*k + 1].get()));
     tot += ms;
   }
   if (ms_total) *ms_total = tot;
@@ -939,12 +934,12 @@ void Driver::ExecuteTaskList(Mesh *pm, const std::string &tl, int stage) {   // 
 void Driver::InitBoundaryValuesAndPrimitives(Mesh *pm) {   // driver.cpp:569-653
   if (pm->pmb_pack->phydro) pm->pmb_pack->phydro->BeginStage();
   if (pm->pmb_pack->pmhd) pm->pmb_pack->pmhd->BeginStage();
-  if (auto *ph = pm->pmb_pack->phydro) {
+  if (auto *ph = pm->pmb_pack->phydro.get()) {
     ph->RestrictU(this, 0);
     ph->SendU(this, 0); ph->RecvU(this, 0); ph->Prolongate(this, 0);
     ph->ApplyPhysicalBCs(this, 0); ph->ConToPrim(this, 0);
   }
-  if (auto *pm_ = pm->pmb_pack->pmhd) {
+  if (auto *pm_ = pm->pmb_pack->pmhd.get()) {
     pm_->RestrictU(this, 0); pm_->RestrictB(this, 0);
     pm_->SendU(this, 0); pm_->RecvU(this, 0); pm_->SendB(this, 0); pm_->RecvB(this, 0);
     pm_->Prolongate(this, 0);
@@ -975,16 +970,16 @@ void Driver::RunStages(Mesh *pm) {                         // driver.cpp:398-423
 int Driver::Execute(Mesh *pm, int max_cycles) {            // driver.cpp:380-459
   int n = 0;
   if (run_ahead) {
-    FluidBase *f = pm->pmb_pack->phydro ? static_cast<FluidBase *>(pm->pmb_pack->phydro)
-                                        : static_cast<FluidBase *>(pm->pmb_pack->pmhd);
+    FluidBase *f = pm->pmb_pack->phydro ? static_cast<FluidBase *>(pm->pmb_pack->phydro.get())
+                                        : static_cast<FluidBase *>(pm->pmb_pack->pmhd.get());
     h_dt[0] = pm->dt; h_dt[1] = pm->time;
     h_dt[2] = h_dt[3] = h_dt[4] = static_cast<Real>(FLT_MAX);
-    HIPCHK(hipMemcpyAsync(d_dt.p, h_dt, 2*sizeof(Real), hipMemcpyHostToDevice, f->stream));
-    HIPCHK(hipMemcpyAsync(f->dt3.p, h_dt + 2, 3*sizeof(Real), hipMemcpyHostToDevice, f->stream));
+    HIPCHK(hipMemcpyAsync(d_dt.p, h_dt.get(), 2*sizeof(Real), hipMemcpyHostToDevice, f->stream));
+    HIPCHK(hipMemcpyAsync(f->dt3.p, h_dt.get() + 2, 3*sizeof(Real), hipMemcpyHostToDevice, f->stream));
     bool pending = false;                // a cycle is enqueued whose results the host has not read yet
     auto collect = [&](long long cyc) {  // results of cycle `cyc` (counted like ra_cycle): dt of the cycle after it
       const int s = static_cast<int>(cyc & 1);
-      HIPCHK(hipEventSynchronize(ra_ev[s]));
+      HIPCHK(hipEventSynchronize(ra_ev[s].get()));
       pm->dtold = pm->dt;
       pm->dt = ra_slot[3*s];
       f->dtnew = ra_slot[3*s + 2];
@@ -992,15 +987,19 @@ int Driver::Execute(Mesh *pm, int max_cycles) {            // driver.cpp:380-459
     };
     while ((pm->time < tlim) && (pm->ncycle < nlim || nlim < 0)) {       // pm->time: start of the cycle to enqueue, exact
       if (max_cycles >= 0 && n >= max_cycles) break;
-      ra_active = true;                  // (Initialize's NewTimeStep takes the synchronous path)
-      // the host's dt is the one of the cycle BEFORE the one being enqueued: every eligible task takes dt from device
-      // memory (stage_phase_dt / stage_fused_dt); a task that formed beta*pm->dt on the host would silently use the old
-      // value, so the field holds a NaN while the cycle is enqueued -- such a use shows in the first comparison
-      const Real dt_host = pm->dt;
-      pm->dt = std::numeric_limits<Real>::quiet_NaN();
-      RunStages(pm);                     // the kernels read dt from d_dt; NewTimeStep enqueues k_mesh_newdt
-      pm->dt = dt_host;
-      ra_active = false;
+      {
+        // the host's dt is the one of the cycle BEFORE the one being enqueued: every eligible task takes dt from device
+        // memory (stage_phase_dt / stage_fused_dt); a task that formed beta*pm->dt on the host would silently use the old
+        // value, so the field holds a NaN while the cycle is enqueued -- such a use shows in the first comparison.
+        // The guard puts both back, on a throw as well: host assignments only, it may run while the stack unwinds
+        struct Restore {
+          Mesh *pm; bool *active; Real dt;
+          ~Restore() { pm->dt = dt; *active = false; }
+        } restore{pm, &ra_active, pm->dt};
+        ra_active = true;                // (Initialize's NewTimeStep takes the synchronous path)
+        pm->dt = std::numeric_limits<Real>::quiet_NaN();
+        RunStages(pm);                   // the kernels read dt from d_dt; NewTimeStep enqueues k_mesh_newdt
+      }
       // dt of the cycle just enqueued is the result of the cycle before it, which has finished by now or will long
       // before the one just enqueued does: the host needs it only here, to advance its clock
       if (pending) collect(ra_cycle - 1);
@@ -1020,22 +1019,24 @@ int Driver::Execute(Mesh *pm, int max_cycles) {            // driver.cpp:380-459
   while ((pm->time < tlim) && (pm->ncycle < nlim || nlim < 0)) {
     if (max_cycles >= 0 && n >= max_cycles) break;
     if (use_graph) {
-      FluidBase *f = pm->pmb_pack->phydro ? static_cast<FluidBase *>(pm->pmb_pack->phydro)
-                                          : static_cast<FluidBase *>(pm->pmb_pack->pmhd);
+      FluidBase *f = pm->pmb_pack->phydro ? static_cast<FluidBase *>(pm->pmb_pack->phydro.get())
+                                          : static_cast<FluidBase *>(pm->pmb_pack->pmhd.get());
       if (!cycle_exec) {
         // record one cycle; the calls enqueue nothing while the stream is being captured
         hipGraph_t graph;
+        hipGraphExec_t exec;
         HIPCHK(hipStreamBeginCapture(f->stream, hipStreamCaptureModeRelaxed));
         capturing = true;
         RunStages(pm);
         capturing = false;
         HIPCHK(hipStreamEndCapture(f->stream, &graph));
-        HIPCHK(hipGraphInstantiate(&cycle_exec, graph, nullptr, nullptr, 0));
+        HIPCHK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+        cycle_exec.reset(exec);
         HIPCHK(hipGraphDestroy(graph));
       }
-      *h_dt = pm->dt;
-      HIPCHK(hipMemcpyAsync(d_dt.p, h_dt, sizeof(Real), hipMemcpyHostToDevice, f->stream));
-      HIPCHK(hipGraphLaunch(cycle_exec, f->stream));
+      h_dt[0] = pm->dt;
+      HIPCHK(hipMemcpyAsync(d_dt.p, h_dt.get(), sizeof(Real), hipMemcpyHostToDevice, f->stream));
+      HIPCHK(hipGraphLaunch(cycle_exec.get(), f->stream));
       f->FinishNewDtPublic();           // dt3 -> host (the one synchronisation of the cycle)
     } else {
       RunStages(pm);
@@ -1068,11 +1069,6 @@ static bool MergeC2P() {      // A/B switch, profiles/r03_whatif_merge_c2p.txt
   return on;
 }
 template <typename T> static void SwapArr(DvceArray<T> &a, DvceArray<T> &b) { std::swap(a.p, b.p); std::swap(a.n, b.n); }
-// hydro: ConsToPrim of the active cells inside the stage kernel (akmi_hydro_stage_w); AKMI_FUSE_C2P=0: A/B switch
-static bool FuseC2P() {
-  static const bool on = !(std::getenv("AKMI_FUSE_C2P") && std::atoi(std::getenv("AKMI_FUSE_C2P")) == 0);
-  return on;
-}
 // Task-granular path, first stage: CopyCons folded into an out-of-place RKUpdate / CT (akmi_rk_update_oop,
 // akmi_mhd_ct_oop), registers swapped afterwards -- no copy traffic.  Not with FOFC (its trial update reads u1/b1
 // before RKUpdate), RK4 (CopyCons updates the second register itself), the update-in-the-sweeps option.
@@ -1163,13 +1159,11 @@ TaskStatus Hydro::RKUpdate(Driver *d, int stage) {         // hydro_update.cpp:2
     // off-rank neighbours: only the sweeps + update here, so that SendU can post the halo messages
     // before the c2p of the active cells is enqueued
     StagePhase(d, stage, AKMI_PHASE_SWEEPS);
-  } else if (fused && !d->use_graph && FuseC2P() && BcsCommuteWithC2P() && !SrcActive() &&
-             akmi_hydro_stage_w_eligible(&pack_c, recon_method, rsolver_method)) {
+  } else if (!d->use_graph && StageWritesPrims()) {
     // the stage kernel converts the cells it finishes (their new state is in its registers) into the second primitive
     // array; ConToPrim then only has the ghost shell left (after the ghost fill): no pass that reads u0 back
     const int do_dt = (stage == d->nexp_stages);
     const int copy = CopyFlag(d, stage, AKMI_PHASE_ALL);
-    if (!w1.p) w1.Realloc(w0.n);
     int wrote = 0;
     d->ProfMark(stream);
     AKCHK(akmi_hydro_stage_w(&pack_c, recon_method, rsolver_method, d->gam0[stage - 1], d->gam1[stage - 1],
@@ -1656,12 +1650,20 @@ TaskStatus MHD::NewTimeStep(Driver *d, int stage) {        // mhd_newdt.cpp:31-1
 // ---- the simulation object behind akmi_sim_* --------------------------------------------------------
 struct Sim {
   ParameterInput pin;
-  Mesh *pmesh = nullptr;
-  Driver *pdriver = nullptr;
-  hipStream_t own_stream = nullptr;     // the caller passed the null stream, which cannot be captured
-  ~Sim() { delete pdriver; delete pmesh; if (own_stream) (void)hipStreamDestroy(own_stream); }
+  // (destroyed in reverse order: the Driver, the Mesh, the stream last)
+  HipHandle<hipStream_t> own_stream;    // the caller passed the null stream, which cannot be captured
+  std::unique_ptr<Mesh> pmesh;
+  std::unique_ptr<Driver> pdriver;
   // work the caller enqueued elsewhere (initial conditions written on the null stream) comes first
   void Enter() { if (own_stream) HIPCHK(hipDeviceSynchronize()); }
+  // akmi_sim_initialize / akmi_sim_execute threw: the registers may be left swapped and cycles half enqueued, so the calls
+  // that work on the state refuse from then on (Refuse); the plain getters and akmi_sim_destroy do not
+  std::string failed;
+  int Fail() { failed = akmi_last_error(); return AKMI_FAIL; }
+  bool Refuse(const char *entry) const {
+    if (!failed.empty()) akmi::set_error("%s: an earlier call on this simulation failed: %s", entry, failed.c_str());
+    return !failed.empty();
+  }
 };
 
 }  // namespace host
@@ -1673,9 +1675,9 @@ using namespace akmi::host;
 extern "C" {
 
 void *akmi_sim_create(const char *deck_text, void *stream) {
-  Sim *s = nullptr;
-  try {
-    s = new Sim;
+  // a throw unwinds through s: what the half-built objects own is released by their destructors
+  AKMI_C_ENTRY("akmi_sim_create", nullptr,
+    auto s = std::make_unique<Sim>();
     s->pin.LoadFromString(deck_text);
     // <turb_driving> (TurbulenceDriver, src/srcterms/turb_driver.cpp) runs on the Python host only: said here, before
     // anything is allocated, rather than ignoring the block and leaving the fluid at rest
@@ -1683,7 +1685,7 @@ void *akmi_sim_create(const char *deck_text, void *stream) {
       AKMI_FATAL("<turb_driving> is not on the C++ host's path: run a driven deck with the Python host "
                  "(python -m athenak_amd)");
     SrcTermsDeckChecks(&s->pin);
-    s->pmesh = new Mesh(&s->pin, Comm::World().rank, Comm::World().nranks);
+    s->pmesh = std::make_unique<Mesh>(&s->pin, Comm::World().rank, Comm::World().nranks);
     s->pmesh->pmb_pack->AddPhysics(&s->pin);
     if (!stream) {
       // a stream of our own (the null stream cannot be captured into a graph), created with the DEFAULT flags: the same
@@ -1691,40 +1693,39 @@ void *akmi_sim_create(const char *deck_text, void *stream) {
       // stage kernel 6 880-6 930 against 7 900-8 170 Mcell-updates/s, the null stream 7 790-7 930 (profiles/r06_stream_kind.txt;
       // AKMI_STREAM_NONBLOCKING=1 brings the old kind back for A/B runs)
       static const bool nb = std::getenv("AKMI_STREAM_NONBLOCKING") && std::atoi(std::getenv("AKMI_STREAM_NONBLOCKING")) != 0;
-      HIPCHK(hipStreamCreateWithFlags(&s->own_stream, nb ? hipStreamNonBlocking : hipStreamDefault));
-      stream = s->own_stream;
+      hipStream_t own;
+      HIPCHK(hipStreamCreateWithFlags(&own, nb ? hipStreamNonBlocking : hipStreamDefault));
+      s->own_stream.reset(own);
+      stream = own;
     }
-    if (auto *ph = s->pmesh->pmb_pack->phydro) ph->stream = (hipStream_t)stream;
-    if (auto *pm = s->pmesh->pmb_pack->pmhd) pm->stream = (hipStream_t)stream;
-    return s;
-  } catch (...) {
-    NoteException("akmi_sim_create");
-    try { delete s; } catch (...) {}      // what the half-built objects own is released by their destructors
-    return nullptr;
-  }
+    if (auto *ph = s->pmesh->pmb_pack->phydro.get()) ph->stream = (hipStream_t)stream;
+    if (auto *pm = s->pmesh->pmb_pack->pmhd.get()) pm->stream = (hipStream_t)stream;
+    return s.release();
+  )
 }
 
 /* the Driver reads <time>/tlim, which the linear-wave problem generator rescales: create it
  * after the initial conditions have been uploaded */
 int akmi_sim_initialize(void *h, double tlim_override) {
-  AKMI_C_ENTRY("akmi_sim_initialize", AKMI_FAIL,
-    Sim *s = static_cast<Sim *>(h);
+  Sim *s = static_cast<Sim *>(h);
+  AKMI_C_ENTRY("akmi_sim_initialize", s->Fail(),
+    if (s->Refuse("akmi_sim_initialize")) return AKMI_FAIL;
     s->Enter();
     if (tlim_override > 0.0) s->pin.SetReal("time", "tlim", tlim_override);
-    delete s->pdriver;
-    s->pdriver = nullptr;
-    s->pdriver = new Driver(&s->pin, s->pmesh);
-    s->pdriver->Initialize(s->pmesh);
+    s->pdriver.reset();
+    s->pdriver = std::make_unique<Driver>(&s->pin, s->pmesh.get());
+    s->pdriver->Initialize(s->pmesh.get());
     return AKMI_COMPLETE;
   )
 }
 
 int akmi_sim_execute(void *h, int max_cycles) {
-  AKMI_C_ENTRY("akmi_sim_execute", AKMI_FAIL,
-    Sim *s = static_cast<Sim *>(h);
+  Sim *s = static_cast<Sim *>(h);
+  AKMI_C_ENTRY("akmi_sim_execute", s->Fail(),
+    if (s->Refuse("akmi_sim_execute")) return AKMI_FAIL;
     if (!s->pdriver) { akmi::set_error("akmi_sim_execute: call akmi_sim_initialize first"); return AKMI_FAIL; }
     s->Enter();
-    return s->pdriver->Execute(s->pmesh, max_cycles);
+    return s->pdriver->Execute(s->pmesh.get(), max_cycles);
   )
 }
 
@@ -1771,14 +1772,15 @@ int akmi_sim_nmb(void *h) { return static_cast<Sim *>(h)->pmesh->nmb_total; }
 void *akmi_sim_array(void *h, const char *name, long long *count) {
   AKMI_C_ENTRY("akmi_sim_array", nullptr,
   Sim *s = static_cast<Sim *>(h);
-  MeshBlockPack *pk = s->pmesh->pmb_pack;
-  FluidBase *f = pk->phydro ? static_cast<FluidBase *>(pk->phydro) : static_cast<FluidBase *>(pk->pmhd);
+  if (s->Refuse("akmi_sim_array")) return nullptr;
+  MeshBlockPack *pk = s->pmesh->pmb_pack.get();
+  FluidBase *f = pk->phydro ? static_cast<FluidBase *>(pk->phydro.get()) : static_cast<FluidBase *>(pk->pmhd.get());
   std::string n(name);
   DvceArray<Real> *a = nullptr;
   if (n == "u0") a = &f->u0; else if (n == "w0") a = &f->w0; else if (n == "u1") a = &f->u1;
   else if (n == "dx") a = &pk->pmb->d_dx;
   else if (pk->pmhd) {
-    auto *m = pk->pmhd;
+    auto *m = pk->pmhd.get();
     if (n == "bcc0") a = &m->bcc0;
     else if (n == "b0x1f") a = &m->b0.x1f; else if (n == "b0x2f") a = &m->b0.x2f; else if (n == "b0x3f") a = &m->b0.x3f;
     else if (n == "b1x1f") a = &m->b1.x1f; else if (n == "b1x2f") a = &m->b1.x2f; else if (n == "b1x3f") a = &m->b1.x3f;
@@ -1794,10 +1796,11 @@ void *akmi_sim_array(void *h, const char *name, long long *count) {
 int akmi_sim_derived(void *h, int which, double *out) {
   AKMI_C_ENTRY("akmi_sim_derived", AKMI_FAIL,
     Sim *s = static_cast<Sim *>(h);
+    if (s->Refuse("akmi_sim_derived")) return AKMI_FAIL;
     s->Enter();
-    MeshBlockPack *pk = s->pmesh->pmb_pack;
-    FluidBase *f = pk->phydro ? static_cast<FluidBase *>(pk->phydro) : static_cast<FluidBase *>(pk->pmhd);
-    auto *m = pk->pmhd;
+    MeshBlockPack *pk = s->pmesh->pmb_pack.get();
+    FluidBase *f = pk->phydro ? static_cast<FluidBase *>(pk->phydro.get()) : static_cast<FluidBase *>(pk->pmhd.get());
+    auto *m = pk->pmhd.get();
     const int rc = akmi_derived_var(&f->pack_c, which, f->w0.p, f->u0.p, m ? m->bcc0.p : nullptr, m ? m->b0.x1f.p : nullptr,
                                     m ? m->b0.x2f.p : nullptr, m ? m->b0.x3f.p : nullptr, out, akmi_derived_ncomp(which),
                                     f->stream);
@@ -1814,10 +1817,11 @@ int akmi_sim_derived(void *h, int which, double *out) {
 int akmi_sim_turb_history(void *h, double *sums) {
   AKMI_C_ENTRY("akmi_sim_turb_history", AKMI_FAIL,
     Sim *s = static_cast<Sim *>(h);
+    if (s->Refuse("akmi_sim_turb_history")) return AKMI_FAIL;
     s->Enter();
-    Mesh *pm = s->pmesh;
-    MeshBlockPack *pk = pm->pmb_pack;
-    auto *m = pk->pmhd;
+    Mesh *pm = s->pmesh.get();
+    MeshBlockPack *pk = pm->pmb_pack.get();
+    auto *m = pk->pmhd.get();
     if (!m) { akmi::set_error("akmi_sim_turb_history: the turbulence history columns need an MHD run"); return AKMI_FAIL; }
     const int nmb = pk->nmb_thispack, K = AKMI_TURB_NHIST;
     DvceArray<Real> partial, work;
@@ -1830,8 +1834,6 @@ int akmi_sim_turb_history(void *h, double *sums) {
       HIPCHK(hipMemcpyAsync(part.data(), partial.p, sizeof(Real)*part.size(), hipMemcpyDeviceToHost, m->stream));
       HIPCHK(hipStreamSynchronize(m->stream));
     }
-    partial.Free();
-    work.Free();
     // a rank whose launch failed still joins the reduction, with -inf in its places: min() carries the failure to every
     // rank, so none is left waiting in the collective
     const Real inf = std::numeric_limits<Real>::infinity();
@@ -1858,10 +1860,11 @@ int akmi_sim_pdf(void *h, const akmi_pdf_axis *x, const akmi_pdf_axis *y, int ma
                  double *weights, unsigned long long *nan_count, int force_global) {
   AKMI_C_ENTRY("akmi_sim_pdf", AKMI_FAIL,
     Sim *s = static_cast<Sim *>(h);
+    if (s->Refuse("akmi_sim_pdf")) return AKMI_FAIL;
     s->Enter();
-    MeshBlockPack *pk = s->pmesh->pmb_pack;
-    FluidBase *f = pk->phydro ? static_cast<FluidBase *>(pk->phydro) : static_cast<FluidBase *>(pk->pmhd);
-    auto *m = pk->pmhd;
+    MeshBlockPack *pk = s->pmesh->pmb_pack.get();
+    FluidBase *f = pk->phydro ? static_cast<FluidBase *>(pk->phydro.get()) : static_cast<FluidBase *>(pk->pmhd.get());
+    auto *m = pk->pmhd.get();
     if (!x) { akmi::set_error("akmi_sim_pdf: null axis"); return AKMI_FAIL; }
     akmi_pdf_axis ax[2] = {*x, y ? *y : *x};
     for (int q = 0; q < (y ? 2 : 1); ++q) {
@@ -1886,10 +1889,11 @@ int akmi_sim_coarsen(void *h, const akmi_coarsen_var *vars, int nvars, int facto
                      const int *nc, double *out, int staged) {
   AKMI_C_ENTRY("akmi_sim_coarsen", AKMI_FAIL,
     Sim *s = static_cast<Sim *>(h);
+    if (s->Refuse("akmi_sim_coarsen")) return AKMI_FAIL;
     s->Enter();
-    MeshBlockPack *pk = s->pmesh->pmb_pack;
-    FluidBase *f = pk->phydro ? static_cast<FluidBase *>(pk->phydro) : static_cast<FluidBase *>(pk->pmhd);
-    auto *m = pk->pmhd;
+    MeshBlockPack *pk = s->pmesh->pmb_pack.get();
+    FluidBase *f = pk->phydro ? static_cast<FluidBase *>(pk->phydro.get()) : static_cast<FluidBase *>(pk->pmhd.get());
+    auto *m = pk->pmhd.get();
     if (!vars || nvars < 1) { akmi::set_error("akmi_sim_coarsen: empty variable table"); return AKMI_FAIL; }
     std::vector<akmi_coarsen_var> tab(vars, vars + nvars);
     for (auto &v : tab) {
@@ -1906,6 +1910,9 @@ int akmi_sim_coarsen(void *h, const akmi_coarsen_var *vars, int nvars, int facto
     return AKMI_COMPLETE;
   )
 }
+
+/* bytes of device memory the DvceArrays of this process hold (0 once every simulation is destroyed) */
+long long akmi_host_device_bytes(void) { return device_bytes.load(); }
 
 const int *akmi_sim_lloc(void *h) { return static_cast<Sim *>(h)->pmesh->lloc_eachmb.data(); }
 int akmi_sim_gids(void *h) { return static_cast<Sim *>(h)->pmesh->pmb_pack->gids; }

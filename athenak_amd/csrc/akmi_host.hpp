@@ -24,6 +24,7 @@
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include "../../include/akmi.h"
 
@@ -67,7 +68,8 @@ class ParameterInput {
 // that returned AKMI_FAIL -- are thrown as HostError; together with whatever else the C++ runtime throws (std::bad_alloc,
 // std::invalid_argument out of std::stoi on a malformed deck value, ...) they stop at the C entry points, which return
 // AKMI_FAIL / NULL with the message in akmi_last_error() (include/akmi.h:24-27; the TaskStatus::fail of
-// src/tasklist/task_list.hpp:30).  No C++ exception crosses `extern "C"`.
+// src/tasklist/task_list.hpp:30).  No C++ exception crosses `extern "C"`.  Every owner below holds what it owns by RAII (DvceArray,
+// std::unique_ptr, HipHandle), so a constructor that throws releases what it and its sub-objects had built.
 struct HostError : std::runtime_error { using std::runtime_error::runtime_error; };
 [[noreturn]] void Throw(const char *file, int line, const std::string &msg);
 #define AKMI_THROW(msg) ::akmi::host::Throw(__FILE__, __LINE__, (msg))
@@ -143,15 +145,32 @@ struct RegionIndcs {    // mesh.hpp:35-41
 };
 
 template <typename T>
-struct DvceArray {      // flat device array (layout contract: include/akmi.h)
+struct DvceArray {      // flat device array, owned: move-only, freed by the destructor (layout contract: include/akmi.h)
   T *p = nullptr;
   size_t n = 0;
-  void Realloc(size_t count);
+  DvceArray() = default;
+  DvceArray(DvceArray &&o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
+  DvceArray &operator=(DvceArray &&o) noexcept {
+    if (this != &o) { Free(); p = o.p; n = o.n; o.p = nullptr; o.n = 0; }
+    return *this;
+  }
+  ~DvceArray() { Free(); }
+  void Realloc(size_t count);   // zero-filled; returns when the fill has completed
   void Free();
   T *data() const { return p; }
 };
 struct DvceFaceFld { DvceArray<Real> x1f, x2f, x3f; };
 struct DvceEdgeFld { DvceArray<Real> x1e, x2e, x3e; };
+
+// the other HIP objects the host creates: std::unique_ptr with the matching destroy call
+struct HipDeleter {
+  void operator()(Real *pinned) const { (void)hipHostFree(pinned); }
+  void operator()(hipEvent_t e) const { (void)hipEventDestroy(e); }
+  void operator()(hipStream_t s) const { (void)hipStreamDestroy(s); }
+  void operator()(hipGraphExec_t g) const { (void)hipGraphExecDestroy(g); }
+};
+template <typename H> using HipHandle = std::unique_ptr<std::remove_pointer_t<H>, HipDeleter>;   // H = hipEvent_t, ...
+using PinnedReals = std::unique_ptr<Real[], HipDeleter>;
 
 class Mesh;
 class MeshBlockPack;
@@ -253,7 +272,6 @@ class MeshBlockTree {   // meshblock_tree.hpp:27-62, meshblock_tree.cpp
 class MeshBlock {       // meshblock.cpp:25-131
  public:
   MeshBlock(MeshBlockPack *ppack, int igids, int nmb);
-  ~MeshBlock();
   void SetNeighborsSMR(Mesh *pm);   // meshblock.cpp:142-425
   int nmb;
   std::vector<int> mb_lev;        // logical level of each block
@@ -275,13 +293,14 @@ namespace mhd { class MHD; }
 class MeshBlockPack {   // meshblock_pack.hpp:44-97
  public:
   MeshBlockPack(Mesh *pm, int igids, int igide);
-  ~MeshBlockPack();
+  ~MeshBlockPack();                 // = default, where Hydro and MHD are complete types
   void AddPhysics(ParameterInput *pin);
   Mesh *pmesh;
   int gids, gide, nmb_thispack;
-  MeshBlock *pmb = nullptr;
-  hydro::Hydro *phydro = nullptr;
-  mhd::MHD *pmhd = nullptr;
+  // (destroyed in reverse order: the physics objects before the MeshBlock whose d_dx their pack_c.dx points at)
+  std::unique_ptr<MeshBlock> pmb;
+  std::unique_ptr<mhd::MHD> pmhd;
+  std::unique_ptr<hydro::Hydro> phydro;
   std::map<std::string, std::shared_ptr<TaskList>> tl_map;
 };
 
@@ -289,7 +308,6 @@ class Mesh {            // mesh.hpp:92-185
  public:
   // host_only: tables only, no device memory (the exchange-plan unit test runs without a GPU)
   explicit Mesh(ParameterInput *pin, int my_rank = 0, int nranks = 1, bool host_only = false);
-  ~Mesh();
   void LoadBalance(const std::vector<float> &clist);   // load_balance.cpp:38-88
   int my_rank, nranks;
   bool host_only;
@@ -310,7 +328,7 @@ class Mesh {            // mesh.hpp:92-185
   std::vector<int> lloc_eachmb;   // [nmb_total][3], Z-ordered
   Real time, dt, dtold, cfl_no;
   int ncycle;
-  MeshBlockPack *pmb_pack = nullptr;
+  std::unique_ptr<MeshBlockPack> pmb_pack;
 };
 
 // level-aware boundary values of one pack (src/bvals/bvals.hpp:134-267 on a multilevel mesh): the
@@ -319,7 +337,6 @@ class Mesh {            // mesh.hpp:92-185
 class MeshBoundaryValues {     // bvals.hpp:134-267, the off-rank part of bvals_cc.cpp / bvals_fc.cpp
  public:
   MeshBoundaryValues(MeshBlockPack *pp, const akmi_pack *pack, int nvar, bool with_fc);
-  ~MeshBoundaryValues();
   MeshBlockPack *pmy_pack;
   const akmi_pack *pack_c;
   int nvar;
@@ -339,7 +356,6 @@ class MeshBoundaryValues {     // bvals.hpp:134-267, the off-rank part of bvals_
 class MeshBoundaryValuesSMR {
  public:
   MeshBoundaryValuesSMR(MeshBlockPack *pp, int nvar);
-  ~MeshBoundaryValuesSMR();
   MeshBlockPack *pmy_pack;
   int nvar, nnghbr;
   akmi_smr smr_c{};
@@ -375,15 +391,17 @@ struct EquationOfState { EOS_Data eos_data; };
 class FluidBase {
  public:
   FluidBase(MeshBlockPack *pp, ParameterInput *pin, const std::string &blk);
-  virtual ~FluidBase();
+  virtual ~FluidBase() = default;
   MeshBlockPack *pmy_pack;
-  EquationOfState *peos;
+  std::unique_ptr<EquationOfState> peos;
   int recon_method, rsolver_method;
   bool fused;
   akmi_pack pack_c;
   DvceArray<Real> u0, w0, u1;
-  DvceArray<Real> w1;                   // second primitive array (allocated on first use): akmi_hydro_stage_w writes the new
-                                        // primitives of the active cells there while neighbours still read w0; then the two trade places
+  DvceArray<Real> w1;                   // second primitive array: akmi_hydro_stage_w writes the new primitives of the active cells
+                                        // there while neighbours still read w0; then the two trade places.  Allocated by Hydro's
+                                        // constructor when the stage may take that path (Hydro::StageWritesPrims); a 3-D deck with
+                                        // <time>/cycle_graph = true is the one case that holds it without using it
   bool w_swapped = false;               // w0 lives in the buffer that was w1 when the arrays were created
   DvceArray<int> counters;
   DvceArray<Real> dt3;
@@ -417,8 +435,8 @@ class FluidBase {
   bool multilevel = false;
   akmi_pack cpack_c;                    // the coarse buffers as a pack of nx/2 cells (coarse BCs)
   DvceArray<Real> coarse_u0, coarse_w0;  // coarse_w0: <mesh_refinement>/prolong_primitives = true only
-  MeshBoundaryValuesSMR *psmr = nullptr;
-  MeshBoundaryValues *pbval = nullptr;  // off-rank neighbours (uniform meshes, nranks > 1)
+  std::unique_ptr<MeshBoundaryValuesSMR> psmr;
+  std::unique_ptr<MeshBoundaryValues> pbval;   // off-rank neighbours (uniform meshes, nranks > 1)
   bool peers() const { return pbval && pbval->HasPeers(); }
   const Real *dt_dev = nullptr;         // set by the Driver when cycles are replayed from a hipGraph
   // the out-of-place first stage trades the two registers; true while u0 / b0 live in the buffers that were
@@ -454,8 +472,8 @@ namespace hydro {
 class Hydro : public FluidBase {    // hydro.hpp:73-154
  public:
   Hydro(MeshBlockPack *pp, ParameterInput *pin);
-  ~Hydro() override;
   DvceFaceFld uflx;
+  bool StageWritesPrims() const;   // what of RKUpdate's choice of akmi_hydro_stage_w is known at construction
   void AssembleHydroTasks(std::map<std::string, std::shared_ptr<TaskList>> tl);
   void StagePhase(Driver *d, int stage, int phases);   // akmi_hydro_stage_phase
   TaskStatus InitRecv(Driver *d, int stage) { return TaskStatus::complete; }
@@ -481,7 +499,6 @@ namespace mhd {
 class MHD : public FluidBase {      // mhd.hpp:93-199
  public:
   MHD(MeshBlockPack *pp, ParameterInput *pin);
-  ~MHD() override;
   DvceArray<Real> bcc0;
   DvceFaceFld b0, b1, uflx, coarse_b0;
   DvceEdgeFld efld;
@@ -528,7 +545,6 @@ class Driver {          // driver.cpp
   int nlim, nexp_stages;
   Real gam0[4], gam1[4], beta[4], delta[4];
   std::int64_t nmb_updated_ = 0;
-  ~Driver();
   // One cycle (all stages) captured into a hipGraph and replayed: on small packs a cycle is a chain of
   // dependent launches of a few microseconds each and the host cannot issue them fast enough.  Nothing
   // in the captured calls changes from cycle to cycle except dt, which the kernels read from d_dt
@@ -538,13 +554,13 @@ class Driver {          // driver.cpp
   // akmi_sim_profile: live timing of the fused-stage launch group -- a HIP event pair on the launch stream
   // around every akmi_*_stage_fused / akmi_*_stage_phase call of the cycles that follow (bench.py's roofline entry)
   bool prof_on = false;
-  std::vector<hipEvent_t> prof_ev;
+  std::vector<HipHandle<hipEvent_t>> prof_ev;
   size_t prof_used = 0;
   void ProfMark(hipStream_t st);
   int ProfRead(double *ms_total, long long *calls);
-  hipGraphExec_t cycle_exec = nullptr;
+  HipHandle<hipGraphExec_t> cycle_exec;
   DvceArray<Real> d_dt;              // [0] dt of the cycle being enqueued, [1] its start time (run-ahead mode)
-  Real *h_dt = nullptr;              // pinned
+  PinnedReals h_dt;
   // Run-ahead cycles.  The reference reads the new time step back at the end of every cycle (hydro_newdt.cpp:121-124,
   // mesh.cpp:573-643) and the device idles while the host wakes up, computes dt and issues the next cycle's first
   // launches -- 30-40 us, 10 % of a cycle of the 128^3 hydro deck.  Here Mesh::NewTimeStep runs ON the device at the end
@@ -555,8 +571,8 @@ class Driver {          // driver.cpp
   // akmi_sim_* call.  Eligible like the cycle graph: fused stage, one rank, uniform mesh, no diffusion time steps.
   // <time>/run_ahead = auto (on when eligible) | true | false; AKMI_RUN_AHEAD=0/1 overrides.
   bool run_ahead = false, ra_active = false;     // ra_active: inside the run-ahead loop of Execute
-  Real *ra_slot = nullptr;           // pinned, device-visible: 2 slots x {dt, time, dtnew}
-  hipEvent_t ra_ev[2] = {nullptr, nullptr};
+  PinnedReals ra_slot;               // device-visible: 2 slots x {dt, time, dtnew}
+  HipHandle<hipEvent_t> ra_ev[2];
   long long ra_cycle = 0;            // cycles enqueued in run-ahead mode (slot = ra_cycle & 1)
   void EnqueueMeshNewDt(FluidBase *f);
  private:

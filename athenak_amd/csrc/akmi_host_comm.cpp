@@ -402,11 +402,6 @@ MeshBoundaryValues::MeshBoundaryValues(MeshBlockPack *pp, const akmi_pack *pack,
     recvbuf[c].Realloc(std::max<long long>(ch[c].nrecvbuf, 1));
   }
 }
-MeshBoundaryValues::~MeshBoundaryValues() {
-  for (int c = 0; c < 2; ++c) {
-    d_send_tab[c].Free(); d_send_off[c].Free(); d_seg_off[c].Free(); sendbuf[c].Free(); recvbuf[c].Free();
-  }
-}
 bool MeshBoundaryValues::HasPeers() const { return !pmy_pack->pmb->plan.peers.empty(); }
 
 void MeshBoundaryValues::Post(int c, hipStream_t st) {

@@ -311,7 +311,7 @@ void Interval(Kind kind, bool send, const Dir &d, int o, int f, int a, int st, b
 
 MeshBoundaryValuesSMR::MeshBoundaryValuesSMR(MeshBlockPack *pp, int nvar_) : pmy_pack(pp), nvar(nvar_) {
   Mesh *pm = pp->pmesh;
-  MeshBlock *pmb = pp->pmb;
+  MeshBlock *pmb = pp->pmb.get();
   const RegionIndcs &in = pm->mb_indcs;
   const int ndim = pm->three_d ? 3 : (pm->multi_d ? 2 : 1);
   const int nmb = pp->nmb_thispack;
@@ -597,13 +597,6 @@ void MeshBoundaryValuesSMR::BuildCcMap(const akmi_pack *pk, hipStream_t st) {
     map_failed("akmi_smr_cc_map", mode); return;
   }
   cc_np = n; cc_tail = tail; cc_map_on = true;
-}
-
-MeshBoundaryValuesSMR::~MeshBoundaryValuesSMR() {
-  d_lists.Free(); d_fc_map[0].Free(); d_fc_map[1].Free(); d_cc_map.Free();
-  d_nghbr.Free(); d_lev.Free(); d_cc.Free(); d_fc.Free(); d_ndat.Free(); d_ox.Free(); d_nflx.Free(); d_same.Free(); d_needs.Free();
-  d_layout.Free(); d_soff.Free(); d_roff.Free();
-  for (auto &b : buf) b.Free();
 }
 
 // the messages of one class: one per peer rank (bvals.cpp:134-310)

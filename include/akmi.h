@@ -696,6 +696,8 @@ int akmi_comm_profile_read(double *out, int n);
  * number of entries needed (call again with a larger buffer if > cap), or -1 on error. */
 long long akmi_host_exchange_plan(const char *deck_text, int rank, int nranks, int nvar, int fc,
                                   long long *out, long long cap);
+/* Bytes of device memory the host's arrays (akmi_sim_*) hold in this process; 0 once every simulation is destroyed. */
+long long akmi_host_device_bytes(void);
 
 /* ---- measurement utility ------------------------------------------------------------ *
  * dst[i] = src[i] for n doubles with the library's own access pattern (8 B per lane,

@@ -93,3 +93,54 @@ assert r["bitwise_equal"], r
 print("alive")
 """ % os.path.join(ROOT, "tests"))
     assert "alive" in out and "too large" in out and "runtime exception" in out
+
+
+# AKMI_FAIL_ALLOC_AFTER counts the allocations (DvceArray::Realloc) of each element type on their own.  ONE akmi_sim_create of
+# the 16^3 Orszag-Tang deck makes 27, read off a build that printed them (gpu run of the knob at 26 and 27: 3 159 072 bytes
+# held either way): 24 of doubles -- dx, u0 w0 u1, dt3, bcc0, b0 and b1 (3 faces each), and on the task path that small 3-D
+# MHD packs take the flux faces (3), the edge fields (3) and the six sweep EMFs -- and 3 of ints (bcs, neighbours, counters)
+NALLOC_REAL_CREATE_16 = 24
+
+
+@pytest.mark.gpu
+def test_failed_create_releases_device_memory():
+    """a create that fails half-way gives back what it had allocated: the second simulation fails at its 5th array of doubles
+    (dt3), with the MeshBlock tables, u0, w0, u1 (12 MB each at 64^3) and the counters in existence"""
+    out = _run(r"""
+h, msg = create(deck(16))
+assert h, msg
+L.akmi_sim_destroy(C.c_void_p(h))
+assert L.akmi_host_device_bytes() == 0, L.akmi_host_device_bytes()
+h, msg = create(deck(64))
+held = L.akmi_host_device_bytes()
+print("held after the failed create:", held)
+assert not h and "akmi_sim_create" in msg and "injected" in msg, (h, msg)
+assert held == 0, held
+print("alive:", msg)
+""", env={"AKMI_FAIL_ALLOC_AFTER": str(NALLOC_REAL_CREATE_16 + 4)})
+    assert "alive" in out
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("deck_name,extra", [("orszag_tang.athinput", ["mhd/fused_stage=true"]),     # run-ahead cycles: d_dt
+                                             ("sod.athinput", [])])                                 # stage kernel writes w1
+def test_destroy_releases_everything(deck_name, extra):
+    """create, initialize, two cycles, destroy: no device array of the host outlives its simulation (the arrays are the
+    zero-filled ones of the create: nothing is compared but the return codes and the counter)"""
+    out = _run(r"""
+ov = ["time/nlim=2"] + %r
+for q in (1, 2, 3):
+    ov += ["mesh/nx%%d=16" %% q, "meshblock/nx%%d=16" %% q]
+h, msg = create(load_deck(%r, ov).Dump().encode())
+assert h, msg
+h = C.c_void_p(h)
+assert L.akmi_host_device_bytes() > 0
+rc = L.akmi_sim_initialize(h, C.c_double(-1.0))
+assert rc == 0, (rc, L.akmi_last_error().decode())
+rc = L.akmi_sim_execute(h, 2)
+assert rc == 2, (rc, L.akmi_last_error().decode())
+L.akmi_sim_destroy(h)
+assert L.akmi_host_device_bytes() == 0, L.akmi_host_device_bytes()
+print("alive")
+""" % (extra, deck_name))
+    assert "alive" in out
