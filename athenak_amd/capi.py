@@ -59,7 +59,10 @@ SYMBOLS = [
     "akmi_turb_history_workspace_bytes", "akmi_turb_history", "akmi_sim_turb_history", "akmi_pdf", "akmi_pdf_lds_bins",
     "akmi_sim_pdf",
     "akmi_coarsen", "akmi_coarsen_default_staged", "akmi_sim_coarsen",
+    "akmi_stage_last_forms", "akmi_mhd_u0_sweeps_eligible", "akmi_sim_stage_forms", "akmi_sim_counters",
 ]
+
+FORM_X3_U0, FORM_X12_U0, FORM_LEAN_C2P = 1, 2, 4      # AKMI_FORM_* of include/akmi.h
 
 # AKMI_DV_* of include/akmi.h: `which` of akmi_derived_var
 DERIVED = {"temperature": 0, "wz": 1, "w2": 2, "jz": 3, "j2": 4, "curv": 5, "k_jxb": 6, "curv_perp": 7, "bmag": 8,

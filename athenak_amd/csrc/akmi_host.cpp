@@ -760,6 +760,16 @@ MHD::MHD(MeshBlockPack *pp, ParameterInput *pin) : FluidBase(pp, pin, "mhd") {
                  c3 = ind.nx3 > 1 ? cpack_c.nx3 + 2*ind.ng : 1;
     FaceAlloc(coarse_b0, nmb, 1, c3, c2, c1, 1);
   }
+  // <mhd>/u0_sweeps (read without adding it to the deck, like small_pack_tasks).  auto: on where the stage kernels have the
+  // form (3-D PLM + HLLD, ideal gas, no scalars) and w0 is ConsToPrim of u0 in every cell when a stage begins, which this
+  // host knows of uniform single-level packs without source, diffusion or FOFC terms
+  {
+    std::string us = pin->DoesParameterExist("mhd", "u0_sweeps") ? pin->GetString("mhd", "u0_sweeps") : "auto";
+    for (char &c : us) c = static_cast<char>(std::tolower(static_cast<unsigned char>(c)));
+    if (us != "auto" && us != "false") AKMI_FATAL("<mhd>/u0_sweeps = " + us + ": auto or false");
+    u0_sweeps = us == "auto" && fused && !kinematic && !multilevel && !use_fofc && !has_src && !has_visc && !has_cond &&
+                !has_resist && akmi_mhd_u0_sweeps_eligible(&pack_c, recon_method, rsolver_method) != 0;
+  }
 }
 
 void MHD::AssembleMHDTasks(std::map<std::string, std::shared_ptr<TaskList>> tl) {
@@ -1116,6 +1126,25 @@ void FluidBase::RestoreRegisters() {
 }
 
 namespace mhd {
+// What the u0 form of the sweeps adds to the copy flag of a stage call (include/akmi.h):
+//  * a stage that is out of place anyway (the first, copy == 2) runs its x3 march from u0;
+//  * the LAST stage of a cycle becomes out of place (copy 3: result into u1's buffer, which holds the state of the start of
+//    the cycle and is read by this stage for the last time; registers traded afterwards) and does the same.
+// Stages in between stay in place -- u1 has to survive them -- and with them the w0 form: a chunk of the march primes
+// its window with the last two cells of the chunk below, which an in-place stage has overwritten in u0 by then.
+// RK4, captured cycle graphs, AKMI_OUT_OF_PLACE=0 and ranks with off-rank neighbours keep the form they had.
+int MHD::U0Copy(const Driver *d, int stage, int phases, int copy) const {
+  if (!u0_sweeps || !(phases & AKMI_PHASE_SWEEPS) || stage < 1 || peers()) return copy;
+  static const bool off = std::getenv("AKMI_OUT_OF_PLACE") && std::atoi(std::getenv("AKMI_OUT_OF_PLACE")) == 0;
+  if (d->integrator == "rk4" || d->use_graph || off) return copy;
+  if (copy == 2) return copy | AKMI_COPY_X3_U0;
+  if (copy == 0 && stage > 1 && stage == d->nexp_stages) return 3 | AKMI_COPY_X3_U0;
+  return copy;
+}
+void MHD::NoteForms(int stage, int phases) {
+  if ((phases & AKMI_PHASE_SWEEPS) && stage >= 1 && stage <= 4) stage_forms[stage - 1] = akmi_stage_last_forms();
+}
+
 void MHD::RestoreRegisters() {
   FluidBase::RestoreRegisters();
   if (!b_swapped) return;
@@ -1380,22 +1409,26 @@ TaskStatus MHD::RKUpdate(Driver *d, int stage) {           // mhd_update.cpp:24-
     StagePhase(d, stage, AKMI_PHASE_SWEEPS | AKMI_PHASE_EMF_CT);
   } else if (fused) {
     int do_dt = (stage == d->nexp_stages);
-    const int copy = CopyFlag(d, stage, AKMI_PHASE_ALL);
+    const int copy_arg = U0Copy(d, stage, AKMI_PHASE_ALL, CopyFlag(d, stage, AKMI_PHASE_ALL));
+    const int copy = copy_arg & AKMI_COPY_MASK;
     d->ProfMark(stream);
     if (dt_dev)
       AKCHK(akmi_mhd_stage_fused_dt(&pack_c, recon_method, rsolver_method, d->gam0[stage - 1],
-                                    d->gam1[stage - 1], d->beta[stage - 1], dt_dev, copy, w0.p, bcc0.p,
+                                    d->gam1[stage - 1], d->beta[stage - 1], dt_dev, copy_arg, w0.p, bcc0.p,
                                     u0.p, u1.p, b0.x1f.p, b0.x2f.p, b0.x3f.p, b1.x1f.p, b1.x2f.p, b1.x3f.p,
                                     do_dt, counters.p, dt3.p, ws.p, stream));
     else
     AKCHK(akmi_mhd_stage_fused(&pack_c, recon_method, rsolver_method, d->gam0[stage - 1],
-                               d->gam1[stage - 1], beta_dt, copy, w0.p, bcc0.p, u0.p, u1.p,
+                               d->gam1[stage - 1], beta_dt, copy_arg, w0.p, bcc0.p, u0.p, u1.p,
                                b0.x1f.p, b0.x2f.p, b0.x3f.p, b1.x1f.p, b1.x2f.p, b1.x3f.p, do_dt,
                                counters.p, dt3.p, ws.p, stream));
     d->ProfMark(stream);
+    NoteForms(stage, AKMI_PHASE_ALL);
     if (copy == 2) {
       SwapArr(u0, u1); u_swapped = !u_swapped;
       SwapArr(b0.x1f, b1.x1f); SwapArr(b0.x2f, b1.x2f); SwapArr(b0.x3f, b1.x3f); b_swapped = !b_swapped;
+    } else if (copy == 3) {
+      SwapArr(u0, u1); u_swapped = !u_swapped;
     }
     interior_done_ = true; dt_ready_ = do_dt;
   } else if (OopFirst(d, stage)) {
@@ -1413,17 +1446,20 @@ void MHD::StagePhase(Driver *d, int stage, int phases) {
   const Real g0 = stage >= 1 ? d->gam0[stage - 1] : 1.0, g1 = stage >= 1 ? d->gam1[stage - 1] : 0.0;
   const Real beta_dt = stage >= 1 ? d->beta[stage - 1]*pmy_pack->pmesh->dt : 0.0;
   const int do_dt = (stage == d->nexp_stages);
-  const int copy = CopyFlag(d, stage, phases);
+  const int copy_arg = U0Copy(d, stage, phases, CopyFlag(d, stage, phases));
+  const int copy = copy_arg & AKMI_COPY_MASK;
   d->ProfMark(stream);
   if (dt_dev && stage >= 1)
-    AKCHK(akmi_mhd_stage_phase_dt(&pack_c, recon_method, rsolver_method, g0, g1, d->beta[stage - 1], dt_dev, copy, w0.p,
+    AKCHK(akmi_mhd_stage_phase_dt(&pack_c, recon_method, rsolver_method, g0, g1, d->beta[stage - 1], dt_dev, copy_arg, w0.p,
                                   bcc0.p, u0.p, u1.p, b0.x1f.p, b0.x2f.p, b0.x3f.p, b1.x1f.p, b1.x2f.p,
                                   b1.x3f.p, do_dt, counters.p, dt3.p, phases, ws.p, stream));
   else
-  AKCHK(akmi_mhd_stage_phase(&pack_c, recon_method, rsolver_method, g0, g1, beta_dt, copy, w0.p,
+  AKCHK(akmi_mhd_stage_phase(&pack_c, recon_method, rsolver_method, g0, g1, beta_dt, copy_arg, w0.p,
                              bcc0.p, u0.p, u1.p, b0.x1f.p, b0.x2f.p, b0.x3f.p, b1.x1f.p, b1.x2f.p,
                              b1.x3f.p, do_dt, counters.p, dt3.p, phases, ws.p, stream));
   d->ProfMark(stream);
+  NoteForms(stage, phases);
+  if (copy == 3 && (phases & AKMI_PHASE_SWEEPS)) { SwapArr(u0, u1); u_swapped = !u_swapped; }
   if (copy == 2) {
     if (phases & AKMI_PHASE_SWEEPS) { SwapArr(u0, u1); u_swapped = !u_swapped; }
     if (phases & AKMI_PHASE_EMF_CT) {
@@ -1764,6 +1800,26 @@ void akmi_sim_destroy(void *h) { try { delete static_cast<Sim *>(h); } catch (..
 double akmi_sim_time(void *h) { return static_cast<Sim *>(h)->pmesh->time; }
 double akmi_sim_dt(void *h) { return static_cast<Sim *>(h)->pmesh->dt; }
 double akmi_sim_tlim(void *h) { Sim *s = static_cast<Sim *>(h); return s->pdriver ? s->pdriver->tlim : s->pin.GetReal("time", "tlim"); }
+int akmi_sim_stage_forms(void *h, int stage) {
+  AKMI_C_ENTRY("akmi_sim_stage_forms", -1,
+    Sim *s = static_cast<Sim *>(h);
+    if (!s || stage < 1 || stage > 4) return -1;
+    MeshBlockPack *pk = s->pmesh->pmb_pack.get();
+    FluidBase *f = pk->pmhd ? static_cast<FluidBase *>(pk->pmhd.get()) : static_cast<FluidBase *>(pk->phydro.get());
+    return f ? f->stage_forms[stage - 1] : -1;
+  )
+}
+int akmi_sim_counters(void *h, int *out3) {
+  AKMI_C_ENTRY("akmi_sim_counters", AKMI_FAIL,
+    Sim *s = static_cast<Sim *>(h);
+    if (!s || !out3 || s->Refuse("akmi_sim_counters")) return AKMI_FAIL;
+    MeshBlockPack *pk = s->pmesh->pmb_pack.get();
+    FluidBase *f = pk->pmhd ? static_cast<FluidBase *>(pk->pmhd.get()) : static_cast<FluidBase *>(pk->phydro.get());
+    HIPCHK(hipMemcpyAsync(out3, f->counters.p, 3*sizeof(int), hipMemcpyDeviceToHost, f->stream));
+    HIPCHK(hipStreamSynchronize(f->stream));
+    return AKMI_COMPLETE;
+  )
+}
 int akmi_sim_ncycle(void *h) { return static_cast<Sim *>(h)->pmesh->ncycle; }
 int akmi_sim_nmb(void *h) { return static_cast<Sim *>(h)->pmesh->nmb_total; }
 

@@ -443,6 +443,8 @@ class FluidBase {
   // u1 / b1 when the arrays were created (akmi_sim_execute copies back so that akmi_sim_array pointers stay valid)
   bool u_swapped = false, b_swapped = false;
   virtual void RestoreRegisters();
+  // forms (AKMI_FORM_* of include/akmi.h) the stages of the last cycle took, by stage - 1; -1: no such stage has run
+  int stage_forms[4] = {-1, -1, -1, -1};
  public:
   void FinishNewDtPublic() { FinishNewDt(); }
  protected:
@@ -506,6 +508,11 @@ class MHD : public FluidBase {      // mhd.hpp:93-199
   void AssembleMHDTasks(std::map<std::string, std::shared_ptr<TaskList>> tl);
   void StagePhase(Driver *d, int stage, int phases);   // akmi_mhd_stage_phase
   void RestoreRegisters() override;
+  // <mhd>/u0_sweeps = auto | false: the sweeps read what u0 holds from u0 instead of its copy in w0 wherever the stage
+  // does not write the array it reads (U0Copy, akmi_host.cpp); false keeps every stage in the form it had before
+  bool u0_sweeps = false;
+  int U0Copy(const Driver *d, int stage, int phases, int copy) const;
+  void NoteForms(int stage, int phases);
   TaskStatus SaveMHDState(Driver *d, int stage) { return TaskStatus::complete; }
   TaskStatus InitRecv(Driver *d, int stage) { return TaskStatus::complete; }
   TaskStatus CopyCons(Driver *d, int stage);

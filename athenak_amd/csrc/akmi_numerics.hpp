@@ -1215,14 +1215,25 @@ AKMI_DEV void c2p_thermal(const Eos &eos, double wd, double di, double e_kin, do
   }
 }
 
+// The two parts of the primitive state that are functions of the stored conserved state alone.  ConsToPrim and the sweeps
+// that read u0 / the face field instead of w0[0..3] / bcc0 go through the same two helpers, so that
+//   w0[dens] == u0[dens],  w0[vel] == (1.0/u0[dens])*u0[mom],  bcc0 == 0.5*(face_lo + face_hi)
+// hold bit for bit by construction (the density is the floored one ConsToPrim writes back, the momentum is never modified).
+AKMI_DEV void vel_from_cons(double ud, double umx, double umy, double umz, double &di, double &wvx, double &wvy,
+                            double &wvz) {
+  di = 1.0/ud;
+  wvx = di*umx; wvy = di*umy; wvz = di*umz;
+}
+AKMI_DEV double bcc_from_faces(double b_lo, double b_hi) { return 0.5*(b_lo + b_hi); }
+
 // SingleC2P_IdealHyd
 template <bool COLD = false>
 AKMI_DEV void c2p_hyd(const Eos &eos, double &ud, double umx, double umy, double umz, double &ue, double &wd,
                       double &wvx, double &wvy, double &wvz, double &we, bool &dfl, bool &efl, bool &tfl) {
   if (ud < eos.dfloor) { ud = eos.dfloor; dfl = true; }
   wd = ud;
-  const double di = 1.0/ud;
-  wvx = di*umx; wvy = di*umy; wvz = di*umz;
+  double di;
+  vel_from_cons(ud, umx, umy, umz, di, wvx, wvy, wvz);
   const double e_kin = 0.5*di*(sqr(umx) + sqr(umy) + sqr(umz));
   c2p_thermal<COLD>(eos, wd, di, e_kin, 0.0, false, ue, we, efl, tfl);
 }
@@ -1235,8 +1246,8 @@ AKMI_DEV void c2p_mhd(const Eos &eos, double &ud, double umx, double umy, double
   const double dfl_here = fmax(eos.dfloor, bsq/eos.sigma_max);
   if (ud < dfl_here) { ud = dfl_here; dfl = true; }
   wd = ud;
-  const double di = 1.0/ud;
-  wvx = di*umx; wvy = di*umy; wvz = di*umz;
+  double di;
+  vel_from_cons(ud, umx, umy, umz, di, wvx, wvy, wvz);
   const double e_kin = 0.5*di*(sqr(umx) + sqr(umy) + sqr(umz));
   const double e_mag = 0.5*(sqr(ubx) + sqr(uby) + sqr(ubz));
   c2p_thermal(eos, wd, di, e_kin, e_mag, true, ue, we, efl, tfl);

@@ -325,6 +325,11 @@ struct UpdArgs {
 //     swaps the two registers afterwards -- the copy (5 + 3 arrays written) disappears.  Only the cells /
 //     faces the update touches are written: the ghost zones of the new register are filled by the halo
 //     exchange and the boundary conditions that follow every stage.
+// 3 = LAST stage of a cycle OUT OF PLACE (MHD, the k_sweep12s + x3 march sequence only): u0 and u1 are read, the new state
+//     goes to u1's buffer, whose old content (the state at the start of the cycle) nothing reads any more, and the caller
+//     swaps the two registers.  The face field stays in place (k_corner_ct sees copy_b1 == 0).
+// A stage that does not write the array it reads may run the x3 march in its u0 form (AKMI_COPY_X3_U0, sweep_update_body).
+__device__ __forceinline__ bool rk_reads_u1(int copy) { return copy == 0 || copy == 3; }
 __device__ __forceinline__ void rk_store(double *__restrict__ u0, double *__restrict__ u1, int copy, size_t c,
                                          double old, double res) {
   if (copy == 2) { u1[c] = res; return; }
@@ -334,7 +339,7 @@ __device__ __forceinline__ void rk_store(double *__restrict__ u0, double *__rest
 // beta*dt: the product the host forms in RKUpdate (hydro_update.cpp:35), same operands, same rounding
 __device__ __forceinline__ void rk_store_u(double *__restrict__ u0, double *__restrict__ u1, int copy, unsigned ob,
                                            double old, double res) {
-  if (copy == 2) { stu(u1, ob, res); return; }
+  if (copy >= 2) { stu(u1, ob, res); return; }
   if (copy) stu(u1, ob, old);
   stu(u0, ob, res);
 }
@@ -507,10 +512,18 @@ static int march_len(long col_blocks, int ncells, int nmb, int lmax, int wgs_per
 // MODE 0: last direction -- finish the RK update.  MODE 1 (x2 sweep of 3-D runs): store the
 // partial divergence acc = dF1/dx1 + dF2/dx2 for the x3 march, which then needs one array
 // instead of two face pairs per variable (USEACC).  Rounding sequence unchanged.
-template <int DIR, int RECON, bool MHD, int MODE, bool USEACC, int RS, bool P2>
+// U0F (x3 march of an MHD PLM stage that is out of place, copy_u1 2 or 3): every cell's conserved state is read ONCE.  The
+// window takes density and momentum from u0 -- the velocities are formed with vel_from_cons, which is what ConsToPrim
+// stored in w0[1..3], bit for bit -- and only the internal energy from w0[4]; the density and the momentum of the cell a
+// face finishes are the ones the window loaded two steps earlier (momenta parked in registers), so the update fetches
+// u0[4] alone: four streams fewer per cell.  NOT for a stage in place: the priming loads of a chunk read the last two
+// cells of the chunk below, which such a stage has overwritten in u0 by then.
+template <int DIR, int RECON, bool MHD, int MODE, bool USEACC, int RS, bool P2, bool U0F = false>
 __device__ __forceinline__ void sweep_update_body(const Geo &g, const FaceEos &eos, const SweepArgs &a,
                                                   const UpdArgs &u, int ml, double *sm) {
   static_assert(DIR == 1 || DIR == 2, "marching kernel is for the x2/x3 sweeps");
+  static_assert(!U0F || (DIR == 2 && MHD && RECON == 1 && MODE == 0 && USEACC && !rs_iso<RS>() && AKMI_PREFETCH_W &&
+                         AKMI_PREFETCH_UPD), "u0 form: x3 march of MHD PLM with the update");
   constexpr bool STORE = MODE == 2;                                  // all flux components of every face go to memory
   int i, j, k, m, s0;
   bool lane_ok;
@@ -581,14 +594,40 @@ __device__ __forceinline__ void sweep_update_body(const Geo &g, const FaceEos &e
   const double *bb = MHD ? a.bcc0 + (size_t)m*3*cs : nullptr;
   unsigned off = (((unsigned)k*(unsigned)g.N2 + (unsigned)j)*(unsigned)g.N1 + (unsigned)i)*8u;   // cell s
   const unsigned st8 = (unsigned)st*8u;
+  const double *cb = U0F ? u.u0 + (size_t)m*g.nvar*cs : wb;      // U0F: slots 0-3 hold density and MOMENTUM
   auto base = [&](int n) -> const double * {
-    return n == 0 ? wb : n == 1 ? wb + ivx*cs : n == 2 ? wb + ivy*cs : n == 3 ? wb + ivz*cs
+    return n == 0 ? cb : n == 1 ? cb + ivx*cs : n == 2 ? cb + ivy*cs : n == 3 ? cb + ivz*cs
          : n == 4 ? wb + 4*cs : n == 5 ? bb + iby*cs : bb + ibz*cs;
   };
+  double mprev[3] = {0.0, 0.0, 0.0}, mcur[3] = {0.0, 0.0, 0.0};     // U0F: momenta (sweep order) of cells s-1 and s
   // prime the window: left state of the first face comes from cell s0-1
+  if constexpr (U0F) {
+    double qd[3], qm[3][3], qv[3][3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      qd[c] = ldu(base(0) - (2 - c)*st, off);
+#pragma unroll
+      for (int n = 0; n < 3; ++n) qm[n][c] = ldu(base(1 + n) - (2 - c)*st, off);
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      double di;
+      vel_from_cons(qd[c], qm[0][c], qm[1][c], qm[2][c], di, qv[0][c], qv[1][c], qv[2][c]);
+    }
+    double pl, dummy;
+    plm(qd[0], qd[1], qd[2], pl, dummy);
+    W_(0, 0) = qd[1]; W_(0, 1) = qd[2]; PL_(0) = pl;
+#pragma unroll
+    for (int n = 0; n < 3; ++n) {
+      plm(qv[n][0], qv[n][1], qv[n][2], pl, dummy);
+      W_(1 + n, 0) = qv[n][1]; W_(1 + n, 1) = qv[n][2]; PL_(1 + n) = pl;
+      mprev[n] = qm[n][1]; mcur[n] = qm[n][2];
+    }
+  }
 #pragma unroll
   for (int n = 0; n < NV; ++n) {
     if (ISO && n == 4) continue;
+    if (U0F && n < 4) continue;
     const double *q = base(n);
     double pl, dummy;
     if constexpr (RECON == 1) {
@@ -639,6 +678,11 @@ __device__ __forceinline__ void sweep_update_body(const Geo &g, const FaceEos &e
       for (int n = 0; n < NV; ++n) nx2[n] = (more && !(ISO && n == 4)) ? ldu(base(n) + (LA + 1)*st, off) : 0.0;
     }
     double L[NV], R[NV];
+    double vnx[3] = {0.0, 0.0, 0.0}, dsc = 0.0;          // U0F: velocities of cell s+1, density of the cell this face finishes
+    if constexpr (U0F) {
+      double di;
+      vel_from_cons(nx[0], nx[1], nx[2], nx[3], di, vnx[0], vnx[1], vnx[2]);
+    }
 #pragma unroll
     for (int n = 0; n < NV; ++n) {
       if (ISO && n == 4) { L[n] = R[n] = 0.0; continue; }      // isothermal: no energy variable
@@ -647,8 +691,10 @@ __device__ __forceinline__ void sweep_update_body(const Geo &g, const FaceEos &e
       L[n] = PL_(n);
       if constexpr (RECON == 1) {
         double qp;
-        if constexpr (PW) qp = nx[n]; else qp = ldu(q + st, off);
+        if constexpr (U0F) qp = (n >= 1 && n <= 3) ? vnx[n >= 1 && n <= 3 ? n - 1 : 0] : nx[n];
+        else if constexpr (PW) qp = nx[n]; else qp = ldu(q + st, off);
         const double w0 = W_(n, 0), w1 = W_(n, 1);
+        if (U0F && n == 0) dsc = w0;
         plm(w0, w1, qp, qln, R[n]);
         W_(n, 0) = w1; W_(n, 1) = qp;
       } else if constexpr (RECON >= 2) {
@@ -683,9 +729,11 @@ __device__ __forceinline__ void sweep_update_body(const Geo &g, const FaceEos &e
 #pragma unroll
         for (int n = 0; n < 5; ++n) {
           if (ISO && n == 4) continue;
-          pa[n] = ldu(u.acc + mb + n*cs, ocm); pu[n] = ldu(u.u0 + mb + n*cs, ocm);
+          pa[n] = ldu(u.acc + mb + n*cs, ocm);
+          if (!U0F || n == 4) pu[n] = ldu(u.u0 + mb + n*cs, ocm);
         }
-        if (AKMI_PREFETCH_U1 && !u.copy_u1) {
+        if constexpr (U0F) { pu[0] = dsc; pu[ivx] = mprev[0]; pu[ivy] = mprev[1]; pu[ivz] = mprev[2]; }
+        if (AKMI_PREFETCH_U1 && rk_reads_u1(u.copy_u1)) {
 #pragma unroll
           for (int n = 0; n < 5; ++n) { if (ISO && n == 4) continue; pu1[n] = ldu(u.u1 + mb + n*cs, ocm); }
         }
@@ -750,8 +798,8 @@ __device__ __forceinline__ void sweep_update_body(const Geo &g, const FaceEos &e
           divf += p2 ? ldexp(dlast, n3) : dlast/dx3;
           const double u0v = pu[n];
           double u1v;
-          if constexpr (AKMI_PREFETCH_U1) u1v = u.copy_u1 ? u0v : pu1[n];
-          else u1v = u.copy_u1 ? u0v : ldu(u.u1 + mb + n*cs, ocm);
+          if constexpr (AKMI_PREFETCH_U1) u1v = !rk_reads_u1(u.copy_u1) ? u0v : pu1[n];
+          else u1v = !rk_reads_u1(u.copy_u1) ? u0v : ldu(u.u1 + mb + n*cs, ocm);
           rk_store_u(u.u0 + mb + n*cs, u.u1 + mb + n*cs, u.copy_u1, ocm, u0v, u.gam0*u0v + u.gam1*u1v - bdt*divf);
         }
       } else {
@@ -777,8 +825,8 @@ __device__ __forceinline__ void sweep_update_body(const Geo &g, const FaceEos &e
         }
         if constexpr (MODE != 1) {
           if constexpr (PRE) u0v[n] = pu[n]; else u0v[n] = ldu(u.u0 + mb + n*cs, ocm);
-          if constexpr (PRE && AKMI_PREFETCH_U1) u1v[n] = u.copy_u1 ? u0v[n] : pu1[n];
-          else u1v[n] = u.copy_u1 ? u0v[n] : ldu(u.u1 + mb + n*cs, ocm);
+          if constexpr (PRE && AKMI_PREFETCH_U1) u1v[n] = !rk_reads_u1(u.copy_u1) ? u0v[n] : pu1[n];
+          else u1v[n] = !rk_reads_u1(u.copy_u1) ? u0v[n] : ldu(u.u1 + mb + n*cs, ocm);
         }
       }
       auto finish = [&](auto P2c) {
@@ -810,6 +858,10 @@ __device__ __forceinline__ void sweep_update_body(const Geo &g, const FaceEos &e
 #pragma unroll
     for (int n = 0; n < 5; ++n) { if (ISO && n == 4) continue; FP_(n) = fv[n]; }
     o1 += st18;
+    if constexpr (U0F) {
+#pragma unroll
+      for (int n = 0; n < 3; ++n) { mprev[n] = mcur[n]; mcur[n] = nx[1 + n]; }
+    }
     if constexpr (PW) {
 #pragma unroll
       for (int n = 0; n < NV; ++n) nx[n] = nx2[n];
@@ -823,14 +875,14 @@ __device__ __forceinline__ void sweep_update_body(const Geo &g, const FaceEos &e
 // the kernel proper: when the cell sizes of the block are powers of two, x/dx == x*(1/dx) bit for
 // bit (both are the correctly rounded value of the same real number, and 1/dx is exact), so the
 // divisions by dx become products; decided per block, two copies of the loop
-template <int DIR, int RECON, bool MHD, int MODE, bool USEACC, int RS>
+template <int DIR, int RECON, bool MHD, int MODE, bool USEACC, int RS, bool U0F = false>
 __global__ void __launch_bounds__(SX*SY, (RECON >= 2 ? 2 : (DIR == 2 ? AKMI_X3_WAVES : AKMI_X2_WAVES)))
 k_sweep_update(Geo g, FaceEos eos, SweepArgs a, UpdArgs u, int ml) {
   constexpr int NV = MHD ? 7 : 5;
   __shared__ double sm[(((RECON >= 2) && AKMI_PPM_WREG ? 0 : NV*RollCfg<RECON>::NW) + NV + 5)*SX*SY];
   const int m = blockIdx.z;
   constexpr bool TRY = AKMI_POW2DX != 0;      // power-of-two cell sizes: x/dx by v_ldexp_f64 (wave-uniform run-time choice)
-  sweep_update_body<DIR, RECON, MHD, MODE, USEACC, RS, TRY>(g, eos, a, u, ml, sm);
+  sweep_update_body<DIR, RECON, MHD, MODE, USEACC, RS, TRY, U0F>(g, eos, a, u, ml, sm);
 }
 
 
@@ -1260,12 +1312,12 @@ k_c2p_newdt(Geo g, Eos eos, double *__restrict__ u0, const double *__restrict__ 
     const size_t c = ix5(g.nvar, g.N3, g.N2, g.N1, m, 0, k, j, i);
     double wd, wvx, wvy, wvz, we = 0.0, ubx = 0, uby = 0, ubz = 0;
     if constexpr (MHD) {
-      ubx = 0.5*(bx1f[ix4(g.N3, g.N2, g.N1 + 1, m, k, j, i)] +
-                 bx1f[ix4(g.N3, g.N2, g.N1 + 1, m, k, j, i + 1)]);
-      uby = 0.5*(bx2f[ix4(g.N3, g.N2 + 1, g.N1, m, k, j, i)] +
-                 bx2f[ix4(g.N3, g.N2 + 1, g.N1, m, k, j + 1, i)]);
-      ubz = 0.5*(bx3f[ix4(g.N3 + 1, g.N2, g.N1, m, k, j, i)] +
-                 bx3f[ix4(g.N3 + 1, g.N2, g.N1, m, k + 1, j, i)]);
+      ubx = bcc_from_faces(bx1f[ix4(g.N3, g.N2, g.N1 + 1, m, k, j, i)],
+                           bx1f[ix4(g.N3, g.N2, g.N1 + 1, m, k, j, i + 1)]);
+      uby = bcc_from_faces(bx2f[ix4(g.N3, g.N2 + 1, g.N1, m, k, j, i)],
+                           bx2f[ix4(g.N3, g.N2 + 1, g.N1, m, k, j + 1, i)]);
+      ubz = bcc_from_faces(bx3f[ix4(g.N3 + 1, g.N2, g.N1, m, k, j, i)],
+                           bx3f[ix4(g.N3 + 1, g.N2, g.N1, m, k + 1, j, i)]);
       const size_t b = ix5(3, g.N3, g.N2, g.N1, m, 0, k, j, i);
       bcc0[b] = ubx; bcc0[b + cs] = uby; bcc0[b + 2*cs] = ubz;
     }
@@ -1371,11 +1423,11 @@ k_c2p_newdt2(Geo g, Eos eos, double *__restrict__ u0, const double *__restrict__
     if constexpr (MHD) {
       const double *b1 = bx1f + ix4(g.N3, g.N2, g.N1 + 1, m, k, j, i);
       const double f0 = b1[0], f1 = b1[1], f2 = b1[2];
-      ubx[0] = 0.5*(f0 + f1); ubx[1] = 0.5*(f1 + f2);
+      ubx[0] = bcc_from_faces(f0, f1); ubx[1] = bcc_from_faces(f1, f2);
       const d2_t y0 = ld2(bx2f + ix4(g.N3, g.N2 + 1, g.N1, m, k, j, i)), y1 = ld2(bx2f + ix4(g.N3, g.N2 + 1, g.N1, m, k, j + 1, i));
-      uby[0] = 0.5*(y0.x + y1.x); uby[1] = 0.5*(y0.y + y1.y);
+      uby[0] = bcc_from_faces(y0.x, y1.x); uby[1] = bcc_from_faces(y0.y, y1.y);
       const d2_t z0 = ld2(bx3f + ix4(g.N3 + 1, g.N2, g.N1, m, k, j, i)), z1 = ld2(bx3f + ix4(g.N3 + 1, g.N2, g.N1, m, k + 1, j, i));
-      ubz[0] = 0.5*(z0.x + z1.x); ubz[1] = 0.5*(z0.y + z1.y);
+      ubz[0] = bcc_from_faces(z0.x, z1.x); ubz[1] = bcc_from_faces(z0.y, z1.y);
       const size_t b = ix5(3, g.N3, g.N2, g.N1, m, 0, k, j, i);
       st2nt(bcc0 + b, ubx[0], ubx[1]); st2nt(bcc0 + b + cs, uby[0], uby[1]); st2nt(bcc0 + b + 2*cs, ubz[0], ubz[1]);
     }
@@ -1782,7 +1834,7 @@ static int launch_sweep(const Geo &g, const Scheme &sc, const SweepArgs &a, hipS
 
 template <int DIR, bool MHD, int MODE = 0, bool USEACC = false>
 static int launch_sweep_update(const Geo &g, const Scheme &sc, const SweepArgs &a,
-                               const UpdArgs &u, hipStream_t st) {
+                               const UpdArgs &u, hipStream_t st, bool u0_form = false) {
   int rc;
   if constexpr (DIR == 0) {
     dim3 grid(cdiv(a.iu - a.il + 1, TX - 1), 1, g.nmb), block(TX, 1);
@@ -1811,6 +1863,17 @@ static int launch_sweep_update(const Geo &g, const Scheme &sc, const SweepArgs &
       grid = dim3(nb, cdiv(nc, ml), g.nmb);
     }
     constexpr int D = (DIR == 0) ? 1 : DIR;
+    if (u0_form) {
+      // the x3 march in its u0 form: MHD, PLM, HLLD, ideal gas (what stage_update asks it for)
+      if constexpr (MHD && DIR == 2 && MODE == 0 && USEACC) {
+        if (sc.iso || sc.recon != 1 || sc.rsolver != AKMI_RS_HLLD) { set_error("x3 march, u0 form: PLM + HLLD, ideal gas"); return AKMI_FAIL; }
+        k_sweep_update<2, 1, true, 0, true, 3, true><<<grid, block, 0, st>>>(g, sc.eos, a, u, ml);
+        rc = AKMI_COMPLETE;
+      } else {
+        set_error("sweep_update: the u0 form exists for the x3 march of MHD only");
+        return AKMI_FAIL;
+      }
+    } else
     rc = dispatch_scheme_eos<MHD>(sc, [&](auto R, auto S) {
       k_sweep_update<D, decltype(R)::value, MHD, MODE, USEACC, decltype(S)::value>
           <<<grid, block, 0, st>>>(g, sc.eos, a, u, ml);
@@ -2133,9 +2196,9 @@ k_c2p_shell(Geo g, Eos eos, double *__restrict__ u0, const double *__restrict__ 
   double wd, wvx, wvy, wvz, we;
   double ubx = 0.0, uby = 0.0, ubz = 0.0;
   if constexpr (MHD) {
-    ubx = 0.5*(bx1f[ix4(g.N3, g.N2, g.N1 + 1, m, k, j, i)] + bx1f[ix4(g.N3, g.N2, g.N1 + 1, m, k, j, i + 1)]);
-    uby = 0.5*(bx2f[ix4(g.N3, g.N2 + 1, g.N1, m, k, j, i)] + bx2f[ix4(g.N3, g.N2 + 1, g.N1, m, k, j + 1, i)]);
-    ubz = 0.5*(bx3f[ix4(g.N3 + 1, g.N2, g.N1, m, k, j, i)] + bx3f[ix4(g.N3 + 1, g.N2, g.N1, m, k + 1, j, i)]);
+    ubx = bcc_from_faces(bx1f[ix4(g.N3, g.N2, g.N1 + 1, m, k, j, i)], bx1f[ix4(g.N3, g.N2, g.N1 + 1, m, k, j, i + 1)]);
+    uby = bcc_from_faces(bx2f[ix4(g.N3, g.N2 + 1, g.N1, m, k, j, i)], bx2f[ix4(g.N3, g.N2 + 1, g.N1, m, k, j + 1, i)]);
+    ubz = bcc_from_faces(bx3f[ix4(g.N3 + 1, g.N2, g.N1, m, k, j, i)], bx3f[ix4(g.N3 + 1, g.N2, g.N1, m, k + 1, j, i)]);
     const size_t b = ix5(3, g.N3, g.N2, g.N1, m, 0, k, j, i);
     bcc0[b] = ubx; bcc0[b + cs] = uby; bcc0[b + 2*cs] = ubz;
   }
@@ -2276,6 +2339,21 @@ int sweeps_store_fluxes(const akmi_pack *p, int recon, int rsolver, const double
                                       nullptr, st);
 }
 
+// forms (AKMI_FORM_*) of the last stage call of this thread that ran sweeps: akmi_stage_last_forms
+static thread_local int last_forms = 0;
+
+static bool mhd_one_kernel() {     // AKMI_MHD_ONE_KERNEL=1: k_mhd_stage3d instead of k_sweep12s + x3 march (A/B runs)
+  static const bool on = getenv("AKMI_MHD_ONE_KERNEL") && atoi(getenv("AKMI_MHD_ONE_KERNEL")) != 0;   // opt-in until it wins
+  return on;
+}
+// the stage takes k_sweep12s + the x3 march (the branch of stage_update that knows copy_u1 == 3 and the u0 form)
+template <bool MHD>
+static bool mhd_u0_sweeps_path(const akmi_pack *p, int recon, int rsolver) {
+  if (!MHD) return false;
+  const Geo g = make_geo(p);
+  return g.three_d && recon == 1 && p->is_ideal && rsolver == AKMI_RS_HLLD && g.nvar == 5 && !mhd_one_kernel();
+}
+
 struct C2PArgs {          // ConsToPrim of the active cells (+ CFL scan) at the end of the stage call
   int enable, do_newdt;
   int *counters;
@@ -2288,12 +2366,25 @@ struct C2PArgs {          // ConsToPrim of the active cells (+ CFL scan) at the 
 template <bool MHD>
 static int stage_update(const akmi_pack *p, int recon, int rsolver, double gam0, double gam1,
                         double beta_dt,
-                        int copy_u1, const double *w0, const double *bcc0, double *u0, double *u1,
+                        int copy_arg, const double *w0, const double *bcc0, double *u0, double *u1,
                         double *b0x1f, double *b0x2f, double *b0x3f, double *b1x1f, double *b1x2f,
                         double *b1x3f, void *ws, const C2PArgs &cp_in, hipStream_t st,
                         int phases = AKMI_PHASE_ALL, const double *dt_dev = nullptr, double *w_out = nullptr,
                         int *wrote_new = nullptr) {
   if (check_scheme(p, recon, "stage") != AKMI_COMPLETE) return AKMI_FAIL;
+  const int copy_u1 = copy_arg & AKMI_COPY_MASK;
+  const bool want_x3_u0 = (copy_arg & AKMI_COPY_X3_U0) != 0;
+  if (copy_u1 > 3 || (copy_arg & ~(AKMI_COPY_MASK | AKMI_COPY_X3_U0))) { set_error("stage: bad copy_u1 = %d", copy_arg); return AKMI_FAIL; }
+  if (want_x3_u0 && copy_u1 < 2) {
+    set_error("stage: the u0 form of the x3 march needs a stage that does not write the array it reads (copy_u1 2 or 3)");
+    return AKMI_FAIL;
+  }
+  const bool sweeps_asked = (phases & AKMI_PHASE_SWEEPS) != 0;
+  if ((copy_u1 == 3 || want_x3_u0) && sweeps_asked && !mhd_u0_sweeps_path<MHD>(p, recon, rsolver)) {
+    set_error("stage: copy_u1 = 3 / AKMI_COPY_X3_U0 exist for the k_sweep12s + x3 march sequence only (MHD, 3-D, PLM + HLLD, ideal gas)");
+    return AKMI_FAIL;
+  }
+  if (sweeps_asked) last_forms = 0;
   if (p->nvar < (p->is_ideal ? 5 : 4)) {
     set_error("stage: nvar = %d is smaller than the fluid variable set of the EOS", p->nvar);
     return AKMI_FAIL;
@@ -2319,7 +2410,7 @@ static int stage_update(const akmi_pack *p, int recon, int rsolver, double gam0,
   UpdArgs u{gam0, gam1, beta_dt, u0, u1, w.flx1, w.flx2, copy_u1, w.acc, dt_dev};
   // copy_u1 == 2 (out-of-place first stage): the new state lands in u1 / b1, which is what the c2p
   // of the active cells has to read
-  double *un = copy_u1 == 2 ? u1 : u0;
+  double *un = copy_u1 >= 2 ? u1 : u0;
   const double *n1f = copy_u1 == 2 ? b1x1f : b0x1f, *n2f = copy_u1 == 2 ? b1x2f : b0x2f,
                *n3f = copy_u1 == 2 ? b1x3f : b0x3f;
   int rc = AKMI_COMPLETE;
@@ -2376,8 +2467,7 @@ static int stage_update(const akmi_pack *p, int recon, int rsolver, double gam0,
   //  measured slower at every slab thickness in rounds 1 and 3 -- profiles/r03_slab_ab.txt; it left the source in round 5.)
   // AKMI_HYDRO_ONE_KERNEL=0: the three-kernel sweep/march sequence also for hydro DC/PLM (A/B runs)
   static const bool hyd_one = !(getenv("AKMI_HYDRO_ONE_KERNEL") && atoi(getenv("AKMI_HYDRO_ONE_KERNEL")) == 0);
-  // AKMI_MHD_ONE_KERNEL=1: k_mhd_stage3d instead of k_sweep12s + x3 march (A/B runs)
-  static const bool mhd_one = getenv("AKMI_MHD_ONE_KERNEL") && atoi(getenv("AKMI_MHD_ONE_KERNEL")) != 0;   // opt-in until it wins
+  const bool mhd_one = mhd_one_kernel();
   const int kA = g.ks, kB = g.ke;
   SweepArgs b1 = a1, b2 = a2, b3 = a3;
   b1.kl = kA - (MHD ? 1 : 0); b1.ku = kB + (MHD ? 1 : 0);
@@ -2410,7 +2500,8 @@ static int stage_update(const akmi_pack *p, int recon, int rsolver, double gam0,
     // (the other order -- x3 march first, leaving dF3/dx3, k_sweep12s finishing the update -- was built and measured in
     //  round 4: x3 march 891 -> 602 us, k_sweep12s 1130 -> 1374 us, +1 % on the bench; profiles/r04_x3first.txt)
     if constexpr (MHD) rc = launch_sweep12s(g, sc, b1, b2, u, st);
-    if (rc == AKMI_COMPLETE) rc = launch_sweep_update<2, MHD, 0, true>(g, sc, b3, u, st);
+    if (rc == AKMI_COMPLETE) rc = launch_sweep_update<2, MHD, 0, true>(g, sc, b3, u, st, want_x3_u0);
+    if (rc == AKMI_COMPLETE && want_x3_u0) last_forms |= AKMI_FORM_X3_U0;
   } else if (do_sweeps) {
     rc = MHD ? launch_sweep<0, MHD, MHD>(g, sc, b1, st)
              : launch_sweep<0, MHD, false>(g, sc, b1, st);
@@ -2430,7 +2521,7 @@ static int stage_update(const akmi_pack *p, int recon, int rsolver, double gam0,
     k_corner_ct<<<grid, block, 7*tl.tw*tl.th*sizeof(double), st>>>(
         g, w.efc[0], w.efc[1], w.efc[2], w.efc[3], w.efc[4], w.efc[5], w.ecc[0], w.ecc[1], w.ecc[2],
         w.flx1, w.flx2, w.flx3, gam0, gam1, beta_dt, b0x1f, b0x2f, b0x3f, b1x1f, b1x2f, b1x3f,
-        copy_u1, kA, kB, 1, nchunk, ckl, tl.tw, tl.th, dt_dev);
+        copy_u1 == 3 ? 0 : copy_u1, kA, kB, 1, nchunk, ckl, tl.tw, tl.th, dt_dev);
     AKMI_CHECK_LAUNCH("corner_ct");
   }
   if (cp.enable && !c2p_done)
@@ -2569,6 +2660,12 @@ int akmi_mhd_stage_phase_dt(const akmi_pack *p, int recon, int rsolver, double g
   C2PArgs cp{1, do_newdt, counters, dt3};
   return stage_update<true>(p, recon, rsolver, gam0, gam1, beta, copy_u1, w0, bcc0, u0, u1, b0x1f, b0x2f,
                             b0x3f, b1x1f, b1x2f, b1x3f, ws, cp, (hipStream_t)stream, phases, dt_dev);
+}
+
+int akmi_stage_last_forms(void) { return last_forms; }
+
+int akmi_mhd_u0_sweeps_eligible(const akmi_pack *p, int recon, int rsolver) {
+  return mhd_u0_sweeps_path<true>(p, recon, rsolver) ? 1 : 0;
 }
 
 int akmi_hydro_stage_w_eligible(const akmi_pack *p, int recon, int rsolver) {

@@ -173,6 +173,17 @@ class NativeSimulation:
         capi.check(self.L.akmi_sim_turb_history(self.h, out), "sim_turb_history")
         return [float(v) for v in out]
 
+    def stage_forms(self, stage):
+        """which forms (capi.FORM_*) stage `stage` (1-based) of the last cycle took: the x3 march from u0, k_sweep12s from
+        u0 and the faces, the lean conversion before it; -1 when no such stage has run"""
+        return int(self.L.akmi_sim_stage_forms(self.h, int(stage)))
+
+    def floor_counters(self):
+        """(density, energy, temperature) floor counts of the conversions so far (EventCounters of the reference)"""
+        out = (C.c_int*3)()
+        capi.check(self.L.akmi_sim_counters(self.h, out), "sim_counters")
+        return tuple(int(v) for v in out)
+
     time = property(lambda s: s.L.akmi_sim_time(s.h))
     dt = property(lambda s: s.L.akmi_sim_dt(s.h))
     tlim = property(lambda s: s.L.akmi_sim_tlim(s.h))

@@ -498,7 +498,20 @@ long long akmi_stage_workspace_bytes(const akmi_pack *p, int is_mhd);
  * Hydro::CopyCons / MHD::CopyCons (5 + 3 arrays written) disappears.  Only the cells and faces the update
  * touches are written; the ghost zones of the new register are filled by the halo exchange and the
  * boundary conditions that follow every stage.  With akmi_*_stage_phase the swap of u follows the
- * SWEEPS part and the swap of b the EMF_CT part (the C2P part is passed the swapped pointers). */
+ * SWEEPS part and the swap of b the EMF_CT part (the C2P part is passed the swapped pointers).
+ * copy_u1 == 3 (MHD, 3-D PLM + HLLD ideal gas: akmi_mhd_u0_sweeps_eligible): the LAST stage of a cycle OUT OF PLACE --
+ * u0 and u1 are read, the new state is written to u1's buffer (the state of the start of the cycle, which nothing
+ * reads any more) and the caller swaps u0/u1 afterwards; b0 is updated in place, b0/b1 are not swapped.
+ * AKMI_COPY_X3_U0, or-ed into copy_u1 == 2 or 3 by a caller whose w0 is ConsToPrim of u0 in every cell, ghost zones
+ * included: the x3 march reads density and momentum once, from u0, instead of w0[0..3] for its window and u0[0..3]
+ * again for the update (bit-identical results; refused for a stage that writes the array it reads).
+ * akmi_stage_last_forms(): which forms the last stage call of this thread that ran sweeps took, a mask of AKMI_FORM_*. */
+enum { AKMI_COPY_X3_U0 = 0x100, AKMI_COPY_MASK = 0xff };
+enum { AKMI_FORM_X3_U0 = 1,     /* x3 march read u0 for its window and parked it for the update */
+       AKMI_FORM_X12_U0 = 2,    /* k_sweep12s read u0 and the face field (not built: always 0)  */
+       AKMI_FORM_LEAN_C2P = 4 };/* the conversion before the stage stored w0[4] only (not built: always 0) */
+int akmi_stage_last_forms(void);
+int akmi_mhd_u0_sweeps_eligible(const akmi_pack *p, int recon, int rsolver);
 int akmi_hydro_stage_update(const akmi_pack *p, int recon, int rsolver, double gam0,
                             double gam1, double beta_dt, int copy_u1, const double *w0,
                             double *u0, double *u1, void *ws, void *stream);
@@ -643,6 +656,10 @@ double akmi_sim_time(void *sim);
 double akmi_sim_dt(void *sim);
 double akmi_sim_tlim(void *sim);
 int akmi_sim_ncycle(void *sim);
+/* forms (AKMI_FORM_* mask) the given stage (1-based) took in the last cycle run; -1 when no such stage has run */
+int akmi_sim_stage_forms(void *sim, int stage);
+/* the three floor counters of the fluid's conversions (density, energy, temperature), as they stand on the device */
+int akmi_sim_counters(void *sim, int *out3);
 int akmi_sim_nmb(void *sim);
 void *akmi_sim_array(void *sim, const char *name, long long *count);
 const int *akmi_sim_lloc(void *sim);
