@@ -7,7 +7,8 @@ not gpu: properties of the oracle's restatement that the reference relies on --
   * the face-field prolongation (shared faces + Toth & Roe interior) keeps div B of every fine
     cell equal to that of its coarse parent, i.e. a divergence-free coarse field stays
     divergence-free, and restricting the prolongated field returns the coarse faces.
-gpu: the HIP kernels against the oracle, bit for bit, in 1-D, 2-D and 3-D."""
+gpu: the HIP kernels against the oracle, bit for bit, in 1-D, 2-D and 3-D, on blocks narrower than one 64x4 tile of
+the kernels' thread mapping and on blocks whose boxes take two or three tiles along x1."""
 import ctypes as C
 
 import numpy as np
@@ -15,11 +16,35 @@ import pytest
 
 from oracle import akref
 
-DIMS = {1: (16, 1, 1), 2: (16, 12, 1), 3: (12, 8, 8)}
+# named MeshBlock shapes: (name, (nx1, nx2, nx3), nmb).  "1", "2", "3": every box inside one 64x4 tile.  The wide ones
+# (fine extents even) put 2-3 tiles along x1; nmb = 3 leaves blocks 0 and 2 to the masked forms and makes nk*nv*nmb no
+# power of two.
+SHAPES = [
+    ("1", (16, 1, 1), 2),
+    ("2", (16, 12, 1), 2),
+    ("3", (12, 8, 8), 2),
+    ("132x1x1", (132, 1, 1), 3),       # coarse box 66 wide, fine box 132: 2 and 3 x1 tiles
+    ("130x10x1", (130, 10, 1), 3),     # coarse 65 x 5: one spill lane, rows off the tile of 4
+    ("128x6x6", (128, 6, 6), 3),       # coarse 64: one full tile; the shared-face boxes are 65 wide
+    ("132x10x6", (132, 10, 6), 3),     # everything off the tile grid in 3-D
+    # coarse boxes of 97..128 lanes: two tiles whose second one starts past lane 96, so that a tile stride anywhere
+    # between 32 and 64 leaves lanes out (a 66-wide box is covered by two tiles of any such stride)
+    ("200x1x1", (200, 1, 1), 3),
+    ("196x6x4", (196, 6, 4), 3),
+]
+_SHAPE = {name: (nx, nmb) for name, nx, nmb in SHAPES}
+NARROW = ["1", "2", "3"]
+ALL = [name for name, _, _ in SHAPES]
 
 
-def _setup(dims, ng=2, nmb=2, nvar=5, seed=3):
-    nx1, nx2, nx3 = DIMS[dims]
+def _dims(shape):
+    nx = _SHAPE[shape][0]
+    return 1 + (nx[1] > 1) + (nx[2] > 1)
+
+
+def _setup(shape, ng=2, nvar=5, seed=3):
+    (nx1, nx2, nx3), nmb = _SHAPE[shape]
+    dims = _dims(shape)
     pk, dx = akref.make_pack(nmb, nx1, nx2, nx3, ng, np.ones((nmb, 3)), 1.4)
     N1, N2, N3 = nx1 + 2*ng, (nx2 + 2*ng if nx2 > 1 else 1), (nx3 + 2*ng if nx3 > 1 else 1)
     c1, c2, c3 = nx1//2 + 2*ng, (nx2//2 + 2*ng if nx2 > 1 else 1), (nx3//2 + 2*ng if nx3 > 1 else 1)
@@ -66,10 +91,10 @@ def _div(b, dims, sl):
     return d
 
 
-@pytest.mark.parametrize("dims", [1, 2, 3])
-def test_restriction_undoes_prolongation(dims):
+@pytest.mark.parametrize("shape", NARROW + ["132x10x6"])
+def test_restriction_undoes_prolongation(shape):
     R = akref.lib()
-    a = _setup(dims)
+    a = _setup(shape)
     box = _active_box(a)
     R.akref_prolong_cc(C.byref(a["pk"]), a["nvar"], akref.ptr(box), akref.ptr(a["cu"]), akref.ptr(a["u"]))
     cu2 = np.zeros_like(a["cu"])
@@ -78,10 +103,11 @@ def test_restriction_undoes_prolongation(dims):
     assert np.abs(cu2[act] - a["cu"][act]).max() < 1e-14
 
 
-@pytest.mark.parametrize("dims", [1, 2, 3])
-def test_prolongation_is_exact_for_linear_data(dims):
+@pytest.mark.parametrize("shape", NARROW + ["132x10x6"])
+def test_prolongation_is_exact_for_linear_data(shape):
     R = akref.lib()
-    a = _setup(dims)
+    a = _setup(shape)
+    dims = a["dims"]
     c3, c2, c1 = a["cN"]
     K, J, I = np.meshgrid(np.arange(c3), np.arange(c2), np.arange(c1), indexing="ij")
     lin = 0.5 + 0.25*I + (0.125*J if dims > 1 else 0) - (0.375*K if dims > 2 else 0)
@@ -101,10 +127,11 @@ def test_prolongation_is_exact_for_linear_data(dims):
     assert np.abs(a["u"][s] - exact[s[2:]]).max() < 1e-14
 
 
-@pytest.mark.parametrize("dims", [2, 3])
-def test_field_prolongation_preserves_divergence(dims):
+@pytest.mark.parametrize("shape", ["2", "3", "132x10x6"])
+def test_field_prolongation_preserves_divergence(shape):
     R = akref.lib()
-    a = _setup(dims)
+    a = _setup(shape)
+    dims = a["dims"]
     _prolong_field(R, a)
     ng = a["ng"]
     N3, N2, N1 = a["N"]
@@ -131,12 +158,12 @@ def test_field_prolongation_preserves_divergence(dims):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("ng", [2, 4])
-@pytest.mark.parametrize("dims", [1, 2, 3])
-def test_hip_operators_match_the_oracle(dims, ng):
+@pytest.mark.parametrize("shape", ALL)
+def test_hip_operators_match_the_oracle(shape, ng):
     import torch
     from athenak_amd import capi
     L, R = capi.lib(), akref.lib()
-    a = _setup(dims, ng=ng, seed=11 + dims)
+    a = _setup(shape, ng=ng, seed=11 + _dims(shape))
     t = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
     dxd = t(a["dx"])
     pkd = capi.Pack.from_buffer_copy(bytes(a["pk"]))
@@ -241,12 +268,13 @@ def _edge_boxes(a):
     return out
 
 
-@pytest.mark.parametrize("dims", [1, 2, 3])
-def test_restricted_fluxes_conserve(dims):
+@pytest.mark.parametrize("shape", NARROW)
+def test_restricted_fluxes_conserve(shape):
     """area-weighted sum of the fine fluxes through a coarse face == the restricted flux; an EMF that is
     constant along an edge restricts to itself; buffer order (t1 fastest, then t2, then variable)"""
     R = akref.lib()
-    a = _setup(dims, ng=2, seed=21 + dims)
+    dims = _dims(shape)
+    a = _setup(shape, ng=2, seed=21 + dims)
     rng = np.random.default_rng(5)
     flx, emf = _flux_arrays(a, rng)
     nv = a["nvar"]
@@ -292,12 +320,12 @@ def test_restricted_fluxes_conserve(dims):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("ng", [2, 3])
-@pytest.mark.parametrize("dims", [1, 2, 3])
-def test_hip_flux_restriction_matches_the_oracle(dims, ng):
+@pytest.mark.parametrize("shape", ALL)
+def test_hip_flux_restriction_matches_the_oracle(shape, ng):
     import torch
     from athenak_amd import capi
     L, R = capi.lib(), akref.lib()
-    a = _setup(dims, ng=ng, seed=31 + dims)
+    a = _setup(shape, ng=ng, seed=31 + _dims(shape))
     flx, emf = _flux_arrays(a, np.random.default_rng(7))
     t = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
     dxd = t(a["dx"])
@@ -345,9 +373,9 @@ def _p2c_numpy(w, bcc, ideal):
     return u
 
 
-def _p2c_case(dims, mhd, ideal, nscal, seed):
-    nx1, nx2, nx3 = DIMS[dims]
-    ng, nmb = 2, 2
+def _p2c_case(shape, mhd, ideal, nscal, seed):
+    (nx1, nx2, nx3), nmb = _SHAPE[shape]
+    ng = 2
     nv = (5 if ideal else 4) + nscal
     pk, dx = akref.make_pack(nmb, nx1, nx2, nx3, ng, np.ones((nmb, 3)), 1.4, nvar=nv)
     pk.is_ideal = int(ideal)
@@ -361,10 +389,10 @@ def _p2c_case(dims, mhd, ideal, nscal, seed):
 
 
 @pytest.mark.parametrize("mhd,ideal,nscal", [(False, True, 0), (True, True, 0), (False, False, 2), (True, True, 1)])
-@pytest.mark.parametrize("dims", [1, 3])
-def test_prim2cons_is_the_reference_formula(dims, mhd, ideal, nscal):
+@pytest.mark.parametrize("shape", ["1", "3"])
+def test_prim2cons_is_the_reference_formula(shape, mhd, ideal, nscal):
     R = akref.lib()
-    pk, dx, w, bcc, box = _p2c_case(dims, mhd, ideal, nscal, 41)
+    pk, dx, w, bcc, box = _p2c_case(shape, mhd, ideal, nscal, 41)
     u = np.full_like(w, 7.0)
     assert R.akref_prim2cons(C.byref(pk), akref.ptr(box), akref.ptr(w), akref.ptr(bcc) if mhd else None,
                              akref.ptr(u)) == 0
@@ -378,12 +406,12 @@ def test_prim2cons_is_the_reference_formula(dims, mhd, ideal, nscal):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("mhd,ideal,nscal", [(False, True, 0), (True, True, 0), (False, False, 2), (True, True, 1)])
-@pytest.mark.parametrize("dims", [1, 2, 3])
-def test_hip_prim2cons_matches_the_oracle(dims, mhd, ideal, nscal):
+@pytest.mark.parametrize("shape", ALL)
+def test_hip_prim2cons_matches_the_oracle(shape, mhd, ideal, nscal):
     import torch
     from athenak_amd import capi
     L, R = capi.lib(), akref.lib()
-    pk, dx, w, bcc, box = _p2c_case(dims, mhd, ideal, nscal, 43)
+    pk, dx, w, bcc, box = _p2c_case(shape, mhd, ideal, nscal, 43)
     t = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
     dxd = t(dx)
     pkd = capi.Pack.from_buffer_copy(bytes(pk))
@@ -395,6 +423,13 @@ def test_hip_prim2cons_matches_the_oracle(dims, mhd, ideal, nscal):
     capi.check(L.akmi_prim2cons(C.byref(pkd), box.ctypes.data_as(C.c_void_p), capi._p(wd),
                                 capi._p(bd) if mhd else None, capi._p(ud), None), "prim2cons")
     assert np.array_equal(u, ud.cpu().numpy())
+    # a box as wide as the block (the ghost box above is ng lanes wide): all cells but the outermost layer
+    N3, N2, N1 = w.shape[2:]
+    wide = np.array([1, N1 - 2, min(1, N2 - 1), max(N2 - 2, 0), min(1, N3 - 1), max(N3 - 2, 0)], dtype=np.int32)
+    R.akref_prim2cons(C.byref(pk), akref.ptr(wide), akref.ptr(w), akref.ptr(bcc) if mhd else None, akref.ptr(u))
+    capi.check(L.akmi_prim2cons(C.byref(pkd), wide.ctypes.data_as(C.c_void_p), capi._p(wd),
+                                capi._p(bd) if mhd else None, capi._p(ud), None), "prim2cons")
+    assert np.array_equal(u, ud.cpu().numpy()) and np.all(u[:, :, :, :, N1 - 1] == 7.0)
     bad = np.array([0, 10**6, 0, 0, 0, 0], dtype=np.int32)
     assert L.akmi_prim2cons(C.byref(pkd), bad.ctypes.data_as(C.c_void_p), capi._p(wd), None, capi._p(ud),
                             None) != 0
