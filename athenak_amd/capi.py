@@ -60,9 +60,12 @@ SYMBOLS = [
     "akmi_sim_pdf",
     "akmi_coarsen", "akmi_coarsen_default_staged", "akmi_sim_coarsen",
     "akmi_stage_last_forms", "akmi_mhd_u0_sweeps_eligible", "akmi_sim_stage_forms", "akmi_sim_counters",
+    "akmi_mhd_c2p_newdt_lean", "akmi_mhd_prims_fill", "akmi_mhd_c2p_takes_pairs",
 ]
 
-FORM_X3_U0, FORM_X12_U0, FORM_LEAN_C2P = 1, 2, 4      # AKMI_FORM_* of include/akmi.h
+FORM_X3_U0, FORM_X12_U0, FORM_LEAN_C2P, FORM_BCC_FACES = 1, 2, 4, 8      # AKMI_FORM_* of include/akmi.h
+COPY_X3_U0, COPY_X12_U0, COPY_BCC_FACES = 0x100, 0x200, 0x400            # AKMI_COPY_*: or-ed into copy_u1 of a stage call
+DROP_W03, DROP_BCC = 1, 2                                                # AKMI_DROP_* of the lean conversion
 
 # AKMI_DV_* of include/akmi.h: `which` of akmi_derived_var
 DERIVED = {"temperature": 0, "wz": 1, "w2": 2, "jz": 3, "j2": 4, "curv": 5, "k_jxb": 6, "curv_perp": 7, "bmag": 8,

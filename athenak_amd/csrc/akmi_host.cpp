@@ -770,6 +770,22 @@ MHD::MHD(MeshBlockPack *pp, ParameterInput *pin) : FluidBase(pp, pin, "mhd") {
     u0_sweeps = us == "auto" && fused && !kinematic && !multilevel && !use_fofc && !has_src && !has_visc && !has_cond &&
                 !has_resist && akmi_mhd_u0_sweeps_eligible(&pack_c, recon_method, rsolver_method) != 0;
   }
+  // <mhd>/lean_prims (read like u0_sweeps).  Eligible where u0_sweeps is: there the stage kernels and the conversion itself
+  // are the only readers of w0 / bcc0 inside a cycle.  auto: only where the conversion takes its pair kernel -- below that
+  // size it is latency-bound, not store-bound (profiles/r05_c2p_pairs.txt) -- and with the forms that won their
+  // measurement (kLeanAuto); true: every form, at any eligible size.  AKMI_LEAN_FORMS=<mask of 1: u0, 2: faces> overrides
+  // the choice of forms (A/B runs).
+  {
+    std::string ls = pin->DoesParameterExist("mhd", "lean_prims") ? pin->GetString("mhd", "lean_prims") : "auto";
+    for (char &c : ls) c = static_cast<char>(std::tolower(static_cast<unsigned char>(c)));
+    if (ls != "auto" && ls != "true" && ls != "false") AKMI_FATAL("<mhd>/lean_prims = " + ls + ": auto, true or false");
+    constexpr int kLeanAuto = 1 | 2;
+    int forms = ls == "true" ? (1 | 2) : ls == "auto" && akmi_mhd_c2p_takes_pairs(&pack_c) != 0 ? kLeanAuto : 0;
+    if (const char *e = std::getenv("AKMI_LEAN_FORMS")) { if (forms) forms = std::atoi(e) & 3; }
+    if (!u0_sweeps) forms = 0;
+    if (forms & 1) { lean_flags |= AKMI_COPY_X12_U0; lean_drop |= AKMI_DROP_W03; }
+    if (forms & 2) { lean_flags |= AKMI_COPY_BCC_FACES; lean_drop |= AKMI_DROP_BCC; }
+  }
 }
 
 void MHD::AssembleMHDTasks(std::map<std::string, std::shared_ptr<TaskList>> tl) {
@@ -997,6 +1013,7 @@ int Driver::Execute(Mesh *pm, int max_cycles) {            // driver.cpp:380-459
     };
     while ((pm->time < tlim) && (pm->ncycle < nlim || nlim < 0)) {       // pm->time: start of the cycle to enqueue, exact
       if (max_cycles >= 0 && n >= max_cycles) break;
+      last_cycle_of_call = (max_cycles >= 0 && n + 1 >= max_cycles) || (nlim >= 0 && pm->ncycle + 1 >= nlim);
       {
         // the host's dt is the one of the cycle BEFORE the one being enqueued: every eligible task takes dt from device
         // memory (stage_phase_dt / stage_fused_dt); a task that formed beta*pm->dt on the host would silently use the old
@@ -1021,6 +1038,8 @@ int Driver::Execute(Mesh *pm, int max_cycles) {            // driver.cpp:380-459
       ++n;
     }
     if (pending) collect(ra_cycle - 1);  // the last cycle: dt of the next one, and the clocks compared once more
+    last_cycle_of_call = true;
+    if (pm->pmb_pack->pmhd) pm->pmb_pack->pmhd->FillPrims();      // the loop ended by tlim: nobody knew when it was enqueued
     HIPCHK(hipStreamSynchronize(f->stream));
     if (pm->pmb_pack->phydro) pm->pmb_pack->phydro->RestoreRegisters();
     if (pm->pmb_pack->pmhd) pm->pmb_pack->pmhd->RestoreRegisters();
@@ -1028,6 +1047,7 @@ int Driver::Execute(Mesh *pm, int max_cycles) {            // driver.cpp:380-459
   }
   while ((pm->time < tlim) && (pm->ncycle < nlim || nlim < 0)) {
     if (max_cycles >= 0 && n >= max_cycles) break;
+    last_cycle_of_call = (max_cycles >= 0 && n + 1 >= max_cycles) || (nlim >= 0 && pm->ncycle + 1 >= nlim);
     if (use_graph) {
       FluidBase *f = pm->pmb_pack->phydro ? static_cast<FluidBase *>(pm->pmb_pack->phydro.get())
                                           : static_cast<FluidBase *>(pm->pmb_pack->pmhd.get());
@@ -1057,6 +1077,8 @@ int Driver::Execute(Mesh *pm, int max_cycles) {            // driver.cpp:380-459
     pm->NewTimeStep(tlim);
     ++n;
   }
+  last_cycle_of_call = true;
+  if (pm->pmb_pack->pmhd) pm->pmb_pack->pmhd->FillPrims(true);      // the loop ended by tlim
   // an odd number of out-of-place first stages leaves u0 / b0 in the buffers that used to be u1 / b1: copy
   // back once per call, so that device pointers handed out by akmi_sim_array stay valid across akmi_sim_execute
   if (pm->pmb_pack->phydro) pm->pmb_pack->phydro->RestoreRegisters();
@@ -1137,12 +1159,35 @@ int MHD::U0Copy(const Driver *d, int stage, int phases, int copy) const {
   if (!u0_sweeps || !(phases & AKMI_PHASE_SWEEPS) || stage < 1 || peers()) return copy;
   static const bool off = std::getenv("AKMI_OUT_OF_PLACE") && std::atoi(std::getenv("AKMI_OUT_OF_PLACE")) == 0;
   if (d->integrator == "rk4" || d->use_graph || off) return copy;
-  if (copy == 2) return copy | AKMI_COPY_X3_U0;
-  if (copy == 0 && stage > 1 && stage == d->nexp_stages) return 3 | AKMI_COPY_X3_U0;
+  if (copy == 2) return copy | AKMI_COPY_X3_U0 | lean_flags;
+  if (copy == 0 && stage > 1 && stage == d->nexp_stages) return 3 | AKMI_COPY_X3_U0 | lean_flags;
   return copy;
 }
-void MHD::NoteForms(int stage, int phases) {
-  if ((phases & AKMI_PHASE_SWEEPS) && stage >= 1 && stage <= 4) stage_forms[stage - 1] = akmi_stage_last_forms();
+// stale: what of w0 / bcc0 a lean conversion had left unwritten when the sweeps ran
+void MHD::NoteForms(int stage, int phases, int stale) {
+  if ((phases & AKMI_PHASE_SWEEPS) && stage >= 1 && stage <= 4)
+    stage_forms[stage - 1] = akmi_stage_last_forms() | (stale ? AKMI_FORM_LEAN_C2P : 0);
+}
+// What the conversion that ends `stage` may leave unwritten: the arrays the NEXT sweeps do not read, when those sweeps are
+// certain to come within this akmi_sim_execute call -- the next stage of the cycle, or the first stage of the next cycle
+// unless this cycle is known to be the last of the call.  (A call that ends by tlim finds that out too late: Execute fills.)
+int MHD::LeanDrop(const Driver *d, int stage) const {
+  if (!lean_drop || stage < 1) return 0;
+  const int next = stage < d->nexp_stages ? stage + 1 : 1;
+  if (next == 1 && d->last_cycle_of_call) return 0;
+  const int ph = AKMI_PHASE_SWEEPS | AKMI_PHASE_EMF_CT;
+  return (U0Copy(d, next, ph, CopyFlag(d, next, ph)) & AKMI_COPY_X3_U0) ? lean_drop : 0;
+}
+void MHD::FillPrims(bool sync) {
+  if (!prims_stale) return;
+  AKCHK(akmi_mhd_prims_fill(&pack_c, u0.p, b0.x1f.p, b0.x2f.p, b0.x3f.p, w0.p, bcc0.p, prims_stale, stream));
+  prims_stale = 0;
+  if (sync) HIPCHK(hipStreamSynchronize(stream));
+}
+// a stage call reads all of w0 / bcc0 except what its form flags take from u0 and the faces
+static int FormsCover(int copy_arg) {
+  return ((copy_arg & AKMI_COPY_X3_U0) && (copy_arg & AKMI_COPY_X12_U0) ? AKMI_DROP_W03 : 0) |
+         ((copy_arg & AKMI_COPY_BCC_FACES) ? AKMI_DROP_BCC : 0);
 }
 
 void MHD::RestoreRegisters() {
@@ -1411,6 +1456,8 @@ TaskStatus MHD::RKUpdate(Driver *d, int stage) {           // mhd_update.cpp:24-
     int do_dt = (stage == d->nexp_stages);
     const int copy_arg = U0Copy(d, stage, AKMI_PHASE_ALL, CopyFlag(d, stage, AKMI_PHASE_ALL));
     const int copy = copy_arg & AKMI_COPY_MASK;
+    if (prims_stale & ~FormsCover(copy_arg)) FillPrims();
+    const int stale = prims_stale;
     d->ProfMark(stream);
     if (dt_dev)
       AKCHK(akmi_mhd_stage_fused_dt(&pack_c, recon_method, rsolver_method, d->gam0[stage - 1],
@@ -1423,7 +1470,7 @@ TaskStatus MHD::RKUpdate(Driver *d, int stage) {           // mhd_update.cpp:24-
                                b0.x1f.p, b0.x2f.p, b0.x3f.p, b1.x1f.p, b1.x2f.p, b1.x3f.p, do_dt,
                                counters.p, dt3.p, ws.p, stream));
     d->ProfMark(stream);
-    NoteForms(stage, AKMI_PHASE_ALL);
+    NoteForms(stage, AKMI_PHASE_ALL, stale);
     if (copy == 2) {
       SwapArr(u0, u1); u_swapped = !u_swapped;
       SwapArr(b0.x1f, b1.x1f); SwapArr(b0.x2f, b1.x2f); SwapArr(b0.x3f, b1.x3f); b_swapped = !b_swapped;
@@ -1448,6 +1495,8 @@ void MHD::StagePhase(Driver *d, int stage, int phases) {
   const int do_dt = (stage == d->nexp_stages);
   const int copy_arg = U0Copy(d, stage, phases, CopyFlag(d, stage, phases));
   const int copy = copy_arg & AKMI_COPY_MASK;
+  if (prims_stale & ~FormsCover(copy_arg)) FillPrims();
+  const int stale = prims_stale;
   d->ProfMark(stream);
   if (dt_dev && stage >= 1)
     AKCHK(akmi_mhd_stage_phase_dt(&pack_c, recon_method, rsolver_method, g0, g1, d->beta[stage - 1], dt_dev, copy_arg, w0.p,
@@ -1458,7 +1507,7 @@ void MHD::StagePhase(Driver *d, int stage, int phases) {
                              bcc0.p, u0.p, u1.p, b0.x1f.p, b0.x2f.p, b0.x3f.p, b1.x1f.p, b1.x2f.p,
                              b1.x3f.p, do_dt, counters.p, dt3.p, phases, ws.p, stream));
   d->ProfMark(stream);
-  NoteForms(stage, phases);
+  NoteForms(stage, phases, stale);
   if (copy == 3 && (phases & AKMI_PHASE_SWEEPS)) { SwapArr(u0, u1); u_swapped = !u_swapped; }
   if (copy == 2) {
     if (phases & AKMI_PHASE_SWEEPS) { SwapArr(u0, u1); u_swapped = !u_swapped; }
@@ -1648,13 +1697,16 @@ TaskStatus MHD::ConToPrim(Driver *d, int stage) {
             n3 = ind.nx3 > 1 ? ind.nx3 + 2*ind.ng : 1;
   if (fused && interior_done_) {
     interior_done_ = false;
+    FillPrims();                       // (this path never converts lean: nothing to do unless the path changed mid-run)
     AKCHK(akmi_mhd_c2p_shell(&pack_c, u0.p, b0.x1f.p, b0.x2f.p, b0.x3f.p, w0.p, bcc0.p, counters.p, stream));
   } else if (fused) {
     int do_dt = (stage == d->nexp_stages);
+    const int drop = LeanDrop(d, stage);
     d->ProfMark(stream);
-    AKCHK(akmi_mhd_c2p_newdt(&pack_c, u0.p, b0.x1f.p, b0.x2f.p, b0.x3f.p, w0.p, bcc0.p,
-                             do_dt ? ((dt3_reset_ || d->ra_active) ? 2 : 1) : 0,
-                             counters.p, dt3.p, stream));
+    AKCHK(akmi_mhd_c2p_newdt_lean(&pack_c, u0.p, b0.x1f.p, b0.x2f.p, b0.x3f.p, w0.p, bcc0.p,
+                                  do_dt ? ((dt3_reset_ || d->ra_active) ? 2 : 1) : 0,
+                                  counters.p, dt3.p, drop, stream));
+    prims_stale = drop;                // every array that is not dropped is written in every cell
     dt3_reset_ = false;
     d->ProfMark(stream);
     dt_ready_ = do_dt;
@@ -1672,7 +1724,7 @@ TaskStatus MHD::ConToPrim(Driver *d, int stage) {
 TaskStatus MHD::NewTimeStep(Driver *d, int stage) {        // mhd_newdt.cpp:31-174
   if (stage != d->nexp_stages) return TaskStatus::complete;
   if (kinematic) AKCHK(akmi_kinematic_newdt(&pack_c, w0.p, dt3.p, stream));      // mhd_newdt.cpp:56-73
-  else if (!dt_ready_) AKCHK(akmi_mhd_newdt(&pack_c, w0.p, bcc0.p, dt3.p, stream));
+  else if (!dt_ready_) { FillPrims(); AKCHK(akmi_mhd_newdt(&pack_c, w0.p, bcc0.p, dt3.p, stream)); }
   dt_ready_ = false;
   if (d->capturing) return TaskStatus::complete;   // the Driver reads dt3 after the graph launch
   if (d->ra_active) { d->EnqueueMeshNewDt(this); return TaskStatus::complete; }

@@ -512,7 +512,15 @@ class MHD : public FluidBase {      // mhd.hpp:93-199
   // does not write the array it reads (U0Copy, akmi_host.cpp); false keeps every stage in the form it had before
   bool u0_sweeps = false;
   int U0Copy(const Driver *d, int stage, int phases, int copy) const;
-  void NoteForms(int stage, int phases);
+  void NoteForms(int stage, int phases, int stale);
+  // <mhd>/lean_prims = auto | true | false.  lean_flags: what U0Copy adds beside AKMI_COPY_X3_U0 (AKMI_COPY_X12_U0,
+  // AKMI_COPY_BCC_FACES); lean_drop: the arrays (AKMI_DROP_*) a stage with those flags does not read, which ConToPrim
+  // leaves unwritten when the next sweeps are certain to run in the same akmi_sim_execute call and to take the flags
+  // (LeanDrop).  prims_stale: the arrays that are unwritten right now; FillPrims writes them (akmi_mhd_prims_fill), before
+  // anything but such a stage reads w0 / bcc0 and before akmi_sim_execute returns.
+  int lean_flags = 0, lean_drop = 0, prims_stale = 0;
+  int LeanDrop(const Driver *d, int stage) const;
+  void FillPrims(bool sync = false);
   TaskStatus SaveMHDState(Driver *d, int stage) { return TaskStatus::complete; }
   TaskStatus InitRecv(Driver *d, int stage) { return TaskStatus::complete; }
   TaskStatus CopyCons(Driver *d, int stage);
@@ -550,6 +558,7 @@ class Driver {          // driver.cpp
   std::string integrator;
   Real tlim;
   int nlim, nexp_stages;
+  bool last_cycle_of_call = true;    // the cycle being enqueued is known to be the last of this Execute (max_cycles, nlim)
   Real gam0[4], gam1[4], beta[4], delta[4];
   std::int64_t nmb_updated_ = 0;
   // One cycle (all stages) captured into a hipGraph and replayed: on small packs a cycle is a chain of

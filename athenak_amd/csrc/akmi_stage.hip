@@ -128,6 +128,7 @@ struct SweepArgs {
   double *ecc1, *ecc2, *ecc3;     // cell-centred EMFs (x1 sweep only)
   int il, iu, jl, ju, kl, ku;     // face ranges of this sweep
   int f3, f2, f1;
+  const double *bt1 = nullptr, *bt2 = nullptr;     // x3 march in its face form: b0.x1f and b0.x2f
 };
 
 // plain sweep (not the last direction): thread per face.  ECC: also emit e_cc for the right
@@ -518,12 +519,16 @@ static int march_len(long col_blocks, int ncells, int nmb, int lmax, int wgs_per
 // face finishes are the ones the window loaded two steps earlier (momenta parked in registers), so the update fetches
 // u0[4] alone: four streams fewer per cell.  NOT for a stage in place: the priming loads of a chunk read the last two
 // cells of the chunk below, which such a stage has overwritten in u0 by then.
-template <int DIR, int RECON, bool MHD, int MODE, bool USEACC, int RS, bool P2, bool U0F = false>
+// BF (on top of U0F, AKMI_COPY_BCC_FACES): slots 5 and 6 (Bx, By here) are bcc_from_faces of b0.x1f at i, i+1 and b0.x2f at
+// j, j+1 instead of bcc0[0..1] -- the priming loads and the one-step-ahead prefetch alike; the prefetched faces stay as
+// loaded until the step that consumes them.
+template <int DIR, int RECON, bool MHD, int MODE, bool USEACC, int RS, bool P2, bool U0F = false, bool BF = false>
 __device__ __forceinline__ void sweep_update_body(const Geo &g, const FaceEos &eos, const SweepArgs &a,
                                                   const UpdArgs &u, int ml, double *sm) {
   static_assert(DIR == 1 || DIR == 2, "marching kernel is for the x2/x3 sweeps");
   static_assert(!U0F || (DIR == 2 && MHD && RECON == 1 && MODE == 0 && USEACC && !rs_iso<RS>() && AKMI_PREFETCH_W &&
                          AKMI_PREFETCH_UPD), "u0 form: x3 march of MHD PLM with the update");
+  static_assert(!BF || U0F, "face form: on top of the u0 form");
   constexpr bool STORE = MODE == 2;                                  // all flux components of every face go to memory
   int i, j, k, m, s0;
   bool lane_ok;
@@ -600,6 +605,28 @@ __device__ __forceinline__ void sweep_update_body(const Geo &g, const FaceEos &e
          : n == 4 ? wb + 4*cs : n == 5 ? bb + iby*cs : bb + ibz*cs;
   };
   double mprev[3] = {0.0, 0.0, 0.0}, mcur[3] = {0.0, 0.0, 0.0};     // U0F: momenta (sweep order) of cells s-1 and s
+  // BF: x1 faces (N3, N2, N1+1) i, i+1 and x2 faces (N3, N2+1, N1) j, j+1 of cell s, advancing with the march
+  const double *bt1m = BF ? a.bt1 + (size_t)m*g.N3*g.N2*(g.N1 + 1) : nullptr;
+  const double *bt2m = BF ? a.bt2 + (size_t)m*g.N3*(g.N2 + 1)*g.N1 : nullptr;
+  unsigned ox = (((unsigned)k*(unsigned)g.N2 + (unsigned)j)*(unsigned)(g.N1 + 1) + (unsigned)i)*8u;
+  unsigned oy = (((unsigned)k*(unsigned)(g.N2 + 1) + (unsigned)j)*(unsigned)g.N1 + (unsigned)i)*8u;
+  const long sx = (long)g.N2*(g.N1 + 1), sy = (long)(g.N2 + 1)*g.N1;          // their strides along k
+  auto ldf = [&](long r, double (&f)[4]) {              // the four faces of the cell r steps beyond cell s, as loaded
+    f[0] = ldu(bt1m + r*sx, ox); f[1] = ldu(bt1m + r*sx + 1, ox);
+    f[2] = ldu(bt2m + r*sy, oy); f[3] = ldu(bt2m + r*sy + g.N1, oy);
+  };
+  if constexpr (BF) {
+    double fa[4], fb[4], fc[4];
+    ldf(-2, fa); ldf(-1, fb); ldf(0, fc);
+#pragma unroll
+    for (int n = 0; n < 2; ++n) {
+      const double qa = bcc_from_faces(fa[2*n], fa[2*n + 1]), qb = bcc_from_faces(fb[2*n], fb[2*n + 1]),
+                   qc = bcc_from_faces(fc[2*n], fc[2*n + 1]);
+      double pl, dummy;
+      plm(qa, qb, qc, pl, dummy);
+      W_(5 + n, 0) = qb; W_(5 + n, 1) = qc; PL_(5 + n) = pl;
+    }
+  }
   // prime the window: left state of the first face comes from cell s0-1
   if constexpr (U0F) {
     double qd[3], qm[3][3], qv[3][3];
@@ -628,6 +655,7 @@ __device__ __forceinline__ void sweep_update_body(const Geo &g, const FaceEos &e
   for (int n = 0; n < NV; ++n) {
     if (ISO && n == 4) continue;
     if (U0F && n < 4) continue;
+    if (BF && n >= 5) continue;
     const double *q = base(n);
     double pl, dummy;
     if constexpr (RECON == 1) {
@@ -663,9 +691,11 @@ __device__ __forceinline__ void sweep_update_body(const Geo &g, const FaceEos &e
   double nx[NV];                         // PW: cells s+1 of the coming step, loaded one step ahead
   // (the face field of the next face prefetched as well: measured, the x3 march loses 865 -> 942 us,
   //  profiles/r03_ab2.txt; requested before the update operands: no effect, profiles/r03_ab4.txt -- both removed)
+  double nf[4] = {0.0, 0.0, 0.0, 0.0};   // BF: the faces behind nx[5], nx[6]
   if constexpr (PW) {
 #pragma unroll
-    for (int n = 0; n < NV; ++n) nx[n] = (ISO && n == 4) ? 0.0 : ldu(base(n) + LA*st, off);
+    for (int n = 0; n < NV; ++n) nx[n] = ((ISO && n == 4) || (BF && n >= 5)) ? 0.0 : ldu(base(n) + LA*st, off);
+    if constexpr (BF) ldf(LA, nf);
   }
   for (int t = 0; t <= ml; ++t) {
     const int s = s0 + t;
@@ -675,7 +705,12 @@ __device__ __forceinline__ void sweep_update_body(const Geo &g, const FaceEos &e
     if constexpr (PW) {
       const bool more = (t < ml) && (s < shi);           // a next step exists: its cell s+2 is inside the array
 #pragma unroll
-      for (int n = 0; n < NV; ++n) nx2[n] = (more && !(ISO && n == 4)) ? ldu(base(n) + (LA + 1)*st, off) : 0.0;
+      for (int n = 0; n < NV; ++n) nx2[n] = (more && !(ISO && n == 4) && !(BF && n >= 5)) ? ldu(base(n) + (LA + 1)*st, off) : 0.0;
+    }
+    double nf2[4] = {0.0, 0.0, 0.0, 0.0};
+    if constexpr (BF) {
+      if ((t < ml) && (s < shi)) ldf(LA + 1, nf2);
+      nx[5] = bcc_from_faces(nf[0], nf[1]); nx[6] = bcc_from_faces(nf[2], nf[3]);
     }
     double L[NV], R[NV];
     double vnx[3] = {0.0, 0.0, 0.0}, dsc = 0.0;          // U0F: velocities of cell s+1, density of the cell this face finishes
@@ -716,6 +751,7 @@ __device__ __forceinline__ void sweep_update_body(const Geo &g, const FaceEos &e
     const unsigned oc = off;                            // cell s == face s of the cell-shaped EMF arrays
     const unsigned ocm = off - st8;                     // cell s-1, the one this face finishes
     off += st8;
+    if constexpr (BF) { ox += (unsigned)sx*8u; oy += (unsigned)sy*8u; }
     // x3 march: fetch the update operands of the cell this face finishes BEFORE the Riemann solve,
     // so that their latency is covered by ~1000 VALU instructions instead of following them
     // (this kernel moves the most bytes of the stage and runs at 3 waves/SIMD)
@@ -865,6 +901,7 @@ __device__ __forceinline__ void sweep_update_body(const Geo &g, const FaceEos &e
     if constexpr (PW) {
 #pragma unroll
       for (int n = 0; n < NV; ++n) nx[n] = nx2[n];
+      if constexpr (BF) { nf[0] = nf2[0]; nf[1] = nf2[1]; nf[2] = nf2[2]; nf[3] = nf2[3]; }
     }
   }
 #undef W_
@@ -875,14 +912,14 @@ __device__ __forceinline__ void sweep_update_body(const Geo &g, const FaceEos &e
 // the kernel proper: when the cell sizes of the block are powers of two, x/dx == x*(1/dx) bit for
 // bit (both are the correctly rounded value of the same real number, and 1/dx is exact), so the
 // divisions by dx become products; decided per block, two copies of the loop
-template <int DIR, int RECON, bool MHD, int MODE, bool USEACC, int RS, bool U0F = false>
+template <int DIR, int RECON, bool MHD, int MODE, bool USEACC, int RS, bool U0F = false, bool BF = false>
 __global__ void __launch_bounds__(SX*SY, (RECON >= 2 ? 2 : (DIR == 2 ? AKMI_X3_WAVES : AKMI_X2_WAVES)))
 k_sweep_update(Geo g, FaceEos eos, SweepArgs a, UpdArgs u, int ml) {
   constexpr int NV = MHD ? 7 : 5;
   __shared__ double sm[(((RECON >= 2) && AKMI_PPM_WREG ? 0 : NV*RollCfg<RECON>::NW) + NV + 5)*SX*SY];
   const int m = blockIdx.z;
   constexpr bool TRY = AKMI_POW2DX != 0;      // power-of-two cell sizes: x/dx by v_ldexp_f64 (wave-uniform run-time choice)
-  sweep_update_body<DIR, RECON, MHD, MODE, USEACC, RS, TRY, U0F>(g, eos, a, u, ml, sm);
+  sweep_update_body<DIR, RECON, MHD, MODE, USEACC, RS, TRY, U0F, BF>(g, eos, a, u, ml, sm);
 }
 
 
@@ -1294,7 +1331,9 @@ __device__ __forceinline__ void c2p_iso_cell(const Geo &g, const Eos &eos, doubl
   for (int n = 4; n < g.nvar; ++n) w0[c + n*cs] = u0[c + n*cs]/ud;
 }
 
-template <bool MHD>
+// DROP (mask of AKMI_DROP_*, ideal gas only): the lean conversion -- w0[0..3] and / or bcc0 are computed as always but not
+// stored; a caller whose next sweeps take them from u0 and the faces (AKMI_COPY_X12_U0 / AKMI_COPY_BCC_FACES) asks for it
+template <bool MHD, int DROP = 0>
 __global__ void __launch_bounds__(SX*SY)
 k_c2p_newdt(Geo g, Eos eos, double *__restrict__ u0, const double *__restrict__ bx1f,
             const double *__restrict__ bx2f, const double *__restrict__ bx3f,
@@ -1318,8 +1357,10 @@ k_c2p_newdt(Geo g, Eos eos, double *__restrict__ u0, const double *__restrict__ 
                            bx2f[ix4(g.N3, g.N2 + 1, g.N1, m, k, j + 1, i)]);
       ubz = bcc_from_faces(bx3f[ix4(g.N3 + 1, g.N2, g.N1, m, k, j, i)],
                            bx3f[ix4(g.N3 + 1, g.N2, g.N1, m, k + 1, j, i)]);
-      const size_t b = ix5(3, g.N3, g.N2, g.N1, m, 0, k, j, i);
-      bcc0[b] = ubx; bcc0[b + cs] = uby; bcc0[b + 2*cs] = ubz;
+      if constexpr (!(DROP & AKMI_DROP_BCC)) {
+        const size_t b = ix5(3, g.N3, g.N2, g.N1, m, 0, k, j, i);
+        bcc0[b] = ubx; bcc0[b + cs] = uby; bcc0[b + 2*cs] = ubz;
+      }
     }
     const bool scan = do_newdt && i >= g.is && i <= g.ie && j >= g.js && j <= g.je && k >= g.ks && k <= g.ke;
     if (!eos.is_ideal) {
@@ -1344,7 +1385,8 @@ k_c2p_newdt(Geo g, Eos eos, double *__restrict__ u0, const double *__restrict__ 
     if (dfl) { u0[c] = ud; atomicAdd(&counters[0], 1); }
     if (efl) { u0[c + 4*cs] = ue; atomicAdd(&counters[1], 1); }
     if (tfl) { u0[c + 4*cs] = ue; atomicAdd(&counters[2], 1); }
-    w0[c] = wd; w0[c + cs] = wvx; w0[c + 2*cs] = wvy; w0[c + 3*cs] = wvz; w0[c + 4*cs] = we;
+    if constexpr (!(DROP & AKMI_DROP_W03)) { w0[c] = wd; w0[c + cs] = wvx; w0[c + 2*cs] = wvy; w0[c + 3*cs] = wvz; }
+    w0[c + 4*cs] = we;
     for (int n = 5; n < g.nvar; ++n) {        // scalars with their floor, ideal_hyd.cpp:94-101
       double us = u0[c + n*cs];
       if (us < 0.0) { us = 0.0; u0[c + n*cs] = 0.0; }
@@ -1399,7 +1441,7 @@ __device__ __forceinline__ void st2nt(double *p, double a, double b) {
 
 // (MHD: 86 VGPRs, five waves per SIMD; held to 80 / 64 registers it spills and runs at 383 / 605 us against 364-389,
 //  profiles/r05_c2p_pairs.txt)
-template <bool MHD>
+template <bool MHD, int DROP = 0>
 __global__ void __launch_bounds__(SX*SY)
 k_c2p_newdt2(Geo g, Eos eos, double *__restrict__ u0, const double *__restrict__ bx1f,
              const double *__restrict__ bx2f, const double *__restrict__ bx3f,
@@ -1428,8 +1470,10 @@ k_c2p_newdt2(Geo g, Eos eos, double *__restrict__ u0, const double *__restrict__
       uby[0] = bcc_from_faces(y0.x, y1.x); uby[1] = bcc_from_faces(y0.y, y1.y);
       const d2_t z0 = ld2(bx3f + ix4(g.N3 + 1, g.N2, g.N1, m, k, j, i)), z1 = ld2(bx3f + ix4(g.N3 + 1, g.N2, g.N1, m, k + 1, j, i));
       ubz[0] = bcc_from_faces(z0.x, z1.x); ubz[1] = bcc_from_faces(z0.y, z1.y);
-      const size_t b = ix5(3, g.N3, g.N2, g.N1, m, 0, k, j, i);
-      st2nt(bcc0 + b, ubx[0], ubx[1]); st2nt(bcc0 + b + cs, uby[0], uby[1]); st2nt(bcc0 + b + 2*cs, ubz[0], ubz[1]);
+      if constexpr (!(DROP & AKMI_DROP_BCC)) {
+        const size_t b = ix5(3, g.N3, g.N2, g.N1, m, 0, k, j, i);
+        st2nt(bcc0 + b, ubx[0], ubx[1]); st2nt(bcc0 + b + cs, uby[0], uby[1]); st2nt(bcc0 + b + 2*cs, ubz[0], ubz[1]);
+      }
     }
     const d2_t vd = ld2nt(u0 + c), vx = ld2nt(u0 + c + cs), vy = ld2nt(u0 + c + 2*cs), vz = ld2nt(u0 + c + 3*cs),
                ve = ld2nt(u0 + c + 4*cs);
@@ -1462,8 +1506,11 @@ k_c2p_newdt2(Geo g, Eos eos, double *__restrict__ u0, const double *__restrict__
         }
       }
     }
-    st2nt(w0 + c, wd[0], wd[1]); st2nt(w0 + c + cs, wvx[0], wvx[1]); st2nt(w0 + c + 2*cs, wvy[0], wvy[1]);
-    st2nt(w0 + c + 3*cs, wvz[0], wvz[1]); st2nt(w0 + c + 4*cs, we[0], we[1]);
+    if constexpr (!(DROP & AKMI_DROP_W03)) {
+      st2nt(w0 + c, wd[0], wd[1]); st2nt(w0 + c + cs, wvx[0], wvx[1]); st2nt(w0 + c + 2*cs, wvy[0], wvy[1]);
+      st2nt(w0 + c + 3*cs, wvz[0], wvz[1]);
+    }
+    st2nt(w0 + c + 4*cs, we[0], we[1]);
   }
   if (!do_newdt) return;        // uniform across the grid
   mv1 = wave_max(mv1); mv2 = wave_max(mv2); mv3 = wave_max(mv3);
@@ -1834,7 +1881,7 @@ static int launch_sweep(const Geo &g, const Scheme &sc, const SweepArgs &a, hipS
 
 template <int DIR, bool MHD, int MODE = 0, bool USEACC = false>
 static int launch_sweep_update(const Geo &g, const Scheme &sc, const SweepArgs &a,
-                               const UpdArgs &u, hipStream_t st, bool u0_form = false) {
+                               const UpdArgs &u, hipStream_t st, bool u0_form = false, bool face_form = false) {
   int rc;
   if constexpr (DIR == 0) {
     dim3 grid(cdiv(a.iu - a.il + 1, TX - 1), 1, g.nmb), block(TX, 1);
@@ -1867,7 +1914,9 @@ static int launch_sweep_update(const Geo &g, const Scheme &sc, const SweepArgs &
       // the x3 march in its u0 form: MHD, PLM, HLLD, ideal gas (what stage_update asks it for)
       if constexpr (MHD && DIR == 2 && MODE == 0 && USEACC) {
         if (sc.iso || sc.recon != 1 || sc.rsolver != AKMI_RS_HLLD) { set_error("x3 march, u0 form: PLM + HLLD, ideal gas"); return AKMI_FAIL; }
-        k_sweep_update<2, 1, true, 0, true, 3, true><<<grid, block, 0, st>>>(g, sc.eos, a, u, ml);
+        if (face_form && (!a.bt1 || !a.bt2)) { set_error("x3 march, face form: needs the x1 and x2 faces"); return AKMI_FAIL; }
+        if (face_form) k_sweep_update<2, 1, true, 0, true, 3, true, true><<<grid, block, 0, st>>>(g, sc.eos, a, u, ml);
+        else k_sweep_update<2, 1, true, 0, true, 3, true><<<grid, block, 0, st>>>(g, sc.eos, a, u, ml);
         rc = AKMI_COMPLETE;
       } else {
         set_error("sweep_update: the u0 form exists for the x3 march of MHD only");
@@ -1906,9 +1955,16 @@ static int launch_sweep_update(const Geo &g, const Scheme &sc, const SweepArgs &
 #ifndef AKMI_X12S_EO2
 #define AKMI_X12S_EO2 1
 #endif
-template <int RS>
+// UC (AKMI_COPY_X12_U0): the window takes density and momentum from u0 and forms the velocities with vel_from_cons where
+// the loaded row is consumed (priming, x2 part of the step) -- what ConsToPrim stored in w0[1..3], bit for bit.  u0 is
+// still the state of the start of the stage: the x3 march writes it after this kernel, in stream order.
+// BF (AKMI_COPY_BCC_FACES): the cell-centred field through bcc_from_faces -- Bz of row s+1 from the x3 faces k and k+1 (the
+// one extra stream), Bx of row s+1 from the x1 faces i and i+1 of that row (i+1: the lane above; lanes 0 and 63 and the
+// last cell of a row of the array never use their own Bx), By of row s-1 from the x2 faces s-1 (carried) and s.
+// All face indices lie inside the face-shaped arrays for k in [ks-1, ke+1] and rows in [js-2, je+2].
+template <int RS, bool UC = false, bool BF = false>
 __global__ void __launch_bounds__(SX*SY, AKMI_X12S_WAVES)
-k_sweep12s(Geo g, FaceEos eos, SweepArgs a1, SweepArgs a2, UpdArgs u, int ml) {
+k_sweep12s(Geo g, FaceEos eos, SweepArgs a1, SweepArgs a2, UpdArgs u, int ml, const double *__restrict__ bx3f) {
   constexpr int NV = 7, NW = 2, NT = SX*SY;
   constexpr int CPW = SX - 4;                              // cells per wave
   __shared__ double sm[(NV*NW + NV + 5)*SX*SY];
@@ -1948,10 +2004,61 @@ k_sweep12s(Geo g, FaceEos eos, SweepArgs a1, SweepArgs a2, UpdArgs u, int ml) {
     return n == 0 ? wb : n == 1 ? wb + 2*cs : n == 2 ? wb + 3*cs : n == 3 ? wb + cs
          : n == 4 ? wb + 4*cs : n == 5 ? bb + 2*cs : bb;
   };
+  // UC: the conserved variables behind window slots 0-3 (d, m2, m3, m1)
+  const double *ub = u.u0 + (size_t)m*g.nvar*cs;
+  auto cbase2 = [&](int n) -> const double * { return n == 0 ? ub : n == 1 ? ub + 2*cs : n == 2 ? ub + 3*cs : ub + cs; };
   unsigned off = (((unsigned)k*(unsigned)g.N2 + (unsigned)s0)*(unsigned)g.N1 + (unsigned)i)*8u;    // cell (k, s, i)
   const unsigned st8 = (unsigned)g.N1*8u;
+  // face-shaped arrays: x2 faces (f3, f2, f1) = (N3, N2+1, N1), x1 faces (N3, N2, N1+1), x3 faces (N3+1, N2, N1)
+  const size_t fs2 = (size_t)a2.f3*a2.f2*a2.f1, fs1 = (size_t)a1.f3*a1.f2*a1.f1;
+  unsigned foff2 = (((unsigned)k*(unsigned)a2.f2 + (unsigned)s0)*(unsigned)a2.f1 + (unsigned)i)*8u;   // x2 face s
+  const unsigned fst28 = (unsigned)a2.f1*8u;
+  unsigned foff1 = (((unsigned)k*(unsigned)a1.f2 + (unsigned)(s0 - 1))*(unsigned)a1.f1 + (unsigned)i)*8u;   // x1 face (k, s-1, i)
+  const unsigned fst18 = (unsigned)a1.f1*8u;
+  const double *bx2m = a2.bxf + (size_t)m*fs2, *bx1m = a1.bxf + (size_t)m*fs1;
+  // x3 face (k, s, i) sits at the byte offset of cell (k, s, i); face k+1 one plane further
+  const double *bx3m = BF ? bx3f + (size_t)m*(size_t)(g.N3 + 1)*g.N2*g.N1 : nullptr;
+  const long pst = (long)g.N2*g.N1;
+  if constexpr (UC) {
+    double qd[3], qm[3][3], qv[3][3];                 // rows s0-2, s0-1, s0; momenta / velocities in window order 2, 3, 1
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      qd[c] = ldu(cbase2(0) - (2 - c)*st, off);
+#pragma unroll
+      for (int n = 0; n < 3; ++n) qm[n][c] = ldu(cbase2(1 + n) - (2 - c)*st, off);
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      double di;
+      vel_from_cons(qd[c], qm[2][c], qm[0][c], qm[1][c], di, qv[2][c], qv[0][c], qv[1][c]);
+    }
+    double pl, dummy;
+    plm(qd[0], qd[1], qd[2], pl, dummy);
+    W_(0, 0) = qd[1]; W_(0, 1) = qd[2]; PL_(0) = pl;
+#pragma unroll
+    for (int n = 0; n < 3; ++n) {
+      plm(qv[n][0], qv[n][1], qv[n][2], pl, dummy);
+      W_(1 + n, 0) = qv[n][1]; W_(1 + n, 1) = qv[n][2]; PL_(1 + n) = pl;
+    }
+  }
+  if constexpr (BF) {
+    double qz[3], qx[3];                              // Bz and Bx of rows s0-2, s0-1, s0
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const long r = -(long)(2 - c)*st;
+      qz[c] = bcc_from_faces(ldu(bx3m + r, off), ldu(bx3m + r + pst, off));
+      const double f = ldu(bx1m + (long)(c - 1)*a1.f1, foff1);
+      qx[c] = bcc_from_faces(f, AKMI_LANE_ABOVE(f));
+    }
+    double pl, dummy;
+    plm(qz[0], qz[1], qz[2], pl, dummy);
+    W_(5, 0) = qz[1]; W_(5, 1) = qz[2]; PL_(5) = pl;
+    plm(qx[0], qx[1], qx[2], pl, dummy);
+    W_(6, 0) = qx[1]; W_(6, 1) = qx[2]; PL_(6) = pl;
+  }
 #pragma unroll
   for (int n = 0; n < NV; ++n) {
+    if ((UC && n < 4) || (BF && n >= 5)) continue;
     const double *q = base2(n);
     double pl, dummy;
     const double qa = ldu(q - 2*st, off), qb = ldu(q - st, off), qc = ldu(q, off);
@@ -1959,17 +2066,11 @@ k_sweep12s(Geo g, FaceEos eos, SweepArgs a1, SweepArgs a2, UpdArgs u, int ml) {
     W_(n, 0) = qb; W_(n, 1) = qc;
     PL_(n) = pl;
   }
-  // face-shaped arrays: x2 faces (f3, f2, f1) = (N3, N2+1, N1), x1 faces (N3, N2, N1+1)
-  const size_t fs2 = (size_t)a2.f3*a2.f2*a2.f1, fs1 = (size_t)a1.f3*a1.f2*a1.f1;
-  unsigned foff2 = (((unsigned)k*(unsigned)a2.f2 + (unsigned)s0)*(unsigned)a2.f1 + (unsigned)i)*8u;   // x2 face s
-  const unsigned fst28 = (unsigned)a2.f1*8u;
-  unsigned foff1 = (((unsigned)k*(unsigned)a1.f2 + (unsigned)(s0 - 1))*(unsigned)a1.f1 + (unsigned)i)*8u;   // x1 face (k, s-1, i)
-  const unsigned fst18 = (unsigned)a1.f1*8u;
-  const double *bx2m = a2.bxf + (size_t)m*fs2, *bx1m = a1.bxf + (size_t)m*fs1;
   double *mf2 = a2.flx + (size_t)m*g.nvar*fs2, *mf1 = a1.flx + (size_t)m*g.nvar*fs1;
   const double *bym = bb + cs;                                                                   // cell-centred By
   const size_t mb = (size_t)m*g.nvar*cs;
-  double by_n = ldu(bym, off - st8), bx1_n = ldu(bx1m, foff1);
+  double by_n = BF ? 0.0 : ldu(bym, off - st8), bx1_n = ldu(bx1m, foff1);
+  double bx2_p = BF ? ldu(bx2m - a2.f1, foff2) : 0.0;            // BF: x2 face s-1
   for (int t = 0;; ++t) {
     const int s = s0 + t;
     if (s > shi + 1) break;                   // the last chunk ends with the x1 faces of row ju(x1)
@@ -1982,16 +2083,27 @@ k_sweep12s(Geo g, FaceEos eos, SweepArgs a1, SweepArgs a2, UpdArgs u, int ml) {
     // the seven cell loads sat in its own scalar branch followed by s_waitcnt vmcnt(0): eight serialised
     // memory round trips per step, profiles/r03_isa_audit.txt.)  Beyond the last face the address is the
     // row the window already holds, i.e. the value `w1` the old form substituted.
-    const double by_c = by_n, bx1 = bx1_n;
-    by_n = ldu(bym, off);
+    // BF: the x2 face s is loaded beyond the last face as well (face je+2 exists): By of the last row needs it
+    const double bx1 = bx1_n;
+    double by_c = by_n;
+    if constexpr (!BF) by_n = ldu(bym, off);
     bx1_n = ldu(bx1m + a1.f1, foff1);
     double qn[NV];
+    double zlo = 0.0, zhi = 0.0, x1n = 0.0;                 // BF: x3 faces k, k+1 and x1 face i of the row qn holds
     {
       const long stq = do_x2 ? st : 0;
 #pragma unroll
-      for (int n = 0; n < NV; ++n) qn[n] = ldu(base2(n) + stq, off);
+      for (int n = 0; n < NV; ++n) {
+        if (BF && n >= 5) continue;
+        qn[n] = ldu(((UC && n < 4) ? cbase2(n) : base2(n)) + stq, off);
+      }
+      if constexpr (BF) {
+        zlo = ldu(bx3m + stq, off); zhi = ldu(bx3m + stq + pst, off);
+        x1n = ldu(bx1m + (do_x2 ? 2 : 1)*(long)a1.f1, foff1);
+      }
     }
-    const double bx2 = ldu(bx2m, do_x2 ? foff2 : foff2 - fst28);
+    const double bx2 = ldu(bx2m, (BF || do_x2) ? foff2 : foff2 - fst28);
+    if constexpr (BF) { by_c = bcc_from_faces(bx2_p, bx2); bx2_p = bx2; }
     // ---- x1 face on the low side of cell (k, jr, i): the cell is W_(.,0) of the march
     double f1d, f1x, f1y, f1z, f1e, f1by, f1bz;
     double dF1[5];
@@ -2030,6 +2142,12 @@ k_sweep12s(Geo g, FaceEos eos, SweepArgs a1, SweepArgs a2, UpdArgs u, int ml) {
       }
     }
     // ---- x2 face s
+    if constexpr (UC) {
+      double di;
+      const double m2 = qn[1], m3 = qn[2], m1 = qn[3];
+      vel_from_cons(qn[0], m1, m2, m3, di, qn[3], qn[1], qn[2]);
+    }
+    if constexpr (BF) { qn[5] = bcc_from_faces(zlo, zhi); qn[6] = bcc_from_faces(x1n, AKMI_LANE_ABOVE(x1n)); }
     double L[NV], R[NV];
 #pragma unroll
     for (int n = 0; n < NV; ++n) {
@@ -2078,7 +2196,7 @@ k_sweep12s(Geo g, FaceEos eos, SweepArgs a1, SweepArgs a2, UpdArgs u, int ml) {
 }
 
 static int launch_sweep12s(const Geo &g, const Scheme &sc, const SweepArgs &a1, const SweepArgs &a2,
-                           const UpdArgs &u, hipStream_t st) {
+                           const UpdArgs &u, hipStream_t st, bool uc = false, bool bf = false, const double *bx3f = nullptr) {
   const long np = (long)(a2.ku - a2.kl + 1)*g.N1;          // flattened (k,i) rows
   const long nwaves = (np + (SX - 4) - 1)/(SX - 4);
   const unsigned nb = (unsigned)((nwaves + SY - 1)/SY);
@@ -2087,7 +2205,11 @@ static int launch_sweep12s(const Geo &g, const Scheme &sc, const SweepArgs &a1, 
   dim3 grid(nb, cdiv(nc, ml), g.nmb), block(SX, SY);
   const int rs = sc.rsolver;
   if (sc.iso || sc.recon != 1 || rs != AKMI_RS_HLLD) { set_error("sweep12s: PLM + HLLD, ideal gas"); return AKMI_FAIL; }
-  k_sweep12s<3><<<grid, block, 0, st>>>(g, sc.eos, a1, a2, u, ml);
+  if (bf && g.ng < 2) { set_error("sweep12s: the face form reads rows js-2 .. je+2"); return AKMI_FAIL; }
+  if (uc && bf) k_sweep12s<3, true, true><<<grid, block, 0, st>>>(g, sc.eos, a1, a2, u, ml, bx3f);
+  else if (uc) k_sweep12s<3, true, false><<<grid, block, 0, st>>>(g, sc.eos, a1, a2, u, ml, bx3f);
+  else if (bf) k_sweep12s<3, false, true><<<grid, block, 0, st>>>(g, sc.eos, a1, a2, u, ml, bx3f);
+  else k_sweep12s<3><<<grid, block, 0, st>>>(g, sc.eos, a1, a2, u, ml, bx3f);
   AKMI_CHECK_LAUNCH("sweep12s");
   return AKMI_COMPLETE;
 }
@@ -2252,26 +2374,60 @@ static int launch_scalars(const Geo &g, const Scheme &sc, const double *w0, cons
   });
 }
 
-template <bool MHD>
+// the cell-centred field and the density / velocity of every cell from u0 and the faces, through the two helpers of
+// ConsToPrim (akmi_numerics.hpp): writes what a lean conversion dropped, and nothing else (akmi_mhd_prims_fill)
+template <int DROP>
+__global__ void __launch_bounds__(SX*SY)
+k_prims_fill(Geo g, const double *__restrict__ u0, const double *__restrict__ bx1f, const double *__restrict__ bx2f,
+             const double *__restrict__ bx3f, double *__restrict__ w0, double *__restrict__ bcc0) {
+  const Cell3 q = flat_cells(0, g.N1, 0, g.N1 - 1, 0, g.N2, 0, g.N3);
+  if (!q.in) return;
+  const int i = q.i, j = q.j, k = q.k, m = q.m;
+  const size_t cs = (size_t)g.N3*g.N2*g.N1;
+  if constexpr ((DROP & AKMI_DROP_BCC) != 0) {
+    const size_t b = ix5(3, g.N3, g.N2, g.N1, m, 0, k, j, i);
+    bcc0[b] = bcc_from_faces(bx1f[ix4(g.N3, g.N2, g.N1 + 1, m, k, j, i)], bx1f[ix4(g.N3, g.N2, g.N1 + 1, m, k, j, i + 1)]);
+    bcc0[b + cs] = bcc_from_faces(bx2f[ix4(g.N3, g.N2 + 1, g.N1, m, k, j, i)], bx2f[ix4(g.N3, g.N2 + 1, g.N1, m, k, j + 1, i)]);
+    bcc0[b + 2*cs] = bcc_from_faces(bx3f[ix4(g.N3 + 1, g.N2, g.N1, m, k, j, i)], bx3f[ix4(g.N3 + 1, g.N2, g.N1, m, k + 1, j, i)]);
+  }
+  if constexpr ((DROP & AKMI_DROP_W03) != 0) {
+    const size_t c = ix5(g.nvar, g.N3, g.N2, g.N1, m, 0, k, j, i);
+    double di, wvx, wvy, wvz;
+    const double ud = u0[c];
+    vel_from_cons(ud, u0[c + cs], u0[c + 2*cs], u0[c + 3*cs], di, wvx, wvy, wvz);
+    w0[c] = ud; w0[c + cs] = wvx; w0[c + 2*cs] = wvy; w0[c + 3*cs] = wvz;
+  }
+}
+
+// the conversion of these cells takes the two-cells-per-thread kernel
+static bool c2p_pairs(const Geo &g, const Eos &eos, int il, int iu, int jl, int ju, int nk) {
+#if AKMI_C2P_PAIRS
+  static const bool pairs_off = getenv("AKMI_C2P_PAIRS") && atoi(getenv("AKMI_C2P_PAIRS")) == 0;       // A/B switch
+  // (from ~4 M cells per launch: at 128^3 = 2.3 M the launch is latency-bound and half the threads lose 5 % of a cycle,
+  //  at 192^3 = 7.5 M the pairs gain 2.4 %, at 256^3 3.5 %; profiles/r05_c2p_pairs.txt)
+  const long ncell = (long)g.nmb*nk*(ju - jl + 1)*g.N1;
+  return !pairs_off && ncell >= AKMI_C2P_PAIRS_MIN && eos.is_ideal && g.nvar == 5 && !(g.N1 & 1) && !(il & 1) && (iu & 1);
+#else
+  return false;
+#endif
+}
+
+template <bool MHD, int DROP = 0>
 static int launch_c2p(const Geo &g, const Eos &eos, double *u0, const double *bx1f,
                       const double *bx2f, const double *bx3f, double *w0, double *bcc0,
                       int do_newdt, int *counters, double *dt3, int il, int iu, int jl, int ju,
                       int k0, int nk, hipStream_t st) {
   dim3 grid((unsigned)(((long)(ju - jl + 1)*g.N1 + SX*SY - 1)/(SX*SY)), 1, nk*g.nmb), block(SX, SY);
 #if AKMI_C2P_PAIRS
-  static const bool pairs_off = getenv("AKMI_C2P_PAIRS") && atoi(getenv("AKMI_C2P_PAIRS")) == 0;       // A/B switch
-  // (from ~4 M cells per launch: at 128^3 = 2.3 M the launch is latency-bound and half the threads lose 5 % of a cycle,
-  //  at 192^3 = 7.5 M the pairs gain 2.4 %, at 256^3 3.5 %; profiles/r05_c2p_pairs.txt)
-  const long ncell = (long)g.nmb*nk*(ju - jl + 1)*g.N1;
-  if (!pairs_off && ncell >= AKMI_C2P_PAIRS_MIN && eos.is_ideal && g.nvar == 5 && !(g.N1 & 1) && !(il & 1) && (iu & 1)) {
+  if (c2p_pairs(g, eos, il, iu, jl, ju, nk)) {
     dim3 grid2((unsigned)(((long)(ju - jl + 1)*(g.N1/2) + SX*SY - 1)/(SX*SY)), 1, nk*g.nmb);
-    k_c2p_newdt2<MHD><<<grid2, block, 0, st>>>(g, eos, u0, bx1f, bx2f, bx3f, w0, bcc0, do_newdt, counters,
+    k_c2p_newdt2<MHD, DROP><<<grid2, block, 0, st>>>(g, eos, u0, bx1f, bx2f, bx3f, w0, bcc0, do_newdt, counters,
                                                dt3, il, iu, jl, ju, k0, nk);
     AKMI_CHECK_LAUNCH("c2p pairs");
     return AKMI_COMPLETE;
   }
 #endif
-  k_c2p_newdt<MHD><<<grid, block, 0, st>>>(g, eos, u0, bx1f, bx2f, bx3f, w0, bcc0, do_newdt, counters,
+  k_c2p_newdt<MHD, DROP><<<grid, block, 0, st>>>(g, eos, u0, bx1f, bx2f, bx3f, w0, bcc0, do_newdt, counters,
                                            dt3, il, iu, jl, ju, k0, nk);
   AKMI_CHECK_LAUNCH("c2p");
   return AKMI_COMPLETE;
@@ -2374,14 +2530,21 @@ static int stage_update(const akmi_pack *p, int recon, int rsolver, double gam0,
   if (check_scheme(p, recon, "stage") != AKMI_COMPLETE) return AKMI_FAIL;
   const int copy_u1 = copy_arg & AKMI_COPY_MASK;
   const bool want_x3_u0 = (copy_arg & AKMI_COPY_X3_U0) != 0;
-  if (copy_u1 > 3 || (copy_arg & ~(AKMI_COPY_MASK | AKMI_COPY_X3_U0))) { set_error("stage: bad copy_u1 = %d", copy_arg); return AKMI_FAIL; }
+  const bool want_x12_u0 = (copy_arg & AKMI_COPY_X12_U0) != 0, want_bf = (copy_arg & AKMI_COPY_BCC_FACES) != 0;
+  constexpr int form_flags = AKMI_COPY_X3_U0 | AKMI_COPY_X12_U0 | AKMI_COPY_BCC_FACES;
+  if (copy_u1 > 3 || (copy_arg & ~(AKMI_COPY_MASK | form_flags))) { set_error("stage: bad copy_u1 = %d", copy_arg); return AKMI_FAIL; }
+  if ((want_x12_u0 || want_bf) && !want_x3_u0) {
+    set_error("stage: AKMI_COPY_X12_U0 / AKMI_COPY_BCC_FACES come on top of AKMI_COPY_X3_U0");
+    return AKMI_FAIL;
+  }
   if (want_x3_u0 && copy_u1 < 2) {
     set_error("stage: the u0 form of the x3 march needs a stage that does not write the array it reads (copy_u1 2 or 3)");
     return AKMI_FAIL;
   }
   const bool sweeps_asked = (phases & AKMI_PHASE_SWEEPS) != 0;
   if ((copy_u1 == 3 || want_x3_u0) && sweeps_asked && !mhd_u0_sweeps_path<MHD>(p, recon, rsolver)) {
-    set_error("stage: copy_u1 = 3 / AKMI_COPY_X3_U0 exist for the k_sweep12s + x3 march sequence only (MHD, 3-D, PLM + HLLD, ideal gas)");
+    set_error("stage: copy_u1 = 3 and the form flags AKMI_COPY_X3_U0 / _X12_U0 / _BCC_FACES exist for the k_sweep12s + x3 march "
+              "sequence only (MHD, 3-D, PLM + HLLD, ideal gas)");
     return AKMI_FAIL;
   }
   if (sweeps_asked) last_forms = 0;
@@ -2499,9 +2662,12 @@ static int stage_update(const akmi_pack *p, int recon, int rsolver, double gam0,
     // x1 sweep inside the x2 march, cells from the march's window (k_sweep12s); x3 march consumes acc
     // (the other order -- x3 march first, leaving dF3/dx3, k_sweep12s finishing the update -- was built and measured in
     //  round 4: x3 march 891 -> 602 us, k_sweep12s 1130 -> 1374 us, +1 % on the bench; profiles/r04_x3first.txt)
-    if constexpr (MHD) rc = launch_sweep12s(g, sc, b1, b2, u, st);
-    if (rc == AKMI_COMPLETE) rc = launch_sweep_update<2, MHD, 0, true>(g, sc, b3, u, st, want_x3_u0);
+    if (want_bf) { b3.bt1 = b0x1f; b3.bt2 = b0x2f; }
+    if constexpr (MHD) rc = launch_sweep12s(g, sc, b1, b2, u, st, want_x12_u0, want_bf, b0x3f);
+    if (rc == AKMI_COMPLETE) rc = launch_sweep_update<2, MHD, 0, true>(g, sc, b3, u, st, want_x3_u0, want_bf);
     if (rc == AKMI_COMPLETE && want_x3_u0) last_forms |= AKMI_FORM_X3_U0;
+    if (rc == AKMI_COMPLETE && want_x12_u0) last_forms |= AKMI_FORM_X12_U0;
+    if (rc == AKMI_COMPLETE && want_bf) last_forms |= AKMI_FORM_BCC_FACES;
   } else if (do_sweeps) {
     rc = MHD ? launch_sweep<0, MHD, MHD>(g, sc, b1, st)
              : launch_sweep<0, MHD, false>(g, sc, b1, st);
@@ -2582,6 +2748,43 @@ int akmi_mhd_c2p_newdt(const akmi_pack *p, double *u0, const double *bx1f, const
   if (do_newdt == 1) k_init_dt3<<<1, 64, 0, st>>>(dt3);
   return launch_c2p<true>(g, make_eos(p), u0, bx1f, bx2f, bx3f, w0, bcc0, do_newdt, counters, dt3,
                           0, g.N1 - 1, 0, g.N2 - 1, 0, g.N3, st);
+}
+
+int akmi_mhd_c2p_newdt_lean(const akmi_pack *p, double *u0, const double *bx1f, const double *bx2f,
+                            const double *bx3f, double *w0, double *bcc0, int do_newdt, int *counters,
+                            double *dt3, int drop, void *stream) {
+  if (drop < 0 || drop > (AKMI_DROP_W03 | AKMI_DROP_BCC)) { set_error("c2p_newdt_lean: bad drop mask %d", drop); return AKMI_FAIL; }
+  if (drop && (!p->is_ideal || p->nvar != 5)) {
+    set_error("c2p_newdt_lean: only the sweeps of an ideal gas without scalars can do without the dropped arrays");
+    return AKMI_FAIL;
+  }
+  Geo g = make_geo(p);
+  hipStream_t st = (hipStream_t)stream;
+  if (do_newdt == 1) k_init_dt3<<<1, 64, 0, st>>>(dt3);
+  auto go = [&](auto D) {
+    return launch_c2p<true, decltype(D)::value>(g, make_eos(p), u0, bx1f, bx2f, bx3f, w0, bcc0, do_newdt, counters, dt3,
+                                                0, g.N1 - 1, 0, g.N2 - 1, 0, g.N3, st);
+  };
+  return drop == 0 ? go(IC<0>{}) : drop == 1 ? go(IC<1>{}) : drop == 2 ? go(IC<2>{}) : go(IC<3>{});
+}
+
+int akmi_mhd_c2p_takes_pairs(const akmi_pack *p) {
+  Geo g = make_geo(p);
+  return c2p_pairs(g, make_eos(p), 0, g.N1 - 1, 0, g.N2 - 1, g.N3) ? 1 : 0;
+}
+
+int akmi_mhd_prims_fill(const akmi_pack *p, const double *u0, const double *bx1f, const double *bx2f,
+                        const double *bx3f, double *w0, double *bcc0, int drop, void *stream) {
+  if (drop < 0 || drop > (AKMI_DROP_W03 | AKMI_DROP_BCC)) { set_error("prims_fill: bad drop mask %d", drop); return AKMI_FAIL; }
+  if (drop == 0) return AKMI_COMPLETE;
+  Geo g = make_geo(p);
+  hipStream_t st = (hipStream_t)stream;
+  dim3 grid((unsigned)(((long)g.N2*g.N1 + SX*SY - 1)/(SX*SY)), 1, g.N3*g.nmb), block(SX, SY);
+  if (drop == 1) k_prims_fill<1><<<grid, block, 0, st>>>(g, u0, bx1f, bx2f, bx3f, w0, bcc0);
+  else if (drop == 2) k_prims_fill<2><<<grid, block, 0, st>>>(g, u0, bx1f, bx2f, bx3f, w0, bcc0);
+  else k_prims_fill<3><<<grid, block, 0, st>>>(g, u0, bx1f, bx2f, bx3f, w0, bcc0);
+  AKMI_CHECK_LAUNCH("prims_fill");
+  return AKMI_COMPLETE;
 }
 
 int akmi_hydro_stage_fused(const akmi_pack *p, int recon, int rsolver, double gam0, double gam1,

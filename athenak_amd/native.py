@@ -175,7 +175,7 @@ class NativeSimulation:
 
     def stage_forms(self, stage):
         """which forms (capi.FORM_*) stage `stage` (1-based) of the last cycle took: the x3 march from u0, k_sweep12s from
-        u0 and the faces, the lean conversion before it; -1 when no such stage has run"""
+        u0, both from the face field, primitives that a lean conversion had left; -1 when no such stage has run"""
         return int(self.L.akmi_sim_stage_forms(self.h, int(stage)))
 
     def floor_counters(self):

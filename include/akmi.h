@@ -505,11 +505,18 @@ long long akmi_stage_workspace_bytes(const akmi_pack *p, int is_mhd);
  * AKMI_COPY_X3_U0, or-ed into copy_u1 == 2 or 3 by a caller whose w0 is ConsToPrim of u0 in every cell, ghost zones
  * included: the x3 march reads density and momentum once, from u0, instead of w0[0..3] for its window and u0[0..3]
  * again for the update (bit-identical results; refused for a stage that writes the array it reads).
+ * AKMI_COPY_X12_U0, or-ed in beside AKMI_COPY_X3_U0 under the same precondition: k_sweep12s reads density and momentum from
+ * u0 instead of w0[0..3] (it runs before the x3 march of the stage writes anything, in stream order).
+ * AKMI_COPY_BCC_FACES, likewise: k_sweep12s and the x3 march form the cell-centred field from b0's faces instead of reading
+ * bcc0.  A stage called with AKMI_COPY_X3_U0 | AKMI_COPY_X12_U0 reads w0[4] alone of w0, with AKMI_COPY_BCC_FACES on top
+ * nothing of bcc0: the conversion before it may drop those arrays (akmi_mhd_c2p_newdt_lean).
  * akmi_stage_last_forms(): which forms the last stage call of this thread that ran sweeps took, a mask of AKMI_FORM_*. */
-enum { AKMI_COPY_X3_U0 = 0x100, AKMI_COPY_MASK = 0xff };
+enum { AKMI_COPY_X3_U0 = 0x100, AKMI_COPY_X12_U0 = 0x200, AKMI_COPY_BCC_FACES = 0x400, AKMI_COPY_MASK = 0xff };
 enum { AKMI_FORM_X3_U0 = 1,     /* x3 march read u0 for its window and parked it for the update */
-       AKMI_FORM_X12_U0 = 2,    /* k_sweep12s read u0 and the face field (not built: always 0)  */
-       AKMI_FORM_LEAN_C2P = 4 };/* the conversion before the stage stored w0[4] only (not built: always 0) */
+       AKMI_FORM_X12_U0 = 2,    /* k_sweep12s read u0 instead of w0[0..3] */
+       AKMI_FORM_LEAN_C2P = 4,  /* the sweeps ran on primitives a lean conversion left (set by the host that ran that
+                                   conversion: akmi_sim_stage_forms; a stage call cannot know) */
+       AKMI_FORM_BCC_FACES = 8 };/* k_sweep12s and the x3 march formed the cell-centred field from the faces */
 int akmi_stage_last_forms(void);
 int akmi_mhd_u0_sweeps_eligible(const akmi_pack *p, int recon, int rsolver);
 int akmi_hydro_stage_update(const akmi_pack *p, int recon, int rsolver, double gam0,
@@ -528,6 +535,22 @@ int akmi_hydro_c2p_newdt(const akmi_pack *p, double *u0, double *w0, int do_newd
 int akmi_mhd_c2p_newdt(const akmi_pack *p, double *u0, const double *bx1f,
                        const double *bx2f, const double *bx3f, double *w0, double *bcc0,
                        int do_newdt, int *counters, double *dt3, void *stream);
+
+/* Lean conversion: akmi_mhd_c2p_newdt that computes everything as before -- floors, write-back to u0, counters, CFL
+ * scan -- but does not STORE the arrays named by drop (a mask of AKMI_DROP_*), which are functions of u0 and the faces
+ * alone.  For a caller whose next stage call carries the form flags that cover what is dropped.  drop == 0 is
+ * akmi_mhd_c2p_newdt.  akmi_mhd_prims_fill writes exactly the dropped arrays from u0 and the faces (no floors, w0[4]
+ * untouched): lean conversion + fill == full conversion, in all eight arrays.  (Converting twice is not the same where a
+ * floor binds: the second pass would count the floored cells again.) */
+enum { AKMI_DROP_W03 = 1,       /* w0[0..3]: density and velocity */
+       AKMI_DROP_BCC = 2 };     /* bcc0 */
+int akmi_mhd_c2p_newdt_lean(const akmi_pack *p, double *u0, const double *bx1f, const double *bx2f,
+                            const double *bx3f, double *w0, double *bcc0, int do_newdt, int *counters,
+                            double *dt3, int drop, void *stream);
+int akmi_mhd_prims_fill(const akmi_pack *p, const double *u0, const double *bx1f, const double *bx2f,
+                        const double *bx3f, double *w0, double *bcc0, int drop, void *stream);
+/* 1 where akmi_mhd_c2p_newdt of this pack takes its two-cells-per-thread kernel, the one that is bound by its stores */
+int akmi_mhd_c2p_takes_pairs(const akmi_pack *p);
 
 /* Whole stage in one call: pass A (as akmi_*_stage_update) + ConsToPrim of the ACTIVE cells
  * (+ the CFL scan when do_newdt) in the same call.  w0/bcc0 are read (old primitives) and
