@@ -129,7 +129,22 @@ struct SweepArgs {
   int il, iu, jl, ju, kl, ku;     // face ranges of this sweep
   int f3, f2, f1;
   const double *bt1 = nullptr, *bt2 = nullptr;     // x3 march in its face form: b0.x1f and b0.x2f
+  unsigned char *mfb = nullptr;   // byte form of the mass-flux sign (AKMI_MF_BYTES): one byte per face of this direction
 };
+
+// Sign of the mass flux as a byte.  On the fused 3-D MHD paths without passive scalars k_corner_ct is the only reader of the
+// three mass fluxes, and all it takes from each is `>= 0.0` (the upwind choice of GS05/07): the sweeps store that bit as
+// one byte per face instead of the double, the corner kernel tests the byte.  Same comparison as before, made by the
+// producer: -0.0 counts as non-negative, NaN as negative (not the sign bit).  The bytes live in the workspace regions of
+// the doubles they replace, face-shaped like them: byte offset = double offset / 8, block m at m*(faces of a block).
+// 0: doubles everywhere (A/B builds, tools/build_variant.sh).
+#ifndef AKMI_MF_BYTES
+#define AKMI_MF_BYTES 1
+#endif
+__device__ __forceinline__ void st_mfs(unsigned char *__restrict__ base, unsigned ob, double fd) {
+  base[ob >> 3] = (unsigned char)(fd >= 0.0);
+}
+__device__ __forceinline__ bool ld_mfs(const unsigned char *__restrict__ base, unsigned ob) { return base[ob >> 3] != 0; }
 
 // plain sweep (not the last direction): thread per face.  ECC: also emit e_cc for the right
 // cell of every face and for the extra column i = il-1 (mhd_corner_e.cpp:309-317 range
@@ -243,6 +258,7 @@ __device__ __forceinline__ void sweep_x1_shared(const Geo &g, const FaceEos &eos
   double *f = a.flx + (size_t)m*g.nvar*fs;
   stu(f, of, fd); stu(f + fs, of, fx); stu(f + 2*fs, of, fy); stu(f + 3*fs, of, fz);
   if constexpr (!rs_iso<RS>()) stu(f + 4*fs, of, fe);
+  if (AKMI_MF_BYTES && MHD && a.mfb) st_mfs(a.mfb + (size_t)m*fs, of, fd);      // the x2 march still reads the double
   if constexpr (MHD) {
     stu(a.ey + (size_t)m*cs, oc, -fby);
     stu(a.ez + (size_t)m*cs, oc, fbz);
@@ -302,6 +318,7 @@ k_sweep(Geo g, FaceEos eos, SweepArgs a, int nk) {
   double *f = a.flx + (size_t)m*g.nvar*fs;
   stu(f, of, fd); stu(f + ivx*fs, of, fx); stu(f + ivy*fs, of, fy); stu(f + ivz*fs, of, fz);
   if constexpr (!rs_iso<RS>()) stu(f + 4*fs, of, fe);
+  if (AKMI_MF_BYTES && MHD && a.mfb) st_mfs(a.mfb + (size_t)m*fs, of, fd);      // the x2 march still reads the double
   if constexpr (MHD) {
     stu(a.ey + (size_t)m*cs, oc, -fby);
     stu(a.ez + (size_t)m*cs, oc, fbz);
@@ -681,6 +698,9 @@ __device__ __forceinline__ void sweep_update_body(const Geo &g, const FaceEos &e
   const unsigned fst8 = ((DIR == 1) ? (unsigned)a.f1 : (unsigned)a.f1*(unsigned)a.f2)*8u;
   const double *bxm = MHD ? a.bxf + (size_t)m*fs : nullptr;
   double *mfm = a.flx ? a.flx + (size_t)m*g.nvar*fs : nullptr;       // variable 0: the mass flux
+  // its sign as a byte instead (wave-uniform; the u0 form exists on the k_sweep12s path only, which always takes bytes)
+  const bool mf_bytes = AKMI_MF_BYTES && MHD && !STORE && (U0F || a.mfb != nullptr);
+  unsigned char *mbm = mf_bytes ? a.mfb + (size_t)m*fs : nullptr;
   // x1 fluxes (N3,N2,N1+1) of the cell row the step finishes (x2 march without acc)
   const size_t fs1 = (size_t)g.N3*g.N2*(g.N1 + 1);
   unsigned o1 = (((unsigned)k*(unsigned)g.N2 + (unsigned)j)*(unsigned)(g.N1 + 1) + (unsigned)i)*8u;
@@ -798,7 +818,7 @@ __device__ __forceinline__ void sweep_update_body(const Geo &g, const FaceEos &e
       fd = fl.d; fx = fl.mx; fy = fl.my; fz = fl.mz; fe = fl.e;
       if (t < ml || s == shi) {
         // CornerE needs the sign of the mass flux and the two face EMFs of this direction
-        stu(mfm, foff, fd);
+        if (mf_bytes) st_mfs(mbm, foff, fd); else stu(mfm, foff, fd);
         stu(a.ey + (size_t)m*cs, oc, -fl.by);
         stu(a.ez + (size_t)m*cs, oc, fl.bz);
       }
@@ -1072,7 +1092,8 @@ __device__ __forceinline__ unsigned xcd_order(unsigned b, unsigned n) {
   return (xcd < rem ? xcd*(q + 1u) : rem*(q + 1u) + (xcd - rem)*q) + slot;
 }
 
-template <bool P2>
+// MFB: flx1..3 are the byte arrays of the mass-flux signs (AKMI_MF_BYTES), else the flux arrays whose variable 0 is compared
+template <bool P2, bool MFB>
 __device__ __forceinline__ void corner_ct_body(const Geo &g, const double *__restrict__ e3x1, const double *__restrict__ e2x1,
             const double *__restrict__ e1x2, const double *__restrict__ e3x2,
             const double *__restrict__ e2x3, const double *__restrict__ e1x3,
@@ -1129,8 +1150,14 @@ __device__ __forceinline__ void corner_ct_body(const Geo &g, const double *__res
   unsigned oc = (((unsigned)k0*(unsigned)g.N2 + (unsigned)j)*(unsigned)g.N1 + (unsigned)i)*8u;            // (.., N2, N1)
   unsigned o1 = (((unsigned)k0*(unsigned)g.N2 + (unsigned)j)*(unsigned)(g.N1 + 1) + (unsigned)i)*8u;      // (.., N2, N1+1)
   unsigned o2 = (((unsigned)k0*(unsigned)(g.N2 + 1) + (unsigned)j)*(unsigned)g.N1 + (unsigned)i)*8u;      // (.., N2+1, N1)
-  const double *f1m = flx1 + (size_t)m*g.nvar*g.N3*PS1, *f2m = flx2 + (size_t)m*g.nvar*g.N3*PS2,
-               *f3m = flx3 + (size_t)m*g.nvar*(g.N3 + 1)*PS;
+  using MF = std::conditional_t<MFB, unsigned char, double>;
+  const size_t mfv = MFB ? 1 : (size_t)g.nvar;
+  const MF *f1m = reinterpret_cast<const MF *>(flx1) + (size_t)m*mfv*g.N3*PS1,
+           *f2m = reinterpret_cast<const MF *>(flx2) + (size_t)m*mfv*g.N3*PS2,
+           *f3m = reinterpret_cast<const MF *>(flx3) + (size_t)m*mfv*(g.N3 + 1)*PS;
+  auto mf_ge0 = [](const MF *__restrict__ q, unsigned ob) -> bool {        // mass flux >= 0 on the face at byte offset ob / 8 B
+    if constexpr (MFB) return ld_mfs(q, ob); else return ldu(q, ob) >= 0.0;
+  };
   const double *x31 = e3x1 + (size_t)m*cs, *x21 = e2x1 + (size_t)m*cs, *x12 = e1x2 + (size_t)m*cs,
                *x32 = e3x2 + (size_t)m*cs, *x23 = e2x3 + (size_t)m*cs, *x13 = e1x3 + (size_t)m*cs;
   const double *c1m = c1 + (size_t)m*cs, *c2m = c2 + (size_t)m*cs, *c3m = c3 + (size_t)m*cs;
@@ -1141,8 +1168,8 @@ __device__ __forceinline__ void corner_ct_body(const Geo &g, const double *__res
   double x2_km = 0.0, x1_km = 0.0, c1_mm = 0.0, c1_m0 = 0.0, c2_mm = 0.0, c2_m0 = 0.0;
   bool f1_km = false, f2_km = false;          // mass flux >= 0 on the x1 / x2 face of plane k-1
   if (edge_ok) {
-    f1_km = ldu(f1m - PS1, o1) >= 0.0;
-    f2_km = ldu(f2m - PS2, o2) >= 0.0;
+    f1_km = mf_ge0(f1m - PS1, o1);
+    f2_km = mf_ge0(f2m - PS2, o2);
     x2_km = ldu(x12 - PS, oc);
     x1_km = ldu(x21 - PS, oc);
     c1_mm = ldu(c1m - PS - g.N1, oc); c1_m0 = ldu(c1m - PS, oc);
@@ -1154,13 +1181,13 @@ __device__ __forceinline__ void corner_ct_body(const Geo &g, const double *__res
     double e1 = 0.0, e2 = 0.0, e3 = 0.0;
     if (edge_ok) {
       bool f1_k, f1_jm, f2_k, f2_im, f3_k, f3_jm, f3_im;     // mass flux >= 0 on the faces round the corner
-      f1_k = ldu(f1m, o1) >= 0.0;
-      f1_jm = ldu(f1m - (g.N1 + 1), o1) >= 0.0;
-      f2_k = ldu(f2m, o2) >= 0.0;
-      f2_im = ldu(f2m - 1, o2) >= 0.0;
-      f3_k = ldu(f3m, oc) >= 0.0;
-      f3_jm = ldu(f3m - g.N1, oc) >= 0.0;
-      f3_im = ldu(f3m - 1, oc) >= 0.0;
+      f1_k = mf_ge0(f1m, o1);
+      f1_jm = mf_ge0(f1m - (g.N1 + 1), o1);
+      f2_k = mf_ge0(f2m, o2);
+      f2_im = mf_ge0(f2m - 1, o2);
+      f3_k = mf_ge0(f3m, oc);
+      f3_jm = mf_ge0(f3m - g.N1, oc);
+      f3_im = mf_ge0(f3m - 1, oc);
       const double c1_0m = ldu(c1m - g.N1, oc), c1_00 = ldu(c1m, oc);
       const double c2_0m = ldu(c2m - 1, oc), c2_00 = ldu(c2m, oc);
       const double x2_k = ldu(x12, oc), x1_k = ldu(x21, oc);
@@ -1234,6 +1261,7 @@ __device__ __forceinline__ void corner_ct_body(const Geo &g, const double *__res
 #ifndef AKMI_CT_WAVES
 #define AKMI_CT_WAVES 6         // waves per SIMD the register allocation aims at: 66 VGPRs, three workgroups per CU
 #endif                          // (two at the 114 VGPRs the compiler takes when left alone: 640-665 us against 621)
+template <bool MFB>
 __global__ void __launch_bounds__(CT_THREADS, AKMI_CT_WAVES)
 k_corner_ct(Geo g, const double *__restrict__ e3x1, const double *__restrict__ e2x1,
             const double *__restrict__ e1x2, const double *__restrict__ e3x2,
@@ -1245,7 +1273,7 @@ k_corner_ct(Geo g, const double *__restrict__ e3x1, const double *__restrict__ e
             double *__restrict__ b0x3f, double *__restrict__ b1x1f, double *__restrict__ b1x2f,
             double *__restrict__ b1x3f, int copy_b1, int kA, int kB, int top, int nchunk,
             int ckl, int tw, int th, const double *dtp) {
-  corner_ct_body<AKMI_POW2DX != 0>(g, e3x1, e2x1, e1x2, e3x2, e2x3, e1x3, c1, c2, c3, flx1, flx2, flx3, gam0,
+  corner_ct_body<AKMI_POW2DX != 0, MFB>(g, e3x1, e2x1, e1x2, e3x2, e2x3, e1x3, c1, c2, c3, flx1, flx2, flx3, gam0,
                                    gam1, beta_dt, b0x1f, b0x2f, b0x3f, b1x1f, b1x2f, b1x3f, copy_b1, kA, kB, top,
                                    nchunk, ckl, tw, th, dtp);
 }
@@ -2066,7 +2094,13 @@ k_sweep12s(Geo g, FaceEos eos, SweepArgs a1, SweepArgs a2, UpdArgs u, int ml, co
     W_(n, 0) = qb; W_(n, 1) = qc;
     PL_(n) = pl;
   }
+#if AKMI_MF_BYTES
+  unsigned char *mf2 = a2.mfb + (size_t)m*fs2, *mf1 = a1.mfb + (size_t)m*fs1;
+#define ST_MF_ st_mfs
+#else
   double *mf2 = a2.flx + (size_t)m*g.nvar*fs2, *mf1 = a1.flx + (size_t)m*g.nvar*fs1;
+#define ST_MF_ stu
+#endif
   const double *bym = bb + cs;                                                                   // cell-centred By
   const size_t mb = (size_t)m*g.nvar*cs;
   double by_n = BF ? 0.0 : ldu(bym, off - st8), bx1_n = ldu(bx1m, foff1);
@@ -2136,7 +2170,7 @@ k_sweep12s(Geo g, FaceEos eos, SweepArgs a1, SweepArgs a2, UpdArgs u, int ml, co
       dF1[3] = AKMI_LANE_ABOVE(f1z) - f1z;
       dF1[4] = AKMI_LANE_ABOVE(f1e) - f1e;
       if (do_x1 && x1_ok) {
-        stu(mf1, foff1, f1d);
+        ST_MF_(mf1, foff1, f1d);
         stu(a1.ey + (size_t)m*cs, orow, -f1by);
         stu(a1.ez + (size_t)m*cs, orow, f1bz);
       }
@@ -2162,7 +2196,7 @@ k_sweep12s(Geo g, FaceEos eos, SweepArgs a1, SweepArgs a2, UpdArgs u, int ml, co
     Cons1D f2 = riemann_mhd_e<RS, AKMI_X12S_EO2 != 0, AKMI_X12S_FM != 0>(eos, L[0], L[1], L[2], L[3], L[4], L[5], L[6], R[0], R[1],
                                   R[2], R[3], R[4], R[5], R[6], bx2);
     if (do_x2 && x2_ok && (t < ml || s == shi)) {
-      stu(mf2, foff2, f2.d);
+      ST_MF_(mf2, foff2, f2.d);
       stu(a2.ey + (size_t)m*cs, off, -f2.by);
       stu(a2.ez + (size_t)m*cs, off, f2.bz);
     }
@@ -2190,6 +2224,7 @@ k_sweep12s(Geo g, FaceEos eos, SweepArgs a1, SweepArgs a2, UpdArgs u, int ml, co
     for (int n = 0; n < 5; ++n) FP_(n) = fv[n];
     off += st8; foff2 += fst28; foff1 += fst18;
   }
+#undef ST_MF_
 #undef W_
 #undef PL_
 #undef FP_
@@ -2630,9 +2665,23 @@ static int stage_update(const akmi_pack *p, int recon, int rsolver, double gam0,
   //  measured slower at every slab thickness in rounds 1 and 3 -- profiles/r03_slab_ab.txt; it left the source in round 5.)
   // AKMI_HYDRO_ONE_KERNEL=0: the three-kernel sweep/march sequence also for hydro DC/PLM (A/B runs)
   static const bool hyd_one = !(getenv("AKMI_HYDRO_ONE_KERNEL") && atoi(getenv("AKMI_HYDRO_ONE_KERNEL")) == 0);
-  const bool mhd_one = mhd_one_kernel();
   const int kA = g.ks, kB = g.ke;
   SweepArgs b1 = a1, b2 = a2, b3 = a3;
+  // which sequence of sweeps the stage takes, and with it the form of the mass-flux signs: functions of the pack, the
+  // scheme and the environment switches alone, so that the phases of a stage agree when they arrive in separate calls
+  const bool mhd_one = MHD && mhd_one_kernel() && sc.recon == 1 && !sc.iso && sc.rsolver == AKMI_RS_HLLD && g.nvar == 5 &&
+                       mhd_tile(g.nx1 + 2, g.nx2 + 2).tw > 0;
+  const bool mhd_12s = MHD && !mhd_one && sc.recon == 1 && !sc.iso && sc.rsolver == AKMI_RS_HLLD && g.nvar == 5;
+  // bytes where k_corner_ct is the only reader of the mass fluxes: no passive scalars (k_scalar_update reads doubles), not
+  // k_mhd_stage3d.  k_sweep12s writes no x1 flux, so the bytes take its place; the generic x1 sweep fills flx1 with the five
+  // fluxes the x2 march reads, and its bytes go behind those of x2 in the region of flx2, of which only variable 0 is used.
+  const bool mf_bytes = AKMI_MF_BYTES && MHD && !mhd_one && g.nvar == (sc.iso ? 4 : 5);
+  if (mf_bytes) {
+    const size_t nb2 = ((size_t)g.nmb*g.N3*(g.N2 + 1)*g.N1 + 255) & ~(size_t)255;
+    b2.mfb = reinterpret_cast<unsigned char *>(w.flx2);
+    b1.mfb = mhd_12s ? reinterpret_cast<unsigned char *>(w.flx1) : b2.mfb + nb2;
+    b3.mfb = reinterpret_cast<unsigned char *>(w.flx3);
+  }
   b1.kl = kA - (MHD ? 1 : 0); b1.ku = kB + (MHD ? 1 : 0);
   b2.kl = b1.kl; b2.ku = b1.ku;
   b3.kl = kA; b3.ku = kB + 1;
@@ -2650,15 +2699,14 @@ static int stage_update(const akmi_pack *p, int recon, int rsolver, double gam0,
                         : launch_hydro_stage3d<false>(g, sc, w0, u, kA, kB, st, Mass3{nullptr, nullptr, nullptr});
       }
     }
-  } else if (do_sweeps && MHD && mhd_one && sc.recon == 1 && !sc.iso && sc.rsolver == AKMI_RS_HLLD && g.nvar == 5 &&
-             mhd_tile(g.nx1 + 2, g.nx2 + 2).tw > 0) {
+  } else if (do_sweeps && mhd_one) {
     // MHD PLM + HLLD: the three sweeps + update in one kernel (k_mhd_stage3d)
     if constexpr (MHD) {
       const MhdStageArgs ma{w0, bcc0, b0x1f, b0x2f, b0x3f, w.flx1, w.flx2, w.flx3, w.efc[0], w.efc[1], w.efc[2], w.efc[3],
                             w.efc[4], w.efc[5], w.ecc[0], w.ecc[1], w.ecc[2]};
       rc = launch_mhd_stage3d(g, sc, ma, u, st);
     }
-  } else if (do_sweeps && MHD && sc.recon == 1 && !sc.iso && sc.rsolver == AKMI_RS_HLLD && g.nvar == 5) {
+  } else if (do_sweeps && mhd_12s) {
     // x1 sweep inside the x2 march, cells from the march's window (k_sweep12s); x3 march consumes acc
     // (the other order -- x3 march first, leaving dF3/dx3, k_sweep12s finishing the update -- was built and measured in
     //  round 4: x3 march 891 -> 602 us, k_sweep12s 1130 -> 1374 us, +1 % on the bench; profiles/r04_x3first.txt)
@@ -2684,10 +2732,11 @@ static int stage_update(const akmi_pack *p, int recon, int rsolver, double gam0,
     const int ckl = march_len((long)tl.n1*tl.n2, kB - kA + 1, g.nmb, CKL);
     const int nchunk = cdiv(kB - kA + 1, ckl);
     dim3 grid(tl.n1, tl.n2, nchunk*g.nmb), block(tl.threads);
-    k_corner_ct<<<grid, block, 7*tl.tw*tl.th*sizeof(double), st>>>(
+    (mf_bytes ? k_corner_ct<true> : k_corner_ct<false>)<<<grid, block, 7*tl.tw*tl.th*sizeof(double), st>>>(
         g, w.efc[0], w.efc[1], w.efc[2], w.efc[3], w.efc[4], w.efc[5], w.ecc[0], w.ecc[1], w.ecc[2],
-        w.flx1, w.flx2, w.flx3, gam0, gam1, beta_dt, b0x1f, b0x2f, b0x3f, b1x1f, b1x2f, b1x3f,
-        copy_u1 == 3 ? 0 : copy_u1, kA, kB, 1, nchunk, ckl, tl.tw, tl.th, dt_dev);
+        mf_bytes ? reinterpret_cast<const double *>(b1.mfb) : w.flx1, mf_bytes ? reinterpret_cast<const double *>(b2.mfb) : w.flx2,
+        mf_bytes ? reinterpret_cast<const double *>(b3.mfb) : w.flx3, gam0, gam1, beta_dt, b0x1f, b0x2f, b0x3f, b1x1f, b1x2f,
+        b1x3f, copy_u1 == 3 ? 0 : copy_u1, kA, kB, 1, nchunk, ckl, tl.tw, tl.th, dt_dev);
     AKMI_CHECK_LAUNCH("corner_ct");
   }
   if (cp.enable && !c2p_done)
