@@ -61,7 +61,10 @@ SYMBOLS = [
     "akmi_coarsen", "akmi_coarsen_default_staged", "akmi_sim_coarsen",
     "akmi_stage_last_forms", "akmi_mhd_u0_sweeps_eligible", "akmi_sim_stage_forms", "akmi_sim_counters",
     "akmi_mhd_c2p_newdt_lean", "akmi_mhd_prims_fill", "akmi_mhd_c2p_takes_pairs",
+    "akmi_amr_check", "akmi_amr_regrid_cc", "akmi_amr_regrid_fc", "akmi_amr_repair_fc",
 ]
+
+AMR_METHOD = {"min_max": 0, "slope": 1, "second_deriv": 2}               # AKMI_AMR_* of include/akmi.h
 
 FORM_X3_U0, FORM_X12_U0, FORM_LEAN_C2P, FORM_BCC_FACES = 1, 2, 4, 8      # AKMI_FORM_* of include/akmi.h
 COPY_X3_U0, COPY_X12_U0, COPY_BCC_FACES = 0x100, 0x200, 0x400            # AKMI_COPY_*: or-ed into copy_u1 of a stage call

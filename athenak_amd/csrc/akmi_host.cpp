@@ -242,7 +242,7 @@ Mesh::Mesh(ParameterInput *pin, int my_rank_, int nranks_, bool host_only_)
     multilevel = true;
     BuildTreeFromScratch(pin);                 // akmi_host_smr.cpp
   } else if (ref != "none") {
-    AKMI_FATAL("<mesh_refinement>/refinement = '" + ref + "': only static refinement is on this build's path");
+    AKMI_FATAL("<mesh_refinement>/refinement = '" + ref + "': the C++ host builds none or static refinement (adaptive runs on the Python host)");
   } else {
     // Z-ordered logical locations (build_tree.cpp:243-258)
     struct Z { std::uint64_t key; int l[3]; };

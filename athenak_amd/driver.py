@@ -132,6 +132,8 @@ class Driver:
         self.nmb_updated_ += pm.nmb_total
         if getattr(self, "pout", None) is not None:
             self.pout.TestAndMakeOutputs(pm, self.pin_, self.tlim)     # driver.cpp:432-445
+        if pm.adaptive:                                                # driver.cpp:447-450
+            pm.pmr.AdaptiveMeshRefinement(self, getattr(self, "pin_", None))
         pm.NewTimeStep(self.tlim)
 
     def Finalize(self, pm, pin, pout=None):

@@ -17,6 +17,9 @@ class Simulation:
         + the restart constructor of ProblemGenerator (main.cpp:329,355-360)"""
         self.pin = pin
         self.pmesh = Mesh(pin, my_rank, nranks)
+        if restart is not None and self.pmesh.adaptive:
+            raise RuntimeError("### FATAL ERROR -r of a deck with <mesh_refinement>/refinement = adaptive: the restart "
+                               "reader rebuilds the mesh from the deck, not from the file")
         self.pmesh.AddCoordinatesAndPhysics(pin)
         if restart is not None:
             self._load_restart(*restart)

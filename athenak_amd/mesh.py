@@ -239,6 +239,27 @@ class MeshBlockPack:
         from .turb_driver import add_turbulence_driver
         self.pturb = add_turbulence_driver(self, pin)
 
+    def RebuildAfterRegrid(self, pin):
+        """the MeshBlocks, the fluid's arrays, the level-aware boundary tables and the task lists of the new mesh,
+        through the constructors a statically refined mesh takes (one code path); the caller installs the
+        regridded u0 / b0"""
+        from .tasklist import TaskList
+        from .hydro import Hydro
+        from .mhd import MHD
+        pm = self.pmesh
+        self.gids = pm.gids_eachrank[pm.my_rank]
+        self.nmb_thispack = pm.nmb_eachrank[pm.my_rank]
+        self.gide = self.gids + self.nmb_thispack - 1
+        self.AddMeshBlocks(pin)
+        for name in self.tl_map:
+            self.tl_map[name] = TaskList()
+        if self.phydro is not None:
+            self.phydro = Hydro(self, pin)
+            self.phydro.AssembleHydroTasks(self.tl_map)
+        if self.pmhd is not None:
+            self.pmhd = MHD(self, pin)
+            self.pmhd.AssembleMHDTasks(self.tl_map)
+
 
 class Mesh:
     """src/mesh/mesh.hpp:92-185, mesh.cpp:46-330, build_tree.cpp (uniform root grid)."""
@@ -290,7 +311,13 @@ class Mesh:
         ref = "none"
         if pin.DoesBlockExist("mesh_refinement"):
             ref = pin.GetOrAddString("mesh_refinement", "refinement", "none")
-        if ref == "static":
+        if ref in ("static", "adaptive"):
+            # mesh.cpp:175-177: an adaptive mesh is multilevel from the start, so the fluid takes the SMR boundary
+            # path even while every block is still on the root level
+            self.adaptive = ref == "adaptive"
+            if self.adaptive and nranks > 1:
+                raise RuntimeError("### FATAL ERROR <mesh_refinement>/refinement = adaptive runs on one rank on this "
+                                   "build's path (nranks=%d): moving MeshBlocks between ranks is not built" % nranks)
             # Mesh::BuildTreeFromScratch with <refined_region*> blocks, build_tree.cpp:32-258
             from .mesh_tree import BuildTreeFromScratch
             # mesh_refinement.cpp:52: prolongate primitive instead of conserved variables into fine ghost zones
@@ -304,8 +331,7 @@ class Mesh:
             self.gid_of_lloc = {tuple(l): i for i, l in enumerate(ll)}
             self.nmb_total = len(ll)
         elif ref != "none":
-            raise RuntimeError("### FATAL ERROR <mesh_refinement>/refinement = '%s': only static "
-                               "refinement is on this build's path" % ref)
+            raise RuntimeError("### FATAL ERROR <mesh_refinement>/refinement = '%s': none, static or adaptive" % ref)
         else:
             # Z-ordered list of logical locations (x1 fastest), build_tree.cpp:243-258
             ll = [(l1, l2, l3) for l3 in range(self.nmb_rootx3) for l2 in range(self.nmb_rootx2)
@@ -320,6 +346,18 @@ class Mesh:
         self.rank_eachmb, self.gids_eachrank, self.nmb_eachrank = LoadBalance(
             self.cost_eachmb, nranks)
         self.nmb_thisrank = self.nmb_eachrank[my_rank]
+        # build_tree.cpp:271-289: with AMR the deck bounds the MeshBlocks of a rank
+        self.nmb_maxperrank = self.nmb_thisrank
+        self.pmr = None
+        if self.adaptive:
+            if not pin.DoesParameterExist("mesh_refinement", "max_nmb_per_rank"):
+                raise RuntimeError("### FATAL ERROR With AMR maximum number of MeshBlocks per rank must be specified "
+                                   "in input file using <mesh_refinement>/max_nmb_per_rank")
+            self.nmb_maxperrank = int(pin.GetReal("mesh_refinement", "max_nmb_per_rank"))
+            if self.nmb_maxperrank < self.nmb_thisrank:
+                raise RuntimeError("### FATAL ERROR On rank=%d Root grid requires more MeshBlocks (nmb_thisrank=%d) "
+                                   "than specified by <mesh_refinement>/max_nmb_per_rank=%d"
+                                   % (my_rank, self.nmb_thisrank, self.nmb_maxperrank))
         # time: build_tree.cpp:301-302
         self.time = pin.GetOrAddReal("time", "start_time", 0.0)
         self.dt = FLT_MAX
@@ -341,6 +379,9 @@ class Mesh:
 
     def AddCoordinatesAndPhysics(self, pin):
         self.pmb_pack.AddPhysics(pin)
+        if self.adaptive:                      # mesh.cpp: pmr is made once the physics exists (the criteria name it)
+            from .mesh_refinement import MeshRefinement
+            self.pmr = MeshRefinement(self, pin)
 
     def NewTimeStep(self, tlim):
         """Mesh::NewTimeStep, src/mesh/mesh.cpp:573-643."""

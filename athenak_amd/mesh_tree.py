@@ -1,7 +1,8 @@
-"""MeshBlockTree: the octree (quadtree / binary tree) of MeshBlocks of a statically refined mesh.
+"""MeshBlockTree: the octree (quadtree / binary tree) of MeshBlocks of a statically or adaptively refined mesh.
 
 Host-side restatement of src/mesh/meshblock_tree.cpp (CreateRootGrid :64-93, AddNode :98-116,
-Refine with its 2:1 balancing :152-250, CreateZOrderedLLList :336-353, FindNeighbor :360-459), of the
+Refine with its 2:1 balancing :152-250, Derefine :256-306, CreateZOrderedLLList :336-353 with the
+new-to-old gid list of a regrid, FindNeighbor :360-459), of the
 <refined_region*> handling of Mesh::BuildTreeFromScratch (src/mesh/build_tree.cpp:32-258) and of the
 56-slot neighbour table of MeshBlock::SetNeighbors (src/mesh/meshblock.cpp:142-425,
 src/mesh/nghbr_index.hpp:28-54).
@@ -67,7 +68,9 @@ class MeshBlockTree:
     def _child(self, node, n):
         i, j, k = n & 1, (n >> 1) & 1, (n >> 2) & 1
         l = node.lloc
-        return _Node(LogicalLocation(l.lx1*2 + i, l.lx2*2 + j, l.lx3*2 + k, l.level + 1))
+        c = _Node(LogicalLocation(l.lx1*2 + i, l.lx2*2 + j, l.lx3*2 + k, l.level + 1))
+        c.gid = node.gid          # a new leaf carries its parent's gid until the next Z-ordering (:41-47)
+        return c
 
     def _create_root(self, node):
         """CreateRootGrid: the root grid may be incomplete (fewer than nleaf children)"""
@@ -87,13 +90,13 @@ class MeshBlockTree:
         sh = rloc.level - level - 1
         return ((rloc.lx1 >> sh) & 1) + (((rloc.lx2 >> sh) & 1) << 1) + (((rloc.lx3 >> sh) & 1) << 2)
 
-    def AddNode(self, rloc, node=None):
+    def AddNode(self, rloc, node=None, nnew=None):
         """create the MeshBlock at rloc, refining on the way down (each refinement also creates the
         same-level neighbours of the refined block: the 2:1 rule)"""
         node = node or self.root
         while node.lloc.level != rloc.level:
             if node.leaf is None:
-                self.Refine(node)
+                self.Refine(node, nnew)
             node = node.leaf[self._leaf_index(rloc, node.lloc.level)]
 
     def _wrap(self, l, d, level):
@@ -106,7 +109,9 @@ class MeshBlockTree:
             return 0 if self.periodic[2*d + 1] else None
         return l
 
-    def Refine(self, node):
+    def Refine(self, node, nnew=None):
+        """nnew: one-element list that counts the MeshBlocks added (nleaf-1 per refinement, those of the neighbours
+        the 2:1 rule drags along included, :248)"""
         if node.leaf is not None:
             return
         node.leaf = [self._child(node, n) for n in range(self.nleaf)]
@@ -126,15 +131,50 @@ class MeshBlockTree:
                     x = self._wrap(l.lx1 + ox, 0, l.level)
                     if x is None:
                         continue
-                    self.AddNode(LogicalLocation(x, y, z, l.level))
+                    self.AddNode(LogicalLocation(x, y, z, l.level), nnew=nnew)
         node.gid = -1
+        if nnew is not None:
+            nnew[0] += self.nleaf - 1
 
-    def CreateZOrderedLLList(self):
-        """leaves in tree-traversal (Z) order; assigns gids"""
+    def Derefine(self, node, ndel=None):
+        """make `node` a leaf again (:256-306).  Refused without a word when a touching child of any touching
+        neighbour is itself refined: the level jump would exceed one."""
+        if node.leaf is None:
+            return False
+        rng = [(-1, 0, 1) if d < self.ndim else (0,) for d in range(3)]
+        for oz in rng[2]:
+            for oy in rng[1]:
+                for ox in rng[0]:
+                    bt = self.FindNeighbor(node.lloc, ox, oy, oz, amrflag=True)
+                    if bt is None or bt.leaf is None:
+                        continue
+                    side = []
+                    for d, o in enumerate((ox, oy, oz)):
+                        if d >= self.ndim:
+                            side.append((0,))
+                        else:
+                            side.append((1,) if o == -1 else ((0,) if o == 1 else (0, 1)))
+                    for lk in side[2]:
+                        for lj in side[1]:
+                            for li in side[0]:
+                                if bt.leaf[li + (lj << 1) + (lk << 2)].leaf is not None:
+                                    return False
+        node.gid = node.leaf[0].gid          # inherits the first leaf's gid
+        node.leaf = None
+        if ndel is not None:
+            ndel[0] += self.nleaf - 1
+        return True
+
+    def CreateZOrderedLLList(self, newtoold=None):
+        """leaves in tree-traversal (Z) order; assigns gids.  newtoold: a list that receives, per new gid, the
+        gid the node carried on the old tree (a refined block's for its children, the first child's for a
+        derefined block)"""
         out = []
 
         def walk(node):
             if node.leaf is None:
+                if newtoold is not None:
+                    newtoold.append(node.gid)
                 node.gid = len(out)
                 out.append(node.lloc)
             else:
@@ -154,7 +194,7 @@ class MeshBlockTree:
                 return None
         return node
 
-    def FindNeighbor(self, myloc, ox1, ox2, ox3):
+    def FindNeighbor(self, myloc, ox1, ox2, ox3, amrflag=False):
         """the block touching myloc in direction (ox1,ox2,ox3): itself if it is a leaf of the same or
         the coarser level, its PARENT node if the neighbours are finer; None at a mesh boundary"""
         ll = myloc.level
@@ -178,7 +218,7 @@ class MeshBlockTree:
         if bt.leaf is None:
             return bt
         probe = bt.leaf[(1 if ox1 < 0 else 0) + ((1 if ox2 < 0 else 0) << 1) + ((1 if ox3 < 0 else 0) << 2)]
-        if probe.leaf is not None:
+        if probe.leaf is not None and not amrflag:
             raise RuntimeError("### FATAL ERROR Neighbor search failed. The Block Tree is broken.")
         return bt
 
@@ -257,6 +297,13 @@ def BuildTreeFromScratch(pin):
     current_level = root_level
     multilevel = pin.DoesBlockExist("mesh_refinement") and \
         gs("mesh_refinement", "refinement") in ("static", "adaptive")
+    adaptive = multilevel and gs("mesh_refinement", "refinement") == "adaptive"
+    max_level = 31
+    if adaptive:                                                  # build_tree.cpp:52-59
+        max_level = pin.GetOrAddInteger("mesh_refinement", "num_levels", 1) + root_level - 1
+        if max_level > 31:
+            raise RuntimeError("### FATAL ERROR Number of refinement levels must be smaller than %d"
+                               % (31 - root_level + 1))
     if multilevel:
         if any(mb[d] % 2 for d in range(ndim)):
             raise RuntimeError("### FATAL ERROR Number of cells in MeshBlock must be divisible by 2 "
@@ -282,6 +329,10 @@ def BuildTreeFromScratch(pin):
                                    "root mesh")
             log = phy + root_level
             current_level = max(current_level, log)
+            if log > max_level:
+                raise RuntimeError("### FATAL ERROR <refined_region> level exceeds maximum allowed (%d)\n"
+                                   "Reduce/specify 'num_levels' in <mesh_refinement> input block if using AMR"
+                                   % max_level)
             lo, hi = [0, 0, 0], [1, 1, 1]
             for d in range(ndim):
                 lxmax = nmb_root[d]*(1 << phy)
@@ -301,4 +352,4 @@ def BuildTreeFromScratch(pin):
                     for i in range(lo[0], hi[0], 2):
                         tree.AddNode(LogicalLocation(i, j, k, log))
     lloc = tree.CreateZOrderedLLList()
-    return tree, lloc, root_level, current_level
+    return tree, lloc, root_level, (max_level if adaptive else current_level)

@@ -38,6 +38,10 @@ class _PhysAlias:
 class NativeSimulation:
     def __init__(self, pin, initialize=True):
         self.pin = pin
+        if pin.DoesBlockExist("mesh_refinement") and pin.GetOrAddString("mesh_refinement", "refinement", "none") == "adaptive":
+            # said here, before the C++ host parses the deck (it would end the process with its own message)
+            raise RuntimeError("### FATAL ERROR <mesh_refinement>/refinement = adaptive runs on the Python host only "
+                               "(--host python): the C++ host builds none or static refinement")
         self.L = capi.lib()
         stream = capi._stream()
         h = self.L.akmi_sim_create(pin.Dump().encode(), stream)

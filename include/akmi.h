@@ -944,6 +944,41 @@ int akmi_coarsen_default_staged(void);      /* AKMI_COARSEN_DEFAULT_STAGED of th
 int akmi_sim_coarsen(void *sim, const akmi_coarsen_var *vars, int nvars, int factor, int moments, const int *lo,
                      const int *nc, double *out, int staged);
 
+/* ---- adaptive mesh refinement (akmi_amr.hip) ------------------------------------------------
+ * Refinement criteria, RefinementCriteria::CheckMinMax / CheckSlope / CheckSecondDeriv
+ * (src/mesh/refinement_criteria.cpp:177-338): one launch per criterion, one workgroup per MeshBlock.  q is one
+ * variable of a device array in the pack's layout; MeshBlock m starts at q + m*mstride and holds (N3, N2, N1)
+ * doubles.  The extremum over the ACTIVE cells of q (min_max), 0.5*sqrt(sum_d (q+ - q-)^2)/q (slope) or
+ * |sum_d (q+ - 2q + q-)|/q (second_deriv) is compared on the device and flags[m] (device, nmb ints) updated as the
+ * reference does, so criteria applied one after the other compose: max > value_max -> 1; max < value_max and
+ * flag == 0 -> -1; equality leaves the flag.  value_max >= FLT_MAX: not checked.  min_max only: value_min > -FLT_MAX
+ * checks the MINIMUM the same way (min < value_min -> 1; min > value_min and flag == 0 -> -1), after the maximum. */
+#define AKMI_AMR_MIN_MAX 0
+#define AKMI_AMR_SLOPE 1
+#define AKMI_AMR_SECOND_DERIV 2
+int akmi_amr_check(const akmi_pack *p, int method, const double *q, long long mstride, double value_min,
+                   double value_max, int *flags, void *stream);
+/* Regrid, out of place: the arrays of the new pack from those of the old one (same MeshBlock sizes, other nmb).
+ * plan (device): one row of three ints per NEW MeshBlock, {kind, old, octant}.
+ *   kind  0: the whole block, ghost zones included, is a copy of old block `old` (MeshRefinement::CopyCC/FC);
+ *   kind -1: the active region (faces: its upper plane included) is the restriction of the nleaf old blocks
+ *            old .. old+nleaf-1, child l into octant l (RestrictCC/FC + DerefineCC/FCSameRank,
+ *            src/mesh/mesh_refinement.cpp:696-810,1223-1382); a plane shared by two octants takes the higher one's;
+ *   kind +1: the active region is the prolongation of octant `octant` (ox1 + 2*ox2 + 4*ox3) of old block `old`,
+ *            whose cells around the octant (its ghost zones where the octant ends at the block's edge) are the
+ *            coarse stencil (CopyForRefinementCC/FC + RefineCC/FC, :919-1182): slope-limited for cells; for
+ *            faces the shared faces first, then the internal ones by the Toth & Roe operator (1-D: the mean).
+ * Everything else of the new arrays is left as it is.  A row that points outside the old pack writes nothing. */
+int akmi_amr_regrid_cc(const akmi_pack *old_pack, const akmi_pack *new_pack, int nvar, const int *plan,
+                       const double *u_old, double *u_new, void *stream);
+int akmi_amr_regrid_fc(const akmi_pack *old_pack, const akmi_pack *new_pack, const int *plan, const double *b_old1,
+                       const double *b_old2, const double *b_old3, double *b_new1, double *b_new2, double *b_new3,
+                       void *stream);
+/* MeshRefinement::RepairAMRFC (:1189-1220): the internal faces of every MeshBlock m with repair[m] > 0 (device,
+ * nmb ints, 0 or 1; a negative entry is not a flag) recomputed from its present shared faces */
+int akmi_amr_repair_fc(const akmi_pack *p, const int *repair, double *bx1f, double *bx2f, double *bx3f,
+                       void *stream);
+
 #ifdef __cplusplus
 }
 #endif
