@@ -673,11 +673,6 @@ static void FaceAlloc(DvceFaceFld &f, size_t nmb, size_t nv, size_t n3, size_t n
   f.x1f.Realloc(nmb*nv*n3*n2*(n1 + fs)); f.x2f.Realloc(nmb*nv*n3*(n2 + fs)*n1);
   f.x3f.Realloc(nmb*nv*(n3 + fs)*n2*n1);
 }
-// hydro: ConsToPrim of the active cells inside the stage kernel (akmi_hydro_stage_w); AKMI_FUSE_C2P=0: A/B switch
-static bool FuseC2P() {
-  static const bool on = !(std::getenv("AKMI_FUSE_C2P") && std::atoi(std::getenv("AKMI_FUSE_C2P")) == 0);
-  return on;
-}
 
 namespace hydro {
 Hydro::Hydro(MeshBlockPack *pp, ParameterInput *pin) : FluidBase(pp, pin, "hydro") {
@@ -699,9 +694,10 @@ Hydro::Hydro(MeshBlockPack *pp, ParameterInput *pin) : FluidBase(pp, pin, "hydro
   else FaceAlloc(uflx, pp->nmb_thispack, nvars, n3, n2, n1, 0);  // hydro.cpp:290-292
   if (StageWritesPrims()) w1.Realloc(w0.n);
 }
-// nothing here changes after construction; RKUpdate adds what the Driver decides (no captured cycle graph)
+// hydro: ConsToPrim of the active cells inside the stage kernel (akmi_hydro_stage_w; the library's answer carries the A/B
+// switches).  Nothing here changes after construction; RKUpdate adds what the Driver decides (no captured cycle graph)
 bool Hydro::StageWritesPrims() const {
-  return fused && !peers() && FuseC2P() && BcsCommuteWithC2P() && !SrcActive() &&
+  return fused && !peers() && BcsCommuteWithC2P() && !SrcActive() &&
          akmi_hydro_stage_w_eligible(&pack_c, recon_method, rsolver_method);
 }
 
@@ -1247,7 +1243,7 @@ TaskStatus Hydro::RKUpdate(Driver *d, int stage) {         // hydro_update.cpp:2
     if (copy == 2) { SwapArr(u0, u1); u_swapped = !u_swapped; }
     if (wrote) { SwapArr(w0, w1); w_swapped = !w_swapped; }
     interior_done_ = true; dt_ready_ = do_dt;
-    want_ghost_c2p_ = true;
+    want_ghost_c2p_ = wrote != 0;       // (0: converted in place, the ghost shell takes the usual path)
   } else if (fused && ((!d->use_graph && MergeC2P()) || SrcActive())) {
     // no off-rank neighbour: ONE ConsToPrim over all cells after the ghost fill (ConToPrim) instead of c2p of the
     // active cells here + c2p of the ghost shell there (thin slabs): 512 blocks of 32^3 1518 -> 1726 Mcell-updates/s.

@@ -1,24 +1,94 @@
-// akmi_hydro_stage3d2.hpp -- k_hydro_stage3d with TWO planes of the primitives in LDS (round 6; included by akmi_stage.hip
-// behind k_hydro_stage3d, whose tile chooser, LDS entry layout and launch parameters it shares).
+// akmi_hydro_stage3d2.hpp -- hydro, 3-D, DC/PLM: the three sweeps and the RK update of a stage in ONE kernel
+// (k_hydro_stage3d2, its tile chooser and LDS layout; included by akmi_stage.hip inside namespace akmi).
 //
-// Same decomposition and the same arithmetic per value as k_hydro_stage3d (hydro_fluxes.cpp:44-170, hydro_update.cpp:24-84):
-// a tile of (tw-1) x (th-1) cell columns marching along k, every cell reconstructed once per in-plane direction, x1 / x2
-// faces from the plane in LDS, the flux taking the place of the left state in the same LDS slot, x3 face per position,
-// update in the kernel.  What changes is where the marching state lives and when memory is touched -- the findings of
-// k_mhd_stage3d (profiles/r06_mhd_stage3d.txt) applied to the kernel that has the registers for three waves per SIMD:
-//   * planes k-1 AND k sit in LDS (plane k+1, loaded during the step, replaces plane k-1 once its readers are past the
-//     in-plane reconstruction): the cells k-1 and k of the position's own column are read from there for the x3 face, so
-//     the ten doubles W0 / W1 leave the register file -- no scratch (the one-plane kernel saves and restores three doubles
-//     per step through scratch, each reload an `s_waitcnt vmcnt(0)`);
+// A workgroup owns a tile of (tw-1) x (th-1) cell columns (lanes flattened over the tw x th positions; the last
+// column / row of positions only provides the face on its low side) and marches along k.  Per step k (two barriers):
+//   (A) planes k-1 and k of the primitives sit in LDS (2-low / 1-high halo in i and j).  Every cell of plane k-1 is
+//       reconstructed ONCE per in-plane direction: its position forms the limited slope from the two LDS
+//       neighbours, keeps the value at the cell's low face (right state of its own face) and hands the value at
+//       the high face to the position above through LDS (that position's left state).  The cells just outside
+//       the tile's low sides (one column, one row) are reconstructed by the first th + tw threads.
+//   (B) every position solves its low x1 and x2 face; the flux replaces the left state in the same LDS slot
+//       (entry (r,t) changes hands only between threads (r,t-1) / (r-1,t) and (r,t) across a barrier, so one array
+//       serves both and nothing is double-buffered).  The x3 face below cell k comes from the position's own entries
+//       of the two planes and the pending left state in registers.  Plane k+1, loaded during the step, replaces
+//       plane k-1 once its readers are past the in-plane reconstruction.
+//   (C) cell k-1 is finished: divf = dF1/dx1; divf += dF2/dx2; divf += dF3/dx3 (hydro_update.cpp:55-80
+//       order, the same rounding sequence as the three-kernel path; hydro_fluxes.cpp:44-170, hydro_update.cpp:24-84).
+// LDS layout: position-major, the five variables of an entry adjacent (stride 5 doubles: conflict-free for 64-bit
+// accesses), so that one address register per thread and array serves every variable and the x-neighbours through
+// the instruction's immediate offset; the y-neighbours cost one more register per array.
+// HBM traffic per cell: w0 once (+halo, L2 hits: neighbouring tiles share an XCD, xcd_order), u0 (+u1) once --
+// no flux or partial divergence arrays.  The CT-extended ranges of MHD do not apply (faces is..ie+1 only).
+//
+// Where the marching state lives and when memory is touched -- the findings of k_mhd_stage3d
+// (profiles/r06_mhd_stage3d.txt) applied to the kernel that has the registers for three waves per SIMD:
+//   * with both planes in LDS the cells k-1 and k of the position's own column are read from there for the x3 face, so
+//     the ten doubles W0 / W1 stay out of the register file -- no scratch (the one-plane kernel of round 5, removed, saved
+//     and restored three doubles per step through scratch, each reload an `s_waitcnt vmcnt(0)`);
 //   * every global load is unconditional (lanes without a cell read element 0 of the plane, planes are clamped into the
 //     array): a load inside a branch turns the wait for it into a wait for everything at the join;
 //   * the loads of plane k+1 are issued after the x1 solve and consumed after the x2 solve, the operands of the update
 //     after the x2 solve and consumed after the x3 solve; the stores of a step (u0, mass fluxes) all come after its last
 //     wait for a load (with loads and stores both outstanding the compiler's wait for a load is `vmcnt(0)`).
+struct HydTile { int tw, th, n1, n2, threads; };
+constexpr int HS_THREADS = 512;
 #ifndef AKMI_HS2_WAVES
-#define AKMI_HS2_WAVES 3
+#define AKMI_HS2_WAVES 3                   // waves per SIMD the register allocation aims at
 #endif
-static size_t hyd2_lds_doubles(int tw, int th) { return HS_ES*(2*(size_t)(tw + 3)*(th + 3) + 2*(size_t)tw*th); }
+
+// LDS of a workgroup, in doubles: the two planes with their halo and two face-shaped arrays
+constexpr int HS_ES = 5;                   // doubles per LDS entry (a padded 48-byte stride measured slower: profiles/r05_hydro_ab.txt)
+static size_t hyd_lds_doubles(int tw, int th) { return HS_ES*(2*(size_t)(tw + 3)*(th + 3) + 2*(size_t)tw*th); }
+
+static HydTile hyd_tile(int c1, int c2) {
+  // The kernel is bound by the issue of dependent fp64 chains (1 330 VALU instructions per cell, three waves per SIMD), so
+  // what a shape costs is the lanes it launches per owned column, not the length of its rows:
+  //   cost = lanes launched (tiles x padded workgroup)
+  //   x (1 + 0.3 x plane-with-halo / owners)    the LDS plane every step loads: (tw+3)(th+3) entries for (tw-1)(th-1) owners
+  //   x (1 + 4/tw)                              short rows (tw = 9: +15 % measured)
+  //   / occupancy                               workgroups per CU by LDS x waves per workgroup, against the 12 waves the
+  //                                             168 VGPRs allow
+  // fitted to the scans in profiles/r04_hydro_tiles.txt and r05_hydro_ab.txt (256^3, the one-plane kernel: 23 x 11 960 us,
+  // 28 x 9 964, 18 x 14 990, 21 x 12 990; 384-thread tiles 27 x 14 / 24 x 16: 1 380-1 480 -- six-wave workgroups leave wave
+  // slots idle).
+  static const int maxt = getenv("AKMI_HS_MAXT") ? atoi(getenv("AKMI_HS_MAXT")) : 256;   // three four-wave workgroups per CU
+  static const int maxlds = getenv("AKMI_HS_LDS") ? atoi(getenv("AKMI_HS_LDS")) : 53*1024;
+  static int f_tw = -1, f_th = 0;                        // AKMI_HS_TILE=tw,th pins the shape (experiments)
+  if (f_tw < 0) {
+    const char *e = getenv("AKMI_HS_TILE");                 // "tw,th" or "twxth"
+    f_tw = 0;
+    if (e && sscanf(e, "%d%*[,x]%d", &f_tw, &f_th) != 2) f_tw = 0;
+    if (f_tw < 4 || f_th < 3 || f_tw*f_th > HS_THREADS) f_tw = 0;
+  }
+  if (f_tw > 0 && 3*(f_tw + 3) + 3*f_th <= f_tw*f_th &&
+      hyd_lds_doubles(f_tw, f_th)*sizeof(double) <= 150*1024)
+    return HydTile{f_tw, f_th, (c1 + f_tw - 2)/(f_tw - 1), (c2 + f_th - 2)/(f_th - 1), (f_tw*f_th + 63)/64*64};
+  HydTile best{0, 0, 0, 0, 0};
+  double best_cost = -1.0;
+  for (int n1 = 1; n1 <= c1; ++n1) {
+    const int tw = (c1 + n1 - 1)/n1 + 1;
+    if (tw > 130) continue;
+    if (tw < 8 && n1 > 1) break;
+    for (int th = 3; th <= 40; ++th) {
+      if (tw*th > maxt) break;
+      if (3*(tw + 3) + 3*th > tw*th) continue;         // one halo entry per thread at most
+      const size_t lds = hyd_lds_doubles(tw, th)*sizeof(double);
+      if (lds > (size_t)maxlds) continue;
+      const int n2 = (c2 + th - 2)/(th - 1);
+      const int threads = (tw*th + 63)/64*64;
+      const int waves_cu = (int)(160*1024/lds)*(threads/64);
+      const double occ = (waves_cu < 12 ? waves_cu : 12)/12.0;
+      const double halo = (double)(tw + 3)*(th + 3)/((double)(tw - 1)*(th - 1));
+      const double cost = (double)n1*n2*threads*(1.0 + 0.3*halo)*(1.0 + 4.0/tw)/occ;
+      if (best_cost < 0 || cost < best_cost) { best = HydTile{tw, th, n1, n2, threads}; best_cost = cost; }
+    }
+  }
+  return best;
+}
+
+// MASS: passive scalars ride along -- leave the three mass fluxes behind for k_scalar_update
+struct Mass3 { double *m1, *m2, *m3; };
 
 // C2P: ConsToPrim of the cell the step finishes (+ the CFL scan on the last stage) in the same kernel -- the new conserved
 // state is in registers there, so pass B of the active cells costs five stores instead of a kernel that reads u0 back

@@ -1,5 +1,5 @@
 // akmi_mhd_stage3d.hpp -- MHD, 3-D, PLM + HLLD: the three sweeps and the RK update of a stage in ONE kernel
-// (included by akmi_stage.hip inside namespace akmi, after k_hydro_stage3d whose helpers it shares).
+// (included by akmi_stage.hip inside namespace akmi, after k_hydro_stage3d2 whose helpers it shares).
 //
 // Replaces, for one RK stage of a MeshBlockPack, the reference sequence MHD::CalculateFluxes (all three
 // directions, src/mhd/mhd_fluxes.cpp:84-266) + MHD::RKUpdate (src/mhd/mhd_update.cpp:24-84) and the two-kernel

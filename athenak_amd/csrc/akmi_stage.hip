@@ -506,7 +506,7 @@ static int march_len(long col_blocks, int ncells, int nmb, int lmax, int wgs_per
     // equal-length workgroups run in rounds of (256 CUs x resident workgroups): pick the chunk
     // length whose last round is fullest, charging the face each chunk recomputes.  Used by the
     // x2/x3 marches of small packs (128^3: -7 % per march); full-length marches, k_corner_ct and
-    // k_hydro_stage3d measured no better than the plain rule (profiles/r01_v14_tail_ab.txt)
+    // the one-kernel hydro stage measured no better than the plain rule (profiles/r01_v14_tail_ab.txt)
     const double resident = 256.0*wgs_per_cu;
     double best = -1.0;
     long best_ml = ml;
@@ -1049,7 +1049,6 @@ k_scalar_update(Geo g, FaceEos eos, const double *__restrict__ w0, const double 
 // ---------------------------------------------------------------------------------------
 // Corner EMFs (mhd_corner_e.cpp:338-414) from face EMFs, cell-centred EMFs and mass-flux
 // signs.  All operands are loaded unconditionally and chosen with selects.
-#define CCE(a, k, j, i) a[ix4(g.N3, g.N2, g.N1, m, k, j, i)]
 __device__ __forceinline__ double upw(bool pos, double fa, double ca, double fb, double cb) {
   return pos ? (fa - ca) : (fb - cb);
 }
@@ -1556,330 +1555,6 @@ k_c2p_newdt2(Geo g, Eos eos, double *__restrict__ u0, const double *__restrict__
   }
 }
 
-
-// ---------------------------------------------------------------------------------------
-// Hydro, 3-D, DC/PLM: the three sweeps and the RK update of a stage in ONE kernel.
-// A workgroup owns a tile of (tw-1) x (th-1) cell columns (lanes flattened over the tw x th
-// positions; the last column / row of positions only provides the face on its low side) and
-// marches along k.  Per step k (two barriers):
-//   (A) plane k-1 of the primitives sits in LDS (2-low / 1-high halo in i and j).  Every cell of it is
-//       reconstructed ONCE per in-plane direction: its position forms the limited slope from the two LDS
-//       neighbours, keeps the value at the cell's low face (right state of its own face) and hands the value at
-//       the high face to the position above through LDS (that position's left state).  The cells just outside
-//       the tile's low sides (one column, one row) are reconstructed by the first th + tw threads.
-//   (B) every position solves its low x1 and x2 face; the flux replaces the left state in the same LDS slot.
-//       The x3 face below cell k comes from registers (own cells k-1, k, k+1, pending left state).  Plane k
-//       replaces plane k-1 in LDS.
-//   (C) cell k-1 is finished: divf = dF1/dx1; divf += dF2/dx2; divf += dF3/dx3 (hydro_update.cpp:55-80
-//       order, the same rounding sequence as the three-kernel path).
-// HBM traffic per cell: w0 once (+halo, L2 hits: neighbouring tiles share an XCD, xcd_order), u0 (+u1) once --
-// no flux or partial divergence arrays.  The CT-extended ranges of MHD do not apply (faces is..ie+1 only).
-struct HydTile { int tw, th, n1, n2, threads; };
-constexpr int HS_THREADS = 512;
-#ifndef AKMI_HS_WAVES
-#define AKMI_HS_WAVES 3                 // waves per SIMD the register allocation aims at (168 VGPRs, 28 B of scratch: three
-                                        // doubles of the x3 march saved and restored once per step; 2: 178 VGPRs, 4: spills 172 B)
-#endif
-
-// LDS of a workgroup, in doubles: the plane with its halo and two face-shaped arrays per direction-pair
-constexpr int HS_ES = 5;                   // doubles per LDS entry (a padded 48-byte stride measured slower: profiles/r05_hydro_ab.txt)
-static size_t hyd_lds_doubles(int tw, int th, int planes = 1) { return HS_ES*(planes*(size_t)(tw + 3)*(th + 3) + 2*(size_t)tw*th); }
-
-static HydTile hyd_tile(int c1, int c2, int planes = 1) {
-  // The kernel is bound by the issue of dependent fp64 chains (1 330 VALU instructions per cell, three waves per SIMD), so
-  // what a shape costs is the lanes it launches per owned column, not the length of its rows:
-  //   cost = lanes launched (tiles x padded workgroup)
-  //   x (1 + 0.3 x plane-with-halo / owners)    the LDS plane every step loads: (tw+3)(th+3) entries for (tw-1)(th-1) owners
-  //   x (1 + 4/tw)                              short rows (tw = 9: +15 % measured)
-  //   / occupancy                               workgroups per CU by LDS x waves per workgroup, against the 12 waves the
-  //                                             168 VGPRs allow
-  // fitted to the scans in profiles/r04_hydro_tiles.txt and r05_hydro_ab.txt (256^3, this kernel: 23 x 11 960 us, 28 x 9 964,
-  // 18 x 14 990, 21 x 12 990; 384-thread tiles 27 x 14 / 24 x 16: 1 380-1 480 -- six-wave workgroups leave wave slots idle).
-  static const int maxt = getenv("AKMI_HS_MAXT") ? atoi(getenv("AKMI_HS_MAXT")) : 256;   // three four-wave workgroups per CU
-  static const int maxlds = getenv("AKMI_HS_LDS") ? atoi(getenv("AKMI_HS_LDS")) : 53*1024;
-  static int f_tw = -1, f_th = 0;                        // AKMI_HS_TILE=tw,th pins the shape (experiments)
-  if (f_tw < 0) {
-    const char *e = getenv("AKMI_HS_TILE");                 // "tw,th" or "twxth"
-    f_tw = 0;
-    if (e && sscanf(e, "%d%*[,x]%d", &f_tw, &f_th) != 2) f_tw = 0;
-    if (f_tw < 4 || f_th < 3 || f_tw*f_th > HS_THREADS) f_tw = 0;
-  }
-  if (f_tw > 0 && 3*(f_tw + 3) + 3*f_th <= f_tw*f_th &&
-      hyd_lds_doubles(f_tw, f_th, planes)*sizeof(double) <= 150*1024)
-    return HydTile{f_tw, f_th, (c1 + f_tw - 2)/(f_tw - 1), (c2 + f_th - 2)/(f_th - 1), (f_tw*f_th + 63)/64*64};
-  HydTile best{0, 0, 0, 0, 0};
-  double best_cost = -1.0;
-  for (int n1 = 1; n1 <= c1; ++n1) {
-    const int tw = (c1 + n1 - 1)/n1 + 1;
-    if (tw > 130) continue;
-    if (tw < 8 && n1 > 1) break;
-    for (int th = 3; th <= 40; ++th) {
-      if (tw*th > maxt) break;
-      if (3*(tw + 3) + 3*th > tw*th) continue;         // one halo entry per thread at most
-      const size_t lds = hyd_lds_doubles(tw, th, planes)*sizeof(double);
-      if (lds > (size_t)maxlds) continue;
-      const int n2 = (c2 + th - 2)/(th - 1);
-      const int threads = (tw*th + 63)/64*64;
-      const int waves_cu = (int)(160*1024/lds)*(threads/64);
-      const double occ = (waves_cu < 12 ? waves_cu : 12)/12.0;
-      const double halo = (double)(tw + 3)*(th + 3)/((double)(tw - 1)*(th - 1));
-      const double cost = (double)n1*n2*threads*(1.0 + 0.3*halo)*(1.0 + 4.0/tw)/occ;
-      if (best_cost < 0 || cost < best_cost) { best = HydTile{tw, th, n1, n2, threads}; best_cost = cost; }
-    }
-  }
-  return best;
-}
-
-// MASS: passive scalars ride along -- leave the three mass fluxes behind for k_scalar_update
-struct Mass3 { double *m1, *m2, *m3; };
-template <int RECON, int RS, bool MASS = false>
-__global__ void __launch_bounds__(HS_THREADS, AKMI_HS_WAVES)
-k_hydro_stage3d(Geo g, FaceEos eos, const double *__restrict__ w0, UpdArgs u, int kA, int kB,
-                int nchunk, int ckl, int tw, int th, Mass3 ms) {
-  static_assert(RECON <= 1, "one-kernel hydro stage: DC and PLM");
-  constexpr bool ISO = rs_iso<RS>();        // isothermal: variable 4 (energy) does not exist; its slots stay unused
-#define ISOSKIP if (ISO && n == 4) continue
-  extern __shared__ double hs_lds[];
-  const int pw = tw + 3, ph = th + 3;        // plane with halo: cols i0-2..i0+tw, rows j0-2..j0+th
-  const int qn = ph*pw, fn = th*tw;
-  constexpr int ES = HS_ES;                 // doubles per LDS entry (five used)
-  // SQ: primitives of the plane being worked on.  SX1/SX2 (one entry per position, x1 / x2 direction) hold FIRST the
-  // left state of the position's low face (written by the cell on the low side: every cell is reconstructed once per
-  // direction), THEN, after the solve, the flux of that face (written by the position itself, read by its low-side
-  // neighbour for the flux difference).  Entry (r,t) changes hands only between threads (r,t-1) / (r-1,t) and (r,t)
-  // across a barrier, so one array serves both and nothing is double-buffered.
-  // Layout: position-major, the five variables of an entry adjacent (stride 5 doubles: conflict-free for 64-bit
-  // accesses), so that one address register per thread and array serves every variable and the x-neighbours through
-  // the instruction's immediate offset; the y-neighbours cost one more register per array.
-  const int tid = threadIdx.x;
-  const int r = tid/tw, t = tid - r*tw;
-  const bool in_tile = r < th;
-  unsigned bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
-  {                       // tiles of a k-chunk of a block side by side on one XCD (x fastest, then y, then chunk / block)
-    const unsigned lin = xcd_order(bx + gridDim.x*(by + gridDim.y*bz), gridDim.x*gridDim.y*gridDim.z);
-    const unsigned row = lin/gridDim.x;
-    bx = lin - row*gridDim.x; bz = row/gridDim.y; by = row - bz*gridDim.y;
-  }
-  const int i0 = g.is + (int)bx*(tw - 1), j0 = g.js + (int)by*(th - 1);
-  const int i = i0 + t, j = j0 + r;
-  const int m = (int)bz/nchunk;
-  const int ch = (int)bz - m*nchunk;
-  const int k0 = kA + ch*ckl;
-  const int k1 = (k0 + ckl - 1 < kB) ? k0 + ckl - 1 : kB;
-  const bool cell_ok = in_tile && i < g.N1 && j < g.N2;                // the column exists in memory
-  const bool own = in_tile && t < tw - 1 && r < th - 1 && i <= g.ie && j <= g.je;
-  const double dx1 = g.dx[3*m], dx2 = g.dx[3*m + 1], dx3 = g.dx[3*m + 2];
-  // power-of-two cell sizes: x/dx == ldexp(x, n) bit for bit (pow2_shift); beta*dt once, in scalar registers
-  const bool p2 = AKMI_POW2DX && is_pow2(dx1) && is_pow2(dx2) && is_pow2(dx3);      // wave-uniform
-  const int n1 = pow2_shift(dx1), n2 = pow2_shift(dx2), n3 = pow2_shift(dx3);
-  const double bdt = to_sgpr(beta_dt_of(u.beta_dt, u.dtp));
-  const size_t cs = (size_t)g.N3*g.N2*g.N1, ps = (size_t)g.N2*g.N1;
-  const double *wb = w0 + (size_t)m*g.nvar*cs;
-  // halo entry of this thread: rows 0,1 and ph-1 in full, columns 0,1 and pw-1 of the tile rows
-  int hy = -1, hx = 0;
-  {
-    const int nh = 3*pw + 3*th;
-    if (tid < nh) {
-      if (tid < 3*pw) { const int q = tid/pw; hy = q < 2 ? q : ph - 1; hx = tid - q*pw; }
-      else { const int q = tid - 3*pw; const int rr = q/3, cc = q - rr*3; hy = 2 + rr; hx = cc < 2 ? cc : pw - 1; }
-    }
-  }
-  const bool hload = hy >= 0 && j0 - 2 + hy < g.N2 && i0 - 2 + hx < g.N1;      // the halo cell exists in memory
-  // the cells just outside the tile's low sides have no position of their own: column 1 of the plane (rows of the
-  // tile) and row 1 (columns of the tile) are reconstructed by the first th + tw threads, one cell each, in the one
-  // direction in which a face of the tile needs them
-  int ha = -1, hb = 0, hc = 0, hd = 0;        // LDS offsets (per variable plane: + n*qn / + n*fn) of below, here, above, destination
-  if (tid < th) { ha = (tid + 2)*pw*ES; hb = ha + ES; hc = ha + 2*ES; hd = ES*qn + tid*tw*ES; }
-  else if (tid < th + tw) { const int c = tid - th; ha = (c + 2)*ES; hb = ha + ES*pw; hc = hb + ES*pw; hd = ES*qn + ES*fn + c*ES; }
-  // own entries: cell (r+2, t+2) of the plane, position (r, t) of the two face arrays
-  const int qo = in_tile ? ((r + 2)*pw + t + 2)*ES : 0, qy = ES*pw;
-  const int xo = in_tile ? ES*qn + (r*tw + t)*ES : ES*qn, x2o = xo + ES*fn, xy = ES*tw;
-  const int hq = hy >= 0 ? (hy*pw + hx)*ES : 0;
-#define SX1o(n) hs_lds[xo + (n)]
-#define SX2o(n) hs_lds[x2o + (n)]
-  // (scalar base of the plane + 32-bit byte offset of the lane within it)
-  const unsigned hcol = hload ? ((unsigned)(j0 - 2 + hy)*(unsigned)g.N1 + (unsigned)(i0 - 2 + hx))*8u : 0u;
-  const unsigned col = cell_ok ? ((unsigned)j*(unsigned)g.N1 + (unsigned)i)*8u : 0u;
-  const size_t mb = (size_t)m*g.nvar*cs;
-  double W0[5], W1[5], PL[5], F3p[5], hv[5];
-#pragma unroll
-  for (int n = 0; n < 5; ++n) {
-      ISOSKIP;
-    const double *q = wb + n*cs;
-    W0[n] = cell_ok ? ldu(q + (size_t)(k0 - 1)*ps, col) : 1.0;
-    W1[n] = cell_ok ? ldu(q + (size_t)k0*ps, col) : 1.0;
-    if constexpr (RECON == 1) {
-      const double qa = cell_ok ? ldu(q + (size_t)(k0 - 2)*ps, col) : 1.0;
-      double dummy;
-      plm(qa, W0[n], W1[n], PL[n], dummy);
-    } else {
-      PL[n] = W0[n];
-    }
-    F3p[n] = 0.0;
-    hv[n] = hload ? ldu(wb + n*cs + (size_t)k0*ps, hcol) : 1.0;
-  }
-  // step k: x3 face k (below cell k) from registers; for k > k0 also the x1/x2 faces of plane k-1
-  // (in LDS since the previous step), which finishes cell k-1; then plane k replaces it
-  for (int k = k0; k <= k1 + 1; ++k) {
-    const bool plane = k > k0;                        // workgroup-uniform
-    double wp[5];
-#pragma unroll
-    for (int n = 0; n < 5; ++n) { ISOSKIP; wp[n] = cell_ok ? ldu(wb + n*cs + (size_t)(k + 1)*ps, col) : 1.0; }
-    double pu0[5], pu1[5];
-    if (plane && own) {                               // operands of the update, used after the solves
-      const size_t c = mb + (size_t)(k - 1)*ps;
-#pragma unroll
-      for (int n = 0; n < 5; ++n) {
-      ISOSKIP;
-        pu0[n] = ldu(u.u0 + c + n*cs, col);
-        pu1[n] = u.copy_u1 ? 0.0 : ldu(u.u1 + c + n*cs, col);
-      }
-    }
-    double f1[5] = {0, 0, 0, 0, 0}, f2[5] = {0, 0, 0, 0, 0};      // this position's own in-plane fluxes
-    if (plane) {
-      // (A) every cell of plane k-1 once per direction: the value at its upper face goes to the position above (its
-      // left state), the value at its lower face stays here (the right state of this position's own low face)
-      double R1[5] = {0, 0, 0, 0, 0}, R2[5] = {0, 0, 0, 0, 0};
-      if (in_tile) {
-        double U1[5] = {0, 0, 0, 0, 0}, U2[5] = {0, 0, 0, 0, 0};
-#pragma unroll
-        for (int n = 0; n < 5; ++n) {
-      ISOSKIP;
-          if constexpr (RECON == 1) {
-            plm(hs_lds[qo - ES + n], W0[n], hs_lds[qo + ES + n], U1[n], R1[n]);
-            plm(hs_lds[qo - qy + n], W0[n], hs_lds[qo + qy + n], U2[n], R2[n]);
-          } else {
-            R1[n] = W0[n]; R2[n] = W0[n]; U1[n] = W0[n]; U2[n] = W0[n];
-          }
-        }
-        if (t + 1 < tw) {
-#pragma unroll
-          for (int n = 0; n < 5; ++n) { ISOSKIP; hs_lds[xo + ES + n] = U1[n]; }
-        }
-        if (r + 1 < th) {
-#pragma unroll
-          for (int n = 0; n < 5; ++n) { ISOSKIP; hs_lds[x2o + xy + n] = U2[n]; }
-        }
-      }
-      if (ha >= 0) {
-#pragma unroll
-        for (int n = 0; n < 5; ++n) {
-      ISOSKIP;
-          if constexpr (RECON == 1) {
-            double up, dummy;
-            plm(hs_lds[ha + n], hs_lds[hb + n], hs_lds[hc + n], up, dummy);
-            hs_lds[hd + n] = up;
-          } else {
-            hs_lds[hd + n] = hs_lds[hb + n];
-          }
-        }
-      }
-      __syncthreads();
-      // (B) the two in-plane faces of this position; the flux takes the place of the left state
-      if (in_tile) {
-        {
-          double fd, fx, fy, fz, fe;
-          riemann_hyd_e<RS, true>(eos, SX1o(0), SX1o(1), SX1o(2), SX1o(3), ISO ? 0.0 : SX1o(4),
-                            R1[0], R1[1], R1[2], R1[3], R1[4], fd, fx, fy, fz, fe);
-          SX1o(0) = fd; SX1o(1) = fx; SX1o(2) = fy; SX1o(3) = fz;
-          if constexpr (!ISO) SX1o(4) = fe;
-          f1[0] = fd; f1[1] = fx; f1[2] = fy; f1[3] = fz; f1[4] = fe;
-          if constexpr (MASS) {
-            if (i <= g.ie + 1 && j <= g.je) ms.m1[ix5(g.nvar, g.N3, g.N2, g.N1 + 1, m, 0, k - 1, j, i)] = fd;
-          }
-        }
-        {  // sweep-aligned order (d, vy, vz, vx, e)
-          double fd, fx, fy, fz, fe;
-          riemann_hyd_e<RS, true>(eos, SX2o(0), SX2o(2), SX2o(3), SX2o(1), ISO ? 0.0 : SX2o(4),
-                            R2[0], R2[2], R2[3], R2[1], R2[4], fd, fx, fy, fz, fe);
-          SX2o(0) = fd; SX2o(2) = fx; SX2o(3) = fy; SX2o(1) = fz;
-          if constexpr (!ISO) SX2o(4) = fe;
-          f2[0] = fd; f2[2] = fx; f2[3] = fy; f2[1] = fz; f2[4] = fe;
-          if constexpr (MASS) {
-            if (i <= g.ie && j <= g.je + 1) ms.m2[ix5(g.nvar, g.N3, g.N2 + 1, g.N1, m, 0, k - 1, j, i)] = fd;
-          }
-        }
-      }
-    }
-    // x3 face below cell k: sweep-aligned order (d, vz, vx, vy, e)
-    double f3[5];
-    {
-      double L[5] = {0, 0, 0, 0, 0}, R[5] = {0, 0, 0, 0, 0};
-#pragma unroll
-      for (int n = 0; n < 5; ++n) {
-      ISOSKIP;
-        if constexpr (RECON == 1) {
-          double qln;
-          L[n] = PL[n];
-          plm(W0[n], W1[n], wp[n], qln, R[n]);
-          PL[n] = qln;
-        } else {
-          L[n] = W0[n]; R[n] = W1[n];
-        }
-      }
-      double fd, fx, fy, fz, fe;
-      riemann_hyd_e<RS, true>(eos, L[0], L[3], L[1], L[2], L[4], R[0], R[3], R[1], R[2], R[4], fd, fx, fy,
-                      fz, fe);
-      f3[0] = fd; f3[3] = fx; f3[1] = fy; f3[2] = fz; f3[4] = fe;
-      if constexpr (MASS) {
-        if (own) ms.m3[ix5(g.nvar, g.N3 + 1, g.N2, g.N1, m, 0, k, j, i)] = fd;
-      }
-    }
-    if (k <= k1) {                                     // plane k for the next step (every reader of plane k-1 is past (A))
-      if (in_tile) {
-#pragma unroll
-        for (int n = 0; n < 5; ++n) { ISOSKIP; hs_lds[qo + n] = W1[n]; }
-      }
-      if (hy >= 0) {
-#pragma unroll
-        for (int n = 0; n < 5; ++n) { ISOSKIP; hs_lds[hq + n] = hv[n]; }
-        if (hload && k + 1 <= k1) {
-#pragma unroll
-          for (int n = 0; n < 5; ++n) { ISOSKIP; hv[n] = ldu(wb + n*cs + (size_t)(k + 1)*ps, hcol); }
-        }
-      }
-    }
-    __syncthreads();
-    if (plane && own) {                                // (C) finish cell k-1
-      const size_t c = mb + (size_t)(k - 1)*ps;
-      double divf[5];
-      if (p2) {                                        // one wave-uniform branch for the fifteen quotients
-#pragma unroll
-        for (int n = 0; n < 5; ++n) {
-      ISOSKIP;
-          divf[n] = ldexp(hs_lds[xo + ES + n] - f1[n], n1);
-          divf[n] += ldexp(hs_lds[x2o + xy + n] - f2[n], n2);
-          divf[n] += ldexp(f3[n] - F3p[n], n3);
-        }
-      } else {
-#pragma unroll
-        for (int n = 0; n < 5; ++n) {
-      ISOSKIP;
-          divf[n] = (hs_lds[xo + ES + n] - f1[n])/dx1;
-          divf[n] += (hs_lds[x2o + xy + n] - f2[n])/dx2;
-          divf[n] += (f3[n] - F3p[n])/dx3;
-        }
-      }
-#pragma unroll
-      for (int n = 0; n < 5; ++n) {
-      ISOSKIP;
-        const double u0v = pu0[n];
-        const double u1v = u.copy_u1 ? u0v : pu1[n];
-        rk_store_u(u.u0 + c + n*cs, u.u1 + c + n*cs, u.copy_u1, col, u0v,
-                   u.gam0*u0v + u.gam1*u1v - bdt*divf[n]);
-      }
-    }
-#pragma unroll
-    for (int n = 0; n < 5; ++n) {
-      ISOSKIP; F3p[n] = f3[n]; W0[n] = W1[n]; W1[n] = wp[n]; }
-  }
-#undef SQ
-#undef SX1o
-#undef SX2o
-#undef ISOSKIP
-}
-
-
 #include "akmi_hydro_stage3d2.hpp"
 #include "akmi_mhd_stage3d.hpp"
 
@@ -2263,52 +1938,30 @@ static int ensure_lds(const void *kern, size_t lds, const char *who) {
   return AKMI_COMPLETE;
 }
 
-static bool hyd_two_planes() {      // AKMI_HS2=0: the one-plane kernel of round 5 (A/B runs)
-  static const bool two = !(getenv("AKMI_HS2") && atoi(getenv("AKMI_HS2")) == 0);
-  return two;
-}
-// may the stage kernel convert the cells it finishes (k_hydro_stage3d2<.., C2P>)?  3-D, DC / PLM, ideal gas, no passive
-// scalars, the two-plane kernel; AKMI_FUSE_C2P=0 switches it off (A/B runs)
-static bool hyd_c2p_inside(const Geo &g, const Scheme &sc) {
-  static const bool on = !(getenv("AKMI_FUSE_C2P") && atoi(getenv("AKMI_FUSE_C2P")) == 0);
-  return on && hyd_two_planes() && g.three_d && sc.recon <= 1 && !sc.iso && g.nvar == 5 && hyd_tile(g.nx1, g.nx2, 2).tw > 0;
-}
-
-// cpa: ConsToPrim of the finished cells inside the kernel (new primitives to cpa->w_out), nullptr: update only
+// tl: the tile of the stage's plan (plan_stage); cpa: ConsToPrim of the finished cells inside the kernel (new primitives
+// to cpa->w_out), nullptr: update only
 template <bool MASS>
-static int launch_hydro_stage3d(const Geo &g, const Scheme &sc, const double *w0, const UpdArgs &u,
+static int launch_hydro_stage3d(const Geo &g, const Scheme &sc, const HydTile &tl, const double *w0, const UpdArgs &u,
                                 int kA, int kB, hipStream_t st, Mass3 ms, const HydC2P *cpa = nullptr) {
-  const bool two = hyd_two_planes();
-  const HydTile tl = hyd_tile(g.nx1, g.nx2, two ? 2 : 1);
-  if (tl.tw == 0) { set_error("hydro_stage3d: no tile shape"); return AKMI_FAIL; }
   int ckl = march_len((long)tl.n1*tl.n2, kB - kA + 1, g.nmb, ML);
   static const int ckl_env = getenv("AKMI_HS_CKL") ? atoi(getenv("AKMI_HS_CKL")) : 0;     // experiments: pin the chunk length
   if (ckl_env > 0) ckl = ckl_env;                   // (128^3: the rule's 4 sits on the flat bottom, profiles/r05_hydro_host_ab.txt)
   const int nchunk = cdiv(kB - kA + 1, ckl);
-  const size_t lds = hyd_lds_doubles(tl.tw, tl.th, two ? 2 : 1)*sizeof(double);
+  const size_t lds = hyd_lds_doubles(tl.tw, tl.th)*sizeof(double);
   dim3 grid(tl.n1, tl.n2, nchunk*g.nmb), block(tl.threads);
   int rc = dispatch_scheme_eos<false>(sc, [&](auto R, auto S) {
     constexpr int RV = decltype(R)::value, SV = decltype(S)::value;
     if constexpr (RV <= 1) {
+      auto go = [&](auto kern, const HydC2P &cp) {
+        if (ensure_lds((const void *)kern, lds, "hydro_stage3d") != AKMI_COMPLETE) return (int)AKMI_FAIL;
+        kern<<<grid, block, lds, st>>>(g, sc.eos, w0, u, kA, kB, nchunk, ckl, tl.tw, tl.th, ms, cp);
+        return (int)AKMI_COMPLETE;
+      };
       if constexpr (!MASS && SV < 10) {
-        if (cpa) {
-          auto kern = k_hydro_stage3d2<RV, SV, false, true>;
-          if (ensure_lds((const void *)kern, lds, "hydro_stage3d") != AKMI_COMPLETE) return (int)AKMI_FAIL;
-          kern<<<grid, block, lds, st>>>(g, sc.eos, w0, u, kA, kB, nchunk, ckl, tl.tw, tl.th, ms, *cpa);
-          return (int)AKMI_COMPLETE;
-        }
+        if (cpa) return go(k_hydro_stage3d2<RV, SV, false, true>, *cpa);
       }
       if (cpa) { set_error("hydro_stage3d: ConsToPrim inside the kernel is for the ideal gas without passive scalars"); return (int)AKMI_FAIL; }
-      if (two) {
-        auto kern = k_hydro_stage3d2<RV, SV, MASS, false>;
-        if (ensure_lds((const void *)kern, lds, "hydro_stage3d") != AKMI_COMPLETE) return (int)AKMI_FAIL;
-        kern<<<grid, block, lds, st>>>(g, sc.eos, w0, u, kA, kB, nchunk, ckl, tl.tw, tl.th, ms, HydC2P{});
-      } else {
-        auto kern = k_hydro_stage3d<RV, SV, MASS>;
-        if (ensure_lds((const void *)kern, lds, "hydro_stage3d") != AKMI_COMPLETE) return (int)AKMI_FAIL;
-        kern<<<grid, block, lds, st>>>(g, sc.eos, w0, u, kA, kB, nchunk, ckl, tl.tw, tl.th, ms);
-      }
-      return (int)AKMI_COMPLETE;
+      return go(k_hydro_stage3d2<RV, SV, MASS, false>, HydC2P{});
     } else {
       set_error("hydro_stage3d: DC and PLM only");
       return (int)AKMI_FAIL;
@@ -2533,37 +2186,80 @@ int sweeps_store_fluxes(const akmi_pack *p, int recon, int rsolver, const double
 // forms (AKMI_FORM_*) of the last stage call of this thread that ran sweeps: akmi_stage_last_forms
 static thread_local int last_forms = 0;
 
-static bool mhd_one_kernel() {     // AKMI_MHD_ONE_KERNEL=1: k_mhd_stage3d instead of k_sweep12s + x3 march (A/B runs)
-  static const bool on = getenv("AKMI_MHD_ONE_KERNEL") && atoi(getenv("AKMI_MHD_ONE_KERNEL")) != 0;   // opt-in until it wins
-  return on;
-}
-// the stage takes k_sweep12s + the x3 march (the branch of stage_update that knows copy_u1 == 3 and the u0 form)
-template <bool MHD>
-static bool mhd_u0_sweeps_path(const akmi_pack *p, int recon, int rsolver) {
-  if (!MHD) return false;
-  const Geo g = make_geo(p);
-  return g.three_d && recon == 1 && p->is_ideal && rsolver == AKMI_RS_HLLD && g.nvar == 5 && !mhd_one_kernel();
+// ---------------------------------------------------------------------------------------
+// Which kernels a stage runs: a function of the pack, the scheme and the environment switches alone.  The phases of a
+// split stage arrive in separate calls and must agree, and the hosts size their arrays at construction from the two
+// eligibility answers (akmi_mhd_u0_sweeps_eligible, akmi_hydro_stage_w_eligible) -- everything that asks, asks plan_stage.
+enum class Sweeps {
+  LowDim,       // 1-D / 2-D: plain sweep (+ x2 march)
+  HydroOne,     // hydro DC / PLM: k_hydro_stage3d2
+  MhdOne,       // MHD PLM + HLLD, ideal gas: k_mhd_stage3d
+  Sweep12sX3,   // MHD PLM + HLLD, ideal gas: k_sweep12s + x3 march (the sequence that knows copy_u1 == 3 and the u0 forms)
+  Generic       // x1 sweep + x2 / x3 marches
+};
+struct StagePlan {
+  Sweeps sweeps;
+  HydTile tile;         // HydroOne (k_mhd_stage3d's launcher asks mhd_tile, whose existence MhdOne implies)
+  bool mf_bytes;        // the mass-flux signs travel as bytes (k_corner_ct<true>)
+  bool c2p_inside;      // HydroOne may convert the cells it finishes (k_hydro_stage3d2<.., C2P>): ideal gas, no passive scalars
+};
+static StagePlan plan_stage(bool mhd, const Geo &g, const Scheme &sc) {
+  // the A/B switches, read once per process (tile and chunk overrides stay with their tile functions)
+  static const auto on = [](const char *e, bool dflt) { return e ? atoi(e) != 0 : dflt; };
+  static const bool hydro_one = on(getenv("AKMI_HYDRO_ONE_KERNEL"), true);   // 0: the generic sequence also for hydro DC / PLM
+  static const bool mhd_one = on(getenv("AKMI_MHD_ONE_KERNEL"), false);      // 1: k_mhd_stage3d (opt-in until it wins)
+  static const bool fuse_c2p = on(getenv("AKMI_FUSE_C2P"), true);            // 0: ConsToPrim as a pass of its own
+  StagePlan pl{Sweeps::Generic, HydTile{0, 0, 0, 0, 0}, false, false};
+  if (!g.three_d) {
+    pl.sweeps = Sweeps::LowDim;
+  } else if (!mhd) {
+    if (hydro_one && sc.recon <= 1) pl.tile = hyd_tile(g.nx1, g.nx2);
+    if (pl.tile.tw > 0) pl.sweeps = Sweeps::HydroOne;
+    pl.c2p_inside = pl.tile.tw > 0 && fuse_c2p && !sc.iso && g.nvar == 5;
+  } else {
+    if (sc.recon == 1 && !sc.iso && sc.rsolver == AKMI_RS_HLLD && g.nvar == 5)
+      pl.sweeps = mhd_one && mhd_tile(g.nx1 + 2, g.nx2 + 2).tw > 0 ? Sweeps::MhdOne : Sweeps::Sweep12sX3;
+    // bytes where k_corner_ct is the only reader of the mass fluxes: no passive scalars (k_scalar_update reads doubles),
+    // not k_mhd_stage3d
+    pl.mf_bytes = AKMI_MF_BYTES && pl.sweeps != Sweeps::MhdOne && g.nvar == (sc.iso ? 4 : 5);
+  }
+  return pl;
 }
 
-struct C2PArgs {          // ConsToPrim of the active cells (+ CFL scan) at the end of the stage call
-  int enable, do_newdt;
-  int *counters;
-  double *dt3;
+// One stage call: what every entry point has, in the order in which the C ABI passes it, through the constructor; every
+// other field has a default, and an entry point sets what it has.
+struct StageCall {
+  StageCall(const akmi_pack *p_, int recon_, int rsolver_, double gam0_, double gam1_, double beta_dt_, int copy_arg_,
+            void *ws_, void *stream)
+      : p(p_), recon(recon_), rsolver(rsolver_), gam0(gam0_), gam1(gam1_), beta_dt(beta_dt_), copy_arg(copy_arg_), ws(ws_),
+        st((hipStream_t)stream) {}
+  const akmi_pack *p;
+  int recon, rsolver;
+  double gam0, gam1, beta_dt;                         // RK weights
+  int copy_arg;                                       // copy_u1 | AKMI_COPY_* form flags
+  void *ws;
+  hipStream_t st;
+  const double *dt_dev = nullptr;                     // set: beta_dt is the weight beta, the kernels multiply it with *dt_dev
+  int phases = AKMI_PHASE_ALL;
+  const double *w0 = nullptr, *bcc0 = nullptr;        // (ConsToPrim of the active cells writes them)
+  double *u0 = nullptr, *u1 = nullptr;
+  double *b0x1f = nullptr, *b0x2f = nullptr, *b0x3f = nullptr, *b1x1f = nullptr, *b1x2f = nullptr, *b1x3f = nullptr;
+  int c2p = 0, do_newdt = 0, *counters = nullptr;     // ConsToPrim of the active cells (+ CFL scan) at the end of the call
+  double *dt3 = nullptr;
+  double *w_out = nullptr;                            // hydro: where a stage kernel that converts its cells puts the new
+  int *wrote_new = nullptr;                           // primitives; *wrote_new = 1 when it did
 };
 
 // Pass A (+ optionally the interior part of pass B) of one stage, in stream order: the Riemann sweeps with the RK update,
 // CornerE + CT, ConsToPrim of the active cells.  `phases` selects the parts, so that a rank with off-rank neighbours can
 // post its halo messages in between.
 template <bool MHD>
-static int stage_update(const akmi_pack *p, int recon, int rsolver, double gam0, double gam1,
-                        double beta_dt,
-                        int copy_arg, const double *w0, const double *bcc0, double *u0, double *u1,
-                        double *b0x1f, double *b0x2f, double *b0x3f, double *b1x1f, double *b1x2f,
-                        double *b1x3f, void *ws, const C2PArgs &cp_in, hipStream_t st,
-                        int phases = AKMI_PHASE_ALL, const double *dt_dev = nullptr, double *w_out = nullptr,
-                        int *wrote_new = nullptr) {
-  if (check_scheme(p, recon, "stage") != AKMI_COMPLETE) return AKMI_FAIL;
-  const int copy_u1 = copy_arg & AKMI_COPY_MASK;
+static int stage_update(const StageCall &c) {
+  const akmi_pack *p = c.p;
+  hipStream_t st = c.st;
+  if (c.phases <= 0 || c.phases > AKMI_PHASE_ALL) { set_error("stage_phase: bad phase mask"); return AKMI_FAIL; }
+  if (check_scheme(p, c.recon, "stage") != AKMI_COMPLETE) return AKMI_FAIL;
+  const int copy_arg = c.copy_arg, copy_u1 = copy_arg & AKMI_COPY_MASK;
   const bool want_x3_u0 = (copy_arg & AKMI_COPY_X3_U0) != 0;
   const bool want_x12_u0 = (copy_arg & AKMI_COPY_X12_U0) != 0, want_bf = (copy_arg & AKMI_COPY_BCC_FACES) != 0;
   constexpr int form_flags = AKMI_COPY_X3_U0 | AKMI_COPY_X12_U0 | AKMI_COPY_BCC_FACES;
@@ -2576,48 +2272,41 @@ static int stage_update(const akmi_pack *p, int recon, int rsolver, double gam0,
     set_error("stage: the u0 form of the x3 march needs a stage that does not write the array it reads (copy_u1 2 or 3)");
     return AKMI_FAIL;
   }
-  const bool sweeps_asked = (phases & AKMI_PHASE_SWEEPS) != 0;
-  if ((copy_u1 == 3 || want_x3_u0) && sweeps_asked && !mhd_u0_sweeps_path<MHD>(p, recon, rsolver)) {
+  // phases: a caller that exchanges halos between the parts of a stage (multi-rank runs) asks
+  // for them one at a time; the parts communicate through u0/b0 and the workspace only
+  const bool do_sweeps = (c.phases & AKMI_PHASE_SWEEPS) != 0;
+  const bool do_emf = MHD && (c.phases & AKMI_PHASE_EMF_CT) != 0;
+  const bool do_c2p = c.c2p && (c.phases & AKMI_PHASE_C2P) != 0;
+  const Geo g = make_geo(p);
+  const Eos eos = make_eos(p);
+  const Scheme sc{c.recon, c.rsolver, make_face_eos(p), !p->is_ideal};
+  const StagePlan plan = plan_stage(MHD, g, sc);
+  if ((copy_u1 == 3 || want_x3_u0) && do_sweeps && plan.sweeps != Sweeps::Sweep12sX3) {
     set_error("stage: copy_u1 = 3 and the form flags AKMI_COPY_X3_U0 / _X12_U0 / _BCC_FACES exist for the k_sweep12s + x3 march "
               "sequence only (MHD, 3-D, PLM + HLLD, ideal gas)");
     return AKMI_FAIL;
   }
-  if (sweeps_asked) last_forms = 0;
-  if (p->nvar < (p->is_ideal ? 5 : 4)) {
-    set_error("stage: nvar = %d is smaller than the fluid variable set of the EOS", p->nvar);
-    return AKMI_FAIL;
-  }
-  Geo g = make_geo(p);
-  Eos eos = make_eos(p);
+  if (do_sweeps) last_forms = 0;
   // the sweeps address one variable of one MeshBlock with a 32-bit byte offset per lane
   if ((size_t)(g.N3 + 1)*(g.N2 + 1)*(g.N1 + 1)*sizeof(double) >= ((size_t)1 << 32)) {
     set_error("stage: a MeshBlock of %d x %d x %d cells (with ghosts) exceeds 4 GB per variable; use smaller "
               "MeshBlocks", g.N1, g.N2, g.N3);
     return AKMI_FAIL;
   }
-  const Scheme sc{recon, rsolver, make_face_eos(p), !p->is_ideal};
-  StageWs w = carve(g, MHD ? 1 : 0, ws);
-  // phases: a caller that exchanges halos between the parts of a stage (multi-rank runs) asks
-  // for them one at a time; the parts communicate through u0/b0 and the workspace only
-  const bool do_sweeps = (phases & AKMI_PHASE_SWEEPS) != 0;
-  const bool do_emf = MHD && (phases & AKMI_PHASE_EMF_CT) != 0;
-  C2PArgs cp = cp_in;
-  if (!(phases & AKMI_PHASE_C2P)) cp.enable = 0;
-  const int ndim = g.three_d ? 3 : (g.multi_d ? 2 : 1);
-  // dt_dev: beta_dt is the RK weight beta, the kernels multiply it with *dt_dev (akmi_*_stage_fused_dt)
-  UpdArgs u{gam0, gam1, beta_dt, u0, u1, w.flx1, w.flx2, copy_u1, w.acc, dt_dev};
+  StageWs w = carve(g, MHD ? 1 : 0, c.ws);
+  UpdArgs u{c.gam0, c.gam1, c.beta_dt, c.u0, c.u1, w.flx1, w.flx2, copy_u1, w.acc, c.dt_dev};
   // copy_u1 == 2 (out-of-place first stage): the new state lands in u1 / b1, which is what the c2p
   // of the active cells has to read
-  double *un = copy_u1 >= 2 ? u1 : u0;
-  const double *n1f = copy_u1 == 2 ? b1x1f : b0x1f, *n2f = copy_u1 == 2 ? b1x2f : b0x2f,
-               *n3f = copy_u1 == 2 ? b1x3f : b0x3f;
+  double *un = copy_u1 >= 2 ? c.u1 : c.u0;
+  const double *n1f = copy_u1 == 2 ? c.b1x1f : c.b0x1f, *n2f = copy_u1 == 2 ? c.b1x2f : c.b0x2f,
+               *n3f = copy_u1 == 2 ? c.b1x3f : c.b0x3f;
   int rc = AKMI_COMPLETE;
   // sweep ranges: hydro_fluxes.cpp:95-104 (no FOFC) / mhd_fluxes.cpp:117-248 (CT-extended)
-  SweepArgs a1{w0, bcc0, b0x1f, w.flx1, w.efc[0], w.efc[1], w.ecc[0], w.ecc[1], w.ecc[2],
+  SweepArgs a1{c.w0, c.bcc0, c.b0x1f, w.flx1, w.efc[0], w.efc[1], w.ecc[0], w.ecc[1], w.ecc[2],
                g.is, g.ie + 1, g.js, g.je, g.ks, g.ke, g.N3, g.N2, g.N1 + 1};
-  SweepArgs a2{w0, bcc0, b0x2f, w.flx2, w.efc[2], w.efc[3], nullptr, nullptr, nullptr,
+  SweepArgs a2{c.w0, c.bcc0, c.b0x2f, w.flx2, w.efc[2], w.efc[3], nullptr, nullptr, nullptr,
                g.is, g.ie, g.js, g.je + 1, g.ks, g.ke, g.N3, g.N2 + 1, g.N1};
-  SweepArgs a3{w0, bcc0, b0x3f, w.flx3, w.efc[4], w.efc[5], nullptr, nullptr, nullptr,
+  SweepArgs a3{c.w0, c.bcc0, c.b0x3f, w.flx3, w.efc[4], w.efc[5], nullptr, nullptr, nullptr,
                g.is, g.ie, g.js, g.je, g.ks, g.ke + 1, g.N3 + 1, g.N2, g.N1};
   if (MHD) {
     if (g.multi_d) { a1.jl = g.js - 1; a1.ju = g.je + 1; }
@@ -2626,122 +2315,99 @@ static int stage_update(const akmi_pack *p, int recon, int rsolver, double gam0,
     if (g.three_d) { a2.kl = g.ks - 1; a2.ku = g.ke + 1; }
     a3.il = g.is - 1; a3.iu = g.ie + 1; a3.jl = g.js - 1; a3.ju = g.je + 1;
   }
-  if (cp.enable && cp.do_newdt == 1) k_init_dt3<<<1, 64, 0, st>>>(cp.dt3);       // 2: the caller has reset the minima
+  if (do_c2p && c.do_newdt == 1) k_init_dt3<<<1, 64, 0, st>>>(c.dt3);       // 2: the caller has reset the minima
   bool c2p_done = false;              // ConsToPrim of the active cells happened inside the sweeps' kernel
-
-  if (ndim < 3) {
-    // 1-D / 2-D: small problems, plain sequence on the caller's stream
-    if (!do_sweeps) {
-    } else if (ndim == 1) {
-      rc = launch_sweep_update<0, MHD>(g, sc, a1, u, st);
-    } else {
-      rc = MHD ? launch_sweep<0, MHD, MHD>(g, sc, a1, st)
-               : launch_sweep<0, MHD, false>(g, sc, a1, st);
-      if (rc == AKMI_COMPLETE) rc = launch_sweep_update<1, MHD>(g, sc, a2, u, st);
-    }
-    if (rc == AKMI_COMPLETE && do_sweeps && g.nvar > (sc.iso ? 4 : 5))
-      rc = launch_scalars(g, sc, w0, w.flx1, w.flx2, w.flx3, u, g.ks, g.ke - g.ks + 1, st);
-    if (rc != AKMI_COMPLETE) return rc;
-    if (do_emf) {
-      rc = akmi_mhd_corner_e(p, w0, bcc0, w.efc[0], w.efc[1], w.efc[2], w.efc[3], w.efc[4], w.efc[5],
-                             w.flx1, w.flx2, w.flx3, w.e1, w.e2, w.e3, st);
-      if (rc != AKMI_COMPLETE) return rc;
-      const int nkc = g.ke - g.ks + 2;
-      long npc = (long)(g.je - g.js + 2)*g.N1;
-      dim3 grid((unsigned)((npc + SX*SY - 1)/(SX*SY)), 1, nkc*g.nmb), block(SX, SY);
-      k_ct_copy<<<grid, block, 0, st>>>(g, gam0, gam1, beta_dt, w.e1, w.e2, w.e3, b0x1f, b0x2f, b0x3f,
-                                        b1x1f, b1x2f, b1x3f, copy_u1, g.ks, nkc, g.ke, dt_dev);
-      AKMI_CHECK_LAUNCH("ct");
-    }
-    if (cp.enable)
-      rc = launch_c2p<MHD>(g, eos, un, n1f, n2f, n3f, const_cast<double *>(w0),
-                           const_cast<double *>(bcc0), cp.do_newdt, cp.counters, cp.dt3, g.is, g.ie,
-                           g.js, g.je, g.ks, g.ke - g.ks + 1, st);
-    return rc;
+  // the bytes of the mass-flux signs: k_sweep12s writes no x1 flux, so they take its place; the generic x1 sweep fills flx1
+  // with the five fluxes the x2 march reads, and its bytes go behind those of x2 in the region of flx2, of which only
+  // variable 0 is used.
+  if (plan.mf_bytes) {
+    const size_t nb2 = ((size_t)g.nmb*g.N3*(g.N2 + 1)*g.N1 + 255) & ~(size_t)255;
+    a2.mfb = reinterpret_cast<unsigned char *>(w.flx2);
+    a1.mfb = plan.sweeps == Sweeps::Sweep12sX3 ? reinterpret_cast<unsigned char *>(w.flx1) : a2.mfb + nb2;
+    a3.mfb = reinterpret_cast<unsigned char *>(w.flx3);
   }
 
-  // ---- 3-D: the VALU-bound sweeps, then the HBM-bound CornerE + CT and ConsToPrim, in stream order.
+  // ---- the VALU-bound sweeps, then the HBM-bound CornerE + CT and ConsToPrim, in stream order.
   // (Cutting the block into k-slabs and running the two groups on two streams one slab apart was built in round 1 and
   //  measured slower at every slab thickness in rounds 1 and 3 -- profiles/r03_slab_ab.txt; it left the source in round 5.)
-  // AKMI_HYDRO_ONE_KERNEL=0: the three-kernel sweep/march sequence also for hydro DC/PLM (A/B runs)
-  static const bool hyd_one = !(getenv("AKMI_HYDRO_ONE_KERNEL") && atoi(getenv("AKMI_HYDRO_ONE_KERNEL")) == 0);
   const int kA = g.ks, kB = g.ke;
-  SweepArgs b1 = a1, b2 = a2, b3 = a3;
-  // which sequence of sweeps the stage takes, and with it the form of the mass-flux signs: functions of the pack, the
-  // scheme and the environment switches alone, so that the phases of a stage agree when they arrive in separate calls
-  const bool mhd_one = MHD && mhd_one_kernel() && sc.recon == 1 && !sc.iso && sc.rsolver == AKMI_RS_HLLD && g.nvar == 5 &&
-                       mhd_tile(g.nx1 + 2, g.nx2 + 2).tw > 0;
-  const bool mhd_12s = MHD && !mhd_one && sc.recon == 1 && !sc.iso && sc.rsolver == AKMI_RS_HLLD && g.nvar == 5;
-  // bytes where k_corner_ct is the only reader of the mass fluxes: no passive scalars (k_scalar_update reads doubles), not
-  // k_mhd_stage3d.  k_sweep12s writes no x1 flux, so the bytes take its place; the generic x1 sweep fills flx1 with the five
-  // fluxes the x2 march reads, and its bytes go behind those of x2 in the region of flx2, of which only variable 0 is used.
-  const bool mf_bytes = AKMI_MF_BYTES && MHD && !mhd_one && g.nvar == (sc.iso ? 4 : 5);
-  if (mf_bytes) {
-    const size_t nb2 = ((size_t)g.nmb*g.N3*(g.N2 + 1)*g.N1 + 255) & ~(size_t)255;
-    b2.mfb = reinterpret_cast<unsigned char *>(w.flx2);
-    b1.mfb = mhd_12s ? reinterpret_cast<unsigned char *>(w.flx1) : b2.mfb + nb2;
-    b3.mfb = reinterpret_cast<unsigned char *>(w.flx3);
-  }
-  b1.kl = kA - (MHD ? 1 : 0); b1.ku = kB + (MHD ? 1 : 0);
-  b2.kl = b1.kl; b2.ku = b1.ku;
-  b3.kl = kA; b3.ku = kB + 1;
-  if (do_sweeps && !MHD && hyd_one && sc.recon <= 1 && hyd_tile(g.nx1, g.nx2).tw > 0) {
+  if (!do_sweeps) {
+  } else if (plan.sweeps == Sweeps::LowDim && !g.multi_d) {
+    rc = launch_sweep_update<0, MHD>(g, sc, a1, u, st);
+  } else if (plan.sweeps == Sweeps::LowDim) {
+    // 2-D (and 1-D above): small problems, plain sequence
+    rc = MHD ? launch_sweep<0, MHD, MHD>(g, sc, a1, st)
+             : launch_sweep<0, MHD, false>(g, sc, a1, st);
+    if (rc == AKMI_COMPLETE) rc = launch_sweep_update<1, MHD>(g, sc, a2, u, st);
+  } else if (plan.sweeps == Sweeps::HydroOne) {
     // hydro DC/PLM: sweeps + update in one kernel
     if constexpr (!MHD) {
-      if (w_out && cp.enable && hyd_c2p_inside(g, sc)) {
+      if (c.w_out && do_c2p && plan.c2p_inside) {
         // (the floor flags of the cells, one byte each, at the start of the workspace: akmi_hydro_ghost_uw reads them there)
-        const HydC2P hc{reinterpret_cast<unsigned char *>(ws), w_out, eos, cp.do_newdt, cp.counters, cp.dt3};
-        rc = launch_hydro_stage3d<false>(g, sc, w0, u, kA, kB, st, Mass3{nullptr, nullptr, nullptr}, &hc);
+        const HydC2P hc{reinterpret_cast<unsigned char *>(c.ws), c.w_out, eos, c.do_newdt, c.counters, c.dt3};
+        rc = launch_hydro_stage3d<false>(g, sc, plan.tile, c.w0, u, kA, kB, st, Mass3{nullptr, nullptr, nullptr}, &hc);
         c2p_done = true;
-        if (wrote_new) *wrote_new = 1;
+        if (c.wrote_new) *c.wrote_new = 1;
+      } else if (g.nvar > (sc.iso ? 4 : 5)) {
+        rc = launch_hydro_stage3d<true>(g, sc, plan.tile, c.w0, u, kA, kB, st, Mass3{w.flx1, w.flx2, w.flx3});
       } else {
-        rc = g.nvar > (sc.iso ? 4 : 5) ? launch_hydro_stage3d<true>(g, sc, w0, u, kA, kB, st, Mass3{w.flx1, w.flx2, w.flx3})
-                        : launch_hydro_stage3d<false>(g, sc, w0, u, kA, kB, st, Mass3{nullptr, nullptr, nullptr});
+        rc = launch_hydro_stage3d<false>(g, sc, plan.tile, c.w0, u, kA, kB, st, Mass3{nullptr, nullptr, nullptr});
       }
     }
-  } else if (do_sweeps && mhd_one) {
+  } else if (plan.sweeps == Sweeps::MhdOne) {
     // MHD PLM + HLLD: the three sweeps + update in one kernel (k_mhd_stage3d)
     if constexpr (MHD) {
-      const MhdStageArgs ma{w0, bcc0, b0x1f, b0x2f, b0x3f, w.flx1, w.flx2, w.flx3, w.efc[0], w.efc[1], w.efc[2], w.efc[3],
-                            w.efc[4], w.efc[5], w.ecc[0], w.ecc[1], w.ecc[2]};
+      const MhdStageArgs ma{c.w0, c.bcc0, c.b0x1f, c.b0x2f, c.b0x3f, w.flx1, w.flx2, w.flx3, w.efc[0], w.efc[1], w.efc[2],
+                            w.efc[3], w.efc[4], w.efc[5], w.ecc[0], w.ecc[1], w.ecc[2]};
       rc = launch_mhd_stage3d(g, sc, ma, u, st);
     }
-  } else if (do_sweeps && mhd_12s) {
+  } else if (plan.sweeps == Sweeps::Sweep12sX3) {
     // x1 sweep inside the x2 march, cells from the march's window (k_sweep12s); x3 march consumes acc
     // (the other order -- x3 march first, leaving dF3/dx3, k_sweep12s finishing the update -- was built and measured in
     //  round 4: x3 march 891 -> 602 us, k_sweep12s 1130 -> 1374 us, +1 % on the bench; profiles/r04_x3first.txt)
-    if (want_bf) { b3.bt1 = b0x1f; b3.bt2 = b0x2f; }
-    if constexpr (MHD) rc = launch_sweep12s(g, sc, b1, b2, u, st, want_x12_u0, want_bf, b0x3f);
-    if (rc == AKMI_COMPLETE) rc = launch_sweep_update<2, MHD, 0, true>(g, sc, b3, u, st, want_x3_u0, want_bf);
+    if (want_bf) { a3.bt1 = c.b0x1f; a3.bt2 = c.b0x2f; }
+    if constexpr (MHD) rc = launch_sweep12s(g, sc, a1, a2, u, st, want_x12_u0, want_bf, c.b0x3f);
+    if (rc == AKMI_COMPLETE) rc = launch_sweep_update<2, MHD, 0, true>(g, sc, a3, u, st, want_x3_u0, want_bf);
     if (rc == AKMI_COMPLETE && want_x3_u0) last_forms |= AKMI_FORM_X3_U0;
     if (rc == AKMI_COMPLETE && want_x12_u0) last_forms |= AKMI_FORM_X12_U0;
     if (rc == AKMI_COMPLETE && want_bf) last_forms |= AKMI_FORM_BCC_FACES;
-  } else if (do_sweeps) {
-    rc = MHD ? launch_sweep<0, MHD, MHD>(g, sc, b1, st)
-             : launch_sweep<0, MHD, false>(g, sc, b1, st);
+  } else {
+    rc = MHD ? launch_sweep<0, MHD, MHD>(g, sc, a1, st)
+             : launch_sweep<0, MHD, false>(g, sc, a1, st);
     // x2 sweep as a march along j that leaves acc = dF1/dx1 + dF2/dx2; x3 march consumes it
-    if (rc == AKMI_COMPLETE) rc = launch_sweep_update<1, MHD, 1, false>(g, sc, b2, u, st);
-    if (rc == AKMI_COMPLETE) rc = launch_sweep_update<2, MHD, 0, true>(g, sc, b3, u, st);
+    if (rc == AKMI_COMPLETE) rc = launch_sweep_update<1, MHD, 1, false>(g, sc, a2, u, st);
+    if (rc == AKMI_COMPLETE) rc = launch_sweep_update<2, MHD, 0, true>(g, sc, a3, u, st);
   }
   if (rc == AKMI_COMPLETE && do_sweeps && g.nvar > (sc.iso ? 4 : 5))
-    rc = launch_scalars(g, sc, w0, w.flx1, w.flx2, w.flx3, u, kA, kB - kA + 1, st);
+    rc = launch_scalars(g, sc, c.w0, w.flx1, w.flx2, w.flx3, u, kA, kB - kA + 1, st);
   if (rc != AKMI_COMPLETE) return rc;
-  if (MHD && do_emf) {
+  if (do_emf && plan.sweeps == Sweeps::LowDim) {
+    rc = akmi_mhd_corner_e(p, c.w0, c.bcc0, w.efc[0], w.efc[1], w.efc[2], w.efc[3], w.efc[4], w.efc[5],
+                           w.flx1, w.flx2, w.flx3, w.e1, w.e2, w.e3, st);
+    if (rc != AKMI_COMPLETE) return rc;
+    const int nkc = kB - kA + 2;
+    long npc = (long)(g.je - g.js + 2)*g.N1;
+    dim3 grid((unsigned)((npc + SX*SY - 1)/(SX*SY)), 1, nkc*g.nmb), block(SX, SY);
+    k_ct_copy<<<grid, block, 0, st>>>(g, c.gam0, c.gam1, c.beta_dt, w.e1, w.e2, w.e3, c.b0x1f, c.b0x2f, c.b0x3f,
+                                      c.b1x1f, c.b1x2f, c.b1x3f, copy_u1, kA, nkc, kB, c.dt_dev);
+    AKMI_CHECK_LAUNCH("ct");
+  } else if (do_emf) {
     // CornerE + CT in one kernel (corner EMFs of the planes [ks, ke+1] stay on chip)
     const CtTile tl = ct_tile(g.nx1 + 1, g.nx2 + 1);
     const int ckl = march_len((long)tl.n1*tl.n2, kB - kA + 1, g.nmb, CKL);
     const int nchunk = cdiv(kB - kA + 1, ckl);
     dim3 grid(tl.n1, tl.n2, nchunk*g.nmb), block(tl.threads);
-    (mf_bytes ? k_corner_ct<true> : k_corner_ct<false>)<<<grid, block, 7*tl.tw*tl.th*sizeof(double), st>>>(
+    const bool mfb = plan.mf_bytes;
+    (mfb ? k_corner_ct<true> : k_corner_ct<false>)<<<grid, block, 7*tl.tw*tl.th*sizeof(double), st>>>(
         g, w.efc[0], w.efc[1], w.efc[2], w.efc[3], w.efc[4], w.efc[5], w.ecc[0], w.ecc[1], w.ecc[2],
-        mf_bytes ? reinterpret_cast<const double *>(b1.mfb) : w.flx1, mf_bytes ? reinterpret_cast<const double *>(b2.mfb) : w.flx2,
-        mf_bytes ? reinterpret_cast<const double *>(b3.mfb) : w.flx3, gam0, gam1, beta_dt, b0x1f, b0x2f, b0x3f, b1x1f, b1x2f,
-        b1x3f, copy_u1 == 3 ? 0 : copy_u1, kA, kB, 1, nchunk, ckl, tl.tw, tl.th, dt_dev);
+        mfb ? reinterpret_cast<const double *>(a1.mfb) : w.flx1, mfb ? reinterpret_cast<const double *>(a2.mfb) : w.flx2,
+        mfb ? reinterpret_cast<const double *>(a3.mfb) : w.flx3, c.gam0, c.gam1, c.beta_dt, c.b0x1f, c.b0x2f, c.b0x3f,
+        c.b1x1f, c.b1x2f, c.b1x3f, copy_u1 == 3 ? 0 : copy_u1, kA, kB, 1, nchunk, ckl, tl.tw, tl.th, c.dt_dev);
     AKMI_CHECK_LAUNCH("corner_ct");
   }
-  if (cp.enable && !c2p_done)
-    rc = launch_c2p<MHD>(g, eos, un, n1f, n2f, n3f, const_cast<double *>(w0),
-                         const_cast<double *>(bcc0), cp.do_newdt, cp.counters, cp.dt3, g.is, g.ie,
+  if (do_c2p && !c2p_done)
+    rc = launch_c2p<MHD>(g, eos, un, n1f, n2f, n3f, const_cast<double *>(c.w0),
+                         const_cast<double *>(c.bcc0), c.do_newdt, c.counters, c.dt3, g.is, g.ie,
                          g.js, g.je, kA, kB - kA + 1, st);
   return rc;
 }
@@ -2766,18 +2432,19 @@ long long akmi_stage_workspace_bytes(const akmi_pack *p, int is_mhd) {
 int akmi_hydro_stage_update(const akmi_pack *p, int recon, int rsolver, double gam0, double gam1,
                             double beta_dt, int copy_u1, const double *w0, double *u0, double *u1,
                             void *ws, void *stream) {
-  C2PArgs cp{0, 0, nullptr, nullptr};
-  return stage_update<false>(p, recon, rsolver, gam0, gam1, beta_dt, copy_u1, w0, nullptr, u0, u1, nullptr,
-                             nullptr, nullptr, nullptr, nullptr, nullptr, ws, cp, (hipStream_t)stream);
+  StageCall c(p, recon, rsolver, gam0, gam1, beta_dt, copy_u1, ws, stream);
+  c.w0 = w0; c.u0 = u0; c.u1 = u1;
+  return stage_update<false>(c);
 }
 
 int akmi_mhd_stage_update(const akmi_pack *p, int recon, int rsolver, double gam0, double gam1,
                           double beta_dt, int copy_u1, const double *w0, const double *bcc0,
                           double *u0, double *u1, double *b0x1f, double *b0x2f, double *b0x3f,
                           double *b1x1f, double *b1x2f, double *b1x3f, void *ws, void *stream) {
-  C2PArgs cp{0, 0, nullptr, nullptr};
-  return stage_update<true>(p, recon, rsolver, gam0, gam1, beta_dt, copy_u1, w0, bcc0, u0, u1, b0x1f, b0x2f,
-                            b0x3f, b1x1f, b1x2f, b1x3f, ws, cp, (hipStream_t)stream);
+  StageCall c(p, recon, rsolver, gam0, gam1, beta_dt, copy_u1, ws, stream);
+  c.w0 = w0; c.bcc0 = bcc0; c.u0 = u0; c.u1 = u1;
+  c.b0x1f = b0x1f; c.b0x2f = b0x2f; c.b0x3f = b0x3f; c.b1x1f = b1x1f; c.b1x2f = b1x2f; c.b1x3f = b1x3f;
+  return stage_update<true>(c);
 }
 
 int akmi_hydro_c2p_newdt(const akmi_pack *p, double *u0, double *w0, int do_newdt, int *counters,
@@ -2839,18 +2506,19 @@ int akmi_mhd_prims_fill(const akmi_pack *p, const double *u0, const double *bx1f
 int akmi_hydro_stage_fused(const akmi_pack *p, int recon, int rsolver, double gam0, double gam1,
                            double beta_dt, int copy_u1, double *w0, double *u0, double *u1,
                            int do_newdt, int *counters, double *dt3, void *ws, void *stream) {
-  C2PArgs cp{1, do_newdt, counters, dt3};
-  return stage_update<false>(p, recon, rsolver, gam0, gam1, beta_dt, copy_u1, w0, nullptr, u0, u1, nullptr,
-                             nullptr, nullptr, nullptr, nullptr, nullptr, ws, cp, (hipStream_t)stream);
+  StageCall c(p, recon, rsolver, gam0, gam1, beta_dt, copy_u1, ws, stream);
+  c.w0 = w0; c.u0 = u0; c.u1 = u1;
+  c.c2p = 1; c.do_newdt = do_newdt; c.counters = counters; c.dt3 = dt3;
+  return stage_update<false>(c);
 }
 
 int akmi_hydro_stage_fused_dt(const akmi_pack *p, int recon, int rsolver, double gam0, double gam1,
                               double beta, const double *dt_dev, int copy_u1, double *w0, double *u0,
                               double *u1, int do_newdt, int *counters, double *dt3, void *ws, void *stream) {
-  C2PArgs cp{1, do_newdt, counters, dt3};
-  return stage_update<false>(p, recon, rsolver, gam0, gam1, beta, copy_u1, w0, nullptr, u0, u1, nullptr,
-                             nullptr, nullptr, nullptr, nullptr, nullptr, ws, cp, (hipStream_t)stream,
-                             AKMI_PHASE_ALL, dt_dev);
+  StageCall c(p, recon, rsolver, gam0, gam1, beta, copy_u1, ws, stream);
+  c.dt_dev = dt_dev; c.w0 = w0; c.u0 = u0; c.u1 = u1;
+  c.c2p = 1; c.do_newdt = do_newdt; c.counters = counters; c.dt3 = dt3;
+  return stage_update<false>(c);
 }
 
 int akmi_mhd_stage_fused_dt(const akmi_pack *p, int recon, int rsolver, double gam0, double gam1,
@@ -2858,9 +2526,11 @@ int akmi_mhd_stage_fused_dt(const akmi_pack *p, int recon, int rsolver, double g
                             double *u0, double *u1, double *b0x1f, double *b0x2f, double *b0x3f,
                             double *b1x1f, double *b1x2f, double *b1x3f, int do_newdt, int *counters,
                             double *dt3, void *ws, void *stream) {
-  C2PArgs cp{1, do_newdt, counters, dt3};
-  return stage_update<true>(p, recon, rsolver, gam0, gam1, beta, copy_u1, w0, bcc0, u0, u1, b0x1f, b0x2f,
-                            b0x3f, b1x1f, b1x2f, b1x3f, ws, cp, (hipStream_t)stream, AKMI_PHASE_ALL, dt_dev);
+  StageCall c(p, recon, rsolver, gam0, gam1, beta, copy_u1, ws, stream);
+  c.dt_dev = dt_dev; c.w0 = w0; c.bcc0 = bcc0; c.u0 = u0; c.u1 = u1;
+  c.b0x1f = b0x1f; c.b0x2f = b0x2f; c.b0x3f = b0x3f; c.b1x1f = b1x1f; c.b1x2f = b1x2f; c.b1x3f = b1x3f;
+  c.c2p = 1; c.do_newdt = do_newdt; c.counters = counters; c.dt3 = dt3;
+  return stage_update<true>(c);
 }
 
 int akmi_mhd_stage_fused(const akmi_pack *p, int recon, int rsolver, double gam0, double gam1,
@@ -2868,20 +2538,21 @@ int akmi_mhd_stage_fused(const akmi_pack *p, int recon, int rsolver, double gam0
                          double *b0x1f, double *b0x2f, double *b0x3f, double *b1x1f, double *b1x2f,
                          double *b1x3f, int do_newdt, int *counters, double *dt3, void *ws,
                          void *stream) {
-  C2PArgs cp{1, do_newdt, counters, dt3};
-  return stage_update<true>(p, recon, rsolver, gam0, gam1, beta_dt, copy_u1, w0, bcc0, u0, u1, b0x1f, b0x2f,
-                            b0x3f, b1x1f, b1x2f, b1x3f, ws, cp, (hipStream_t)stream);
+  StageCall c(p, recon, rsolver, gam0, gam1, beta_dt, copy_u1, ws, stream);
+  c.w0 = w0; c.bcc0 = bcc0; c.u0 = u0; c.u1 = u1;
+  c.b0x1f = b0x1f; c.b0x2f = b0x2f; c.b0x3f = b0x3f; c.b1x1f = b1x1f; c.b1x2f = b1x2f; c.b1x3f = b1x3f;
+  c.c2p = 1; c.do_newdt = do_newdt; c.counters = counters; c.dt3 = dt3;
+  return stage_update<true>(c);
 }
 
 int akmi_hydro_stage_phase(const akmi_pack *p, int recon, int rsolver, double gam0, double gam1,
                            double beta_dt, int copy_u1, double *w0, double *u0, double *u1,
                            int do_newdt, int *counters, double *dt3, int phases, void *ws,
                            void *stream) {
-  if (phases <= 0 || phases > AKMI_PHASE_ALL) { set_error("stage_phase: bad phase mask"); return AKMI_FAIL; }
-  C2PArgs cp{1, do_newdt, counters, dt3};
-  return stage_update<false>(p, recon, rsolver, gam0, gam1, beta_dt, copy_u1, w0, nullptr, u0, u1, nullptr,
-                             nullptr, nullptr, nullptr, nullptr, nullptr, ws, cp,
-                             (hipStream_t)stream, phases);
+  StageCall c(p, recon, rsolver, gam0, gam1, beta_dt, copy_u1, ws, stream);
+  c.phases = phases; c.w0 = w0; c.u0 = u0; c.u1 = u1;
+  c.c2p = 1; c.do_newdt = do_newdt; c.counters = counters; c.dt3 = dt3;
+  return stage_update<false>(c);
 }
 
 int akmi_mhd_stage_phase(const akmi_pack *p, int recon, int rsolver, double gam0, double gam1,
@@ -2889,52 +2560,57 @@ int akmi_mhd_stage_phase(const akmi_pack *p, int recon, int rsolver, double gam0
                          double *b0x1f, double *b0x2f, double *b0x3f, double *b1x1f, double *b1x2f,
                          double *b1x3f, int do_newdt, int *counters, double *dt3, int phases,
                          void *ws, void *stream) {
-  if (phases <= 0 || phases > AKMI_PHASE_ALL) { set_error("stage_phase: bad phase mask"); return AKMI_FAIL; }
-  C2PArgs cp{1, do_newdt, counters, dt3};
-  return stage_update<true>(p, recon, rsolver, gam0, gam1, beta_dt, copy_u1, w0, bcc0, u0, u1, b0x1f, b0x2f,
-                            b0x3f, b1x1f, b1x2f, b1x3f, ws, cp, (hipStream_t)stream, phases);
+  StageCall c(p, recon, rsolver, gam0, gam1, beta_dt, copy_u1, ws, stream);
+  c.phases = phases; c.w0 = w0; c.bcc0 = bcc0; c.u0 = u0; c.u1 = u1;
+  c.b0x1f = b0x1f; c.b0x2f = b0x2f; c.b0x3f = b0x3f; c.b1x1f = b1x1f; c.b1x2f = b1x2f; c.b1x3f = b1x3f;
+  c.c2p = 1; c.do_newdt = do_newdt; c.counters = counters; c.dt3 = dt3;
+  return stage_update<true>(c);
 }
 
 int akmi_hydro_stage_phase_dt(const akmi_pack *p, int recon, int rsolver, double gam0, double gam1, double beta,
                               const double *dt_dev, int copy_u1, double *w0, double *u0, double *u1, int do_newdt,
                               int *counters, double *dt3, int phases, void *ws, void *stream) {
-  if (phases <= 0 || phases > AKMI_PHASE_ALL) { set_error("stage_phase: bad phase mask"); return AKMI_FAIL; }
-  C2PArgs cp{1, do_newdt, counters, dt3};
-  return stage_update<false>(p, recon, rsolver, gam0, gam1, beta, copy_u1, w0, nullptr, u0, u1, nullptr,
-                             nullptr, nullptr, nullptr, nullptr, nullptr, ws, cp, (hipStream_t)stream, phases, dt_dev);
+  StageCall c(p, recon, rsolver, gam0, gam1, beta, copy_u1, ws, stream);
+  c.dt_dev = dt_dev; c.phases = phases; c.w0 = w0; c.u0 = u0; c.u1 = u1;
+  c.c2p = 1; c.do_newdt = do_newdt; c.counters = counters; c.dt3 = dt3;
+  return stage_update<false>(c);
 }
 
 int akmi_mhd_stage_phase_dt(const akmi_pack *p, int recon, int rsolver, double gam0, double gam1, double beta,
                             const double *dt_dev, int copy_u1, double *w0, double *bcc0, double *u0, double *u1,
                             double *b0x1f, double *b0x2f, double *b0x3f, double *b1x1f, double *b1x2f, double *b1x3f,
                             int do_newdt, int *counters, double *dt3, int phases, void *ws, void *stream) {
-  if (phases <= 0 || phases > AKMI_PHASE_ALL) { set_error("stage_phase: bad phase mask"); return AKMI_FAIL; }
-  C2PArgs cp{1, do_newdt, counters, dt3};
-  return stage_update<true>(p, recon, rsolver, gam0, gam1, beta, copy_u1, w0, bcc0, u0, u1, b0x1f, b0x2f,
-                            b0x3f, b1x1f, b1x2f, b1x3f, ws, cp, (hipStream_t)stream, phases, dt_dev);
+  StageCall c(p, recon, rsolver, gam0, gam1, beta, copy_u1, ws, stream);
+  c.dt_dev = dt_dev; c.phases = phases; c.w0 = w0; c.bcc0 = bcc0; c.u0 = u0; c.u1 = u1;
+  c.b0x1f = b0x1f; c.b0x2f = b0x2f; c.b0x3f = b0x3f; c.b1x1f = b1x1f; c.b1x2f = b1x2f; c.b1x3f = b1x3f;
+  c.c2p = 1; c.do_newdt = do_newdt; c.counters = counters; c.dt3 = dt3;
+  return stage_update<true>(c);
 }
 
 int akmi_stage_last_forms(void) { return last_forms; }
 
+// the stage takes k_sweep12s + the x3 march: the sequence that knows copy_u1 == 3 and the u0 forms
 int akmi_mhd_u0_sweeps_eligible(const akmi_pack *p, int recon, int rsolver) {
-  return mhd_u0_sweeps_path<true>(p, recon, rsolver) ? 1 : 0;
+  const Scheme sc{recon, rsolver, make_face_eos(p), !p->is_ideal};
+  return plan_stage(true, make_geo(p), sc).sweeps == Sweeps::Sweep12sX3 ? 1 : 0;
 }
 
+// akmi_hydro_stage_w converts the cells it finishes (wrote_new = 1 when the caller asks for ConsToPrim)
 int akmi_hydro_stage_w_eligible(const akmi_pack *p, int recon, int rsolver) {
-  Geo g = make_geo(p);
   const Scheme sc{recon, rsolver, make_face_eos(p), !p->is_ideal};
   return (rsolver == AKMI_RS_LLF || rsolver == AKMI_RS_HLLE || rsolver == AKMI_RS_HLLC || rsolver == AKMI_RS_ROE) &&
-         hyd_c2p_inside(g, sc) ? 1 : 0;
+         plan_stage(false, make_geo(p), sc).c2p_inside ? 1 : 0;
 }
 
 int akmi_hydro_stage_w(const akmi_pack *p, int recon, int rsolver, double gam0, double gam1, double beta,
                        const double *dt_dev, int copy_u1, double *w0, double *w0_new, double *u0, double *u1,
                        int do_newdt, int *counters, double *dt3, void *ws, void *stream, int *wrote_new) {
   if (wrote_new) *wrote_new = 0;
-  C2PArgs cp{1, do_newdt, counters, dt3};
-  return stage_update<false>(p, recon, rsolver, gam0, gam1, beta, copy_u1, w0, nullptr, u0, u1, nullptr, nullptr, nullptr,
-                             nullptr, nullptr, nullptr, ws, cp, (hipStream_t)stream, AKMI_PHASE_ALL, dt_dev, w0_new,
-                             wrote_new);
+  StageCall c(p, recon, rsolver, gam0, gam1, beta, copy_u1, ws, stream);
+  c.dt_dev = dt_dev; c.w0 = w0; c.u0 = u0; c.u1 = u1;
+  c.c2p = 1; c.do_newdt = do_newdt; c.counters = counters; c.dt3 = dt3;
+  c.w_out = w0_new; c.wrote_new = wrote_new;
+  return stage_update<false>(c);
 }
 
 int akmi_hydro_c2p_shell(const akmi_pack *p, double *u0, double *w0, int *counters, void *stream) {

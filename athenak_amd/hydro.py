@@ -243,7 +243,6 @@ class FluidBase:
 
 import os as _os
 _MERGE_C2P = _os.environ.get("AKMI_MERGE_C2P", "1") != "0"      # A/B switch (profiles/r03_whatif_merge_c2p.txt)
-_FUSE_C2P = _os.environ.get("AKMI_FUSE_C2P", "1") != "0"        # hydro: ConsToPrim inside the stage kernel (akmi_hydro_stage_w)
 _TASK_OOP = _os.environ.get("AKMI_TASK_OOP", "1") != "0"        # A/B switch: first stage of the task path out of place
 
 
@@ -399,7 +398,7 @@ class Hydro(FluidBase):
             # off-rank neighbours: only the sweeps + update here, so that SendU can post the
             # halo messages before the c2p of the active cells is enqueued (see SendU)
             self._stage_phase(pdrive, stage, capi.PHASE_SWEEPS)
-        elif self.fused and _FUSE_C2P and self._w_eligible():
+        elif self.fused and self._w_eligible():
             # the stage kernel converts the cells it finishes (their new state is in its registers) into the second
             # primitive array; ConToPrim then only has the ghost shell left (after the ghost fill)
             self._stage_w(pdrive, stage)
@@ -469,7 +468,7 @@ class Hydro(FluidBase):
             self.w0, self.w1 = self.w1, self.w0
         self._interior_done = True
         self._dt_ready = bool(do_dt)
-        self._want_ghost_c2p = True
+        self._want_ghost_c2p = bool(wrote.value)    # (0: converted in place, the ghost shell takes the usual path)
 
     def _stage_phase(self, pdrive, stage, phases):
         """akmi_hydro_stage_phase: the parts of the fused stage named by the mask `phases`"""

@@ -5,7 +5,8 @@ once per process, so every case runs in a process of its own and must be bit-ide
   AKMI_OUT_OF_PLACE=0  C++ host: CopyCons + in-place first stage instead of the out-of-place stage with swapped registers
 (the sign-word, two-kernel-x12 and k_march3ct options of rounds 3-4 lost their measurements and left the source in round 5)
   AKMI_MHD_ONE_KERNEL=1  the three MHD sweeps + update in one tile kernel (k_mhd_stage3d; opt-in, slower)
-  AKMI_FUSE_C2P=0 / AKMI_HS2=0 / AKMI_STREAM_NONBLOCKING=1  hydro one-kernel stage: see test_hydro_stage_option_does_not_change_a_bit
+  AKMI_FUSE_C2P=0 / AKMI_STREAM_NONBLOCKING=1  hydro one-kernel stage: see test_hydro_stage_option_does_not_change_a_bit
+  AKMI_HYDRO_ONE_KERNEL=0  3-D hydro DC / PLM: x1 sweep + x2 / x3 marches instead of k_hydro_stage3d2
 C++ host, single rank, uniform mesh:
   AKMI_RUN_AHEAD=0  the new time step read back at the end of every cycle (one host synchronisation per cycle) instead of
                     Mesh::NewTimeStep on the device with the host one cycle ahead (default when eligible)
@@ -61,17 +62,54 @@ def test_option_does_not_change_a_bit(env):
     assert r.returncode == 0 and "ok" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
 
 
-@pytest.mark.parametrize("env", [{"AKMI_FUSE_C2P": "0"}, {"AKMI_HS2": "0"}, {"AKMI_STREAM_NONBLOCKING": "1"}],
+@pytest.mark.parametrize("env", [{"AKMI_FUSE_C2P": "0"}, {"AKMI_STREAM_NONBLOCKING": "1"}],
                          ids=lambda e: ",".join("%s=%s" % kv for kv in sorted(e.items())))
 def test_hydro_stage_option_does_not_change_a_bit(env):
     """the hydro one-kernel stage: AKMI_FUSE_C2P=0 ConsToPrim as a pass of its own after the ghost fill instead of inside the
-    stage kernel (akmi_hydro_stage_w + second primitive array); AKMI_HS2=0 the one-plane kernel of round 5 (which also
-    excludes the conversion inside it); AKMI_STREAM_NONBLOCKING=1 the C++ host's stream created non-blocking.  The sweep of
+    stage kernel (akmi_hydro_stage_w + second primitive array); AKMI_STREAM_NONBLOCKING=1 the C++ host's stream created
+    non-blocking.  The sweep of
     tools/h3_check.py (shapes, decompositions, DC / PLM, every Riemann solver, isothermal, passive scalars, RK1-3, both hosts)
     stays bitwise equal to the oracle -- as it is with the defaults (test_gpu_parity.py, test_gpu_schemes.py)."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "h3_check.py")], env=dict(os.environ, **env),
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0 and "bad: 0" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
+
+
+HYDRO_SWEEPS_SCRIPT = r"""
+import ctypes, json, sys
+sys.path.insert(0, %r); sys.path.insert(0, %r)
+import parity_util as pu
+CASES = (("sod", 32, 3, 16, dict(cycles=3, cfl=0.3, recon="plm", rsolver="hllc")),      # eight blocks, ideal gas, no scalars
+         ("sod", (36, 28, 20), 3, (18, 14, 10), dict(cycles=3, recon="dc", rsolver="llf", integrator="rk3")))
+out = dict(counters=[])
+for problem, n, dims, mb, kw in CASES:
+    for native in (False, True):
+        r = pu.compare_run(problem, n, dims, mb, native=native, fused=True, keep=True, **kw)
+        assert r["bitwise_equal"] and r["cycles"] == 3 and r["dt"][0] == r["dt"][1], (problem, n, native, r["diffs"], r["dt"])
+        sim = r["sim"]
+        out["counters"].append(list(sim.floor_counters()) if native else sim.phys.counters.cpu().tolist())
+        if not native and "eligible" not in out:         # the first pack, asked through the Python host's binding
+            ph = sim.phys
+            out["eligible"] = int(ph.L.akmi_hydro_stage_w_eligible(ctypes.byref(ph.pack_c), ph.recon_method, ph.rsolver_method))
+print("result " + json.dumps(out))
+""" % (ROOT, os.path.join(ROOT, "tests"))
+
+
+def test_hydro_three_kernel_sweeps_do_not_change_a_bit():
+    """AKMI_HYDRO_ONE_KERNEL=0: the x1 sweep + x2 / x3 marches instead of k_hydro_stage3d2, through both hosts.  The stage
+    then converts no cell inside a sweep kernel: akmi_hydro_stage_w_eligible answers 0 for the pack that is eligible
+    otherwise, the hosts take the usual ConsToPrim path, and the floor counters they report -- where flags read from
+    workspace bytes that hold fluxes would show -- equal those of the same runs without the switch."""
+    import json
+    got = {}
+    for name, env in (("off", {"AKMI_HYDRO_ONE_KERNEL": "0"}), ("default", {})):
+        base = {k: v for k, v in os.environ.items() if k != "AKMI_HYDRO_ONE_KERNEL"}
+        r = subprocess.run([sys.executable, "-c", HYDRO_SWEEPS_SCRIPT], env=dict(base, **env), capture_output=True,
+                           text=True, timeout=900)
+        assert r.returncode == 0 and "result " in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
+        got[name] = json.loads(r.stdout.split("result ", 1)[1])
+    assert got["off"]["eligible"] == 0 and got["default"]["eligible"] == 1, got
+    assert got["off"]["counters"] == got["default"]["counters"], got
 
 
 def test_mhd_one_kernel_stage_is_bit_identical():

@@ -83,7 +83,7 @@ def test_native_cpp_driver_schemes(case):
     assert res["cycles"] == cycles and res["bitwise_equal"], res["diffs"]
 
 
-# hydro DC/PLM in 3-D: the whole stage update is one kernel (k_hydro_stage3d) whose tile shape depends on
+# hydro DC/PLM in 3-D: the whole stage update is one kernel (k_hydro_stage3d2) whose tile shape depends on
 # the block size -- every hydro solver, both reconstructions, blocks that do not fill the tiles, many small
 # blocks, outflow faces, the phased issue of multi-stage integrators
 HYDRO_ONE_KERNEL = [
