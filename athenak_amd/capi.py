@@ -62,6 +62,7 @@ SYMBOLS = [
     "akmi_stage_last_forms", "akmi_mhd_u0_sweeps_eligible", "akmi_sim_stage_forms", "akmi_sim_counters",
     "akmi_mhd_c2p_newdt_lean", "akmi_mhd_prims_fill", "akmi_mhd_c2p_takes_pairs",
     "akmi_amr_check", "akmi_amr_regrid_cc", "akmi_amr_regrid_fc", "akmi_amr_repair_fc",
+    "akmi_ionn_imp_update",
 ]
 
 AMR_METHOD = {"min_max": 0, "slope": 1, "second_deriv": 2}               # AKMI_AMR_* of include/akmi.h

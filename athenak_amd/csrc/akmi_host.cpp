@@ -1768,6 +1768,10 @@ void *akmi_sim_create(const char *deck_text, void *stream) {
     if (s->pin.DoesBlockExist("turb_driving"))
       AKMI_FATAL("<turb_driving> is not on the C++ host's path: run a driven deck with the Python host "
                  "(python -m athenak_amd)");
+    // two-fluid MHD (IonNeutral, src/ion-neutral/) and its ImEx integrators likewise
+    if (s->pin.DoesBlockExist("ion-neutral"))
+      AKMI_FATAL("<ion-neutral> is not on the C++ host's path (--host native): run a two-fluid deck with the Python "
+                 "host (python -m athenak_amd)");
     SrcTermsDeckChecks(&s->pin);
     s->pmesh = std::make_unique<Mesh>(&s->pin, Comm::World().rank, Comm::World().nranks);
     s->pmesh->pmb_pack->AddPhysics(&s->pin);

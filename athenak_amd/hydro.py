@@ -148,6 +148,11 @@ class FluidBase:
         self.turb_driving = pin.DoesBlockExist("turb_driving")
         if self.turb_driving:
             self.fused = False
+        # <ion-neutral>: ImpRKUpdate changes u0 of both fluids between RKUpdate and SendU, and FirstTwoImpRK owns the
+        # copy into the second register, so both fluids take the task-granular chain with nothing folded (see _oop_first)
+        self.ion_neutral = pin.DoesBlockExist("ion-neutral")
+        if self.ion_neutral:
+            self.fused = False
         # physical source terms, hydro.cpp:101-103 / mhd.cpp:137-139: psrc exists iff the fluid's block does
         self.psrc = None
         if pin.DoesBlockExist(blk + "_srcterms"):
@@ -227,7 +232,7 @@ class FluidBase:
         trial update reads u1/b1 before RKUpdate), RK4 (CopyCons updates the second register itself), or the
         update-in-the-sweeps option."""
         return (stage == 1 and not self.fused and not self.use_fofc and not self.turb_driving
-                and pdrive.integrator != "rk4" and _TASK_OOP)
+                and not self.ion_neutral and pdrive.integrator != "rk4" and _TASK_OOP)
 
     @staticmethod
     def _copy_flag(pdrive, stage, phases):

@@ -16,6 +16,9 @@ class Simulation:
         """restart = (header, record reader) of outputs.read_restart(): Mesh::BuildTreeFromRestart
         + the restart constructor of ProblemGenerator (main.cpp:329,355-360)"""
         self.pin = pin
+        if restart is not None and pin.DoesBlockExist("ion-neutral"):
+            raise RuntimeError("### FATAL ERROR -r of a deck with <ion-neutral>: restarting a two-fluid run is not on "
+                               "this path yet")
         self.pmesh = Mesh(pin, my_rank, nranks)
         if restart is not None and self.pmesh.adaptive:
             raise RuntimeError("### FATAL ERROR -r of a deck with <mesh_refinement>/refinement = adaptive: the restart "

@@ -199,6 +199,7 @@ class MeshBlockPack:
         self.pmb = None
         self.phydro = None
         self.pmhd = None
+        self.pionn = None
         self.pturb = None
         self.tl_map = {}
         for name in ("before_timeintegrator", "after_timeintegrator", "before_stagen",
@@ -216,6 +217,8 @@ class MeshBlockPack:
         from .srcterms import srcterms_deck_checks
         turb_deck_checks(pin)
         srcterms_deck_checks(pin)
+        from .ion_neutral import IonNeutral, ionn_deck_checks
+        ionn_deck_checks(pin, getattr(getattr(self, "pmesh", None), "nranks", 1))
         # (1) units, meshblock_pack.cpp:108-112: created iff the block exists
         self.punit = None
         if pin.DoesBlockExist("units"):
@@ -231,10 +234,15 @@ class MeshBlockPack:
         if nphys == 0:
             raise RuntimeError("### FATAL ERROR At least one physics module must be specified "
                                "in input file (<hydro> or <mhd>)")
-        if self.phydro is not None:
-            self.phydro.AssembleHydroTasks(self.tl_map)
-        if self.pmhd is not None:
-            self.pmhd.AssembleMHDTasks(self.tl_map)
+        # (5) ion-neutral (two-fluid) MHD, meshblock_pack.cpp:141-165: its task list replaces those of the two fluids
+        if pin.DoesBlockExist("ion-neutral"):
+            self.pionn = IonNeutral(self, pin)
+            self.pionn.AssembleIonNeutralTasks(self.tl_map)
+        else:
+            if self.phydro is not None:
+                self.phydro.AssembleHydroTasks(self.tl_map)
+            if self.pmhd is not None:
+                self.pmhd.AssembleMHDTasks(self.tl_map)
         # (6) turbulence driver, meshblock_pack.cpp:177-189
         from .turb_driver import add_turbulence_driver
         self.pturb = add_turbulence_driver(self, pin)

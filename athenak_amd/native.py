@@ -42,6 +42,9 @@ class NativeSimulation:
             # said here, before the C++ host parses the deck (it would end the process with its own message)
             raise RuntimeError("### FATAL ERROR <mesh_refinement>/refinement = adaptive runs on the Python host only "
                                "(--host python): the C++ host builds none or static refinement")
+        if pin.DoesBlockExist("ion-neutral"):
+            raise RuntimeError("### FATAL ERROR <ion-neutral> runs on the Python host only (--host python): the C++ host "
+                               "(--host native) has neither the two-fluid task list nor the ImEx integrators")
         self.L = capi.lib()
         stream = capi._stream()
         h = self.L.akmi_sim_create(pin.Dump().encode(), stream)

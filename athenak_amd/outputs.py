@@ -177,6 +177,14 @@ def _outvars(variable, is_mhd, is_ideal=True, turb=False, nscalars=0):
            % (variable, ", ".join(sorted(list(table) + [k for k in _DERIVED if k.startswith(blk + "_")]))))
 
 
+def _out_fluid(pk, variable=None):
+    """(fluid, is_mhd) an output block reads.  With two fluids (<ion-neutral>) the hydro_* variables read the neutral
+    fluid and the mhd_* variables the ion fluid, as the reference's groups do (basetype_output.cpp:196-477)."""
+    if getattr(pk, "pionn", None) is not None and variable is not None and variable.startswith("hydro_"):
+        return pk.phydro, False
+    return (pk.pmhd, True) if pk.pmhd is not None else (pk.phydro, False)
+
+
 class BaseTypeOutput:
     def __init__(self, pin, pm, op):
         self.out_params = op
@@ -185,15 +193,19 @@ class BaseTypeOutput:
         self.outarray = None
         pk = pm.pmb_pack
         if op.file_type not in ("hst", "rst", "pdf"):
-            phys = pk.pmhd if pk.pmhd is not None else pk.phydro
-            self.outvars = _outvars(op.variable, pk.pmhd is not None, phys.peos.eos_data.is_ideal,
-                                    getattr(pk, "pturb", None) is not None, getattr(phys, "nscalars", 0))
+            two = getattr(pk, "pionn", None) is not None
+            if two and op.file_type not in ("tab", "bin"):
+                _fatal("%s output of a run with two fluids is not on this path yet (output block '%s'): tab, bin and hst"
+                       % (op.file_type, op.block_name))
+            phys, is_mhd = _out_fluid(pk, op.variable)
+            self.outvars = _outvars(op.variable, is_mhd, phys.peos.eos_data.is_ideal,
+                                    getattr(pk, "pturb", None) is not None and not two, getattr(phys, "nscalars", 0))
 
     def LoadOutputData(self, pm):
         """basetype_output.cpp:729-862: per-block index ranges (ghost zones, slices) and a
         host copy of the selected components"""
         pk = pm.pmb_pack
-        phys = pk.pmhd if pk.pmhd is not None else pk.phydro
+        phys, _ = _out_fluid(pk, getattr(self.out_params, "variable", None))
         self._load_ranges(pm)
         self._load_outarray(pm, pk, phys)
 
@@ -348,6 +360,14 @@ class HistoryOutput(BaseTypeOutput):
             self.labels += ["1-ME", "2-ME", "3-ME"]
         self.hdata = None
         self.header_written = False
+        # two fluids (<ion-neutral>): <basename>.hydro.hst of the neutrals as well (history.cpp:32-52 builds one
+        # HistoryData per physics module); self.labels / hdata / header_written above are the ion (MHD) fluid's
+        self.neutral = None
+        if getattr(pk, "pionn", None) is not None:
+            nl = ["mass", "1-mom", "2-mom", "3-mom", "tot-E", "1-KE", "2-KE", "3-KE"]
+            if not pk.phydro.peos.eos_data.is_ideal:
+                nl.remove("tot-E")
+            self.neutral = {"labels": nl, "hdata": None, "header_written": False}
         # history.cpp:35-47: the user-defined columns after the physics', or alone with user_hist_only
         self.user_hist = user_hist_of(pin)
         self.physics_hist = not (self.user_hist and op.user_hist_only)
@@ -373,6 +393,12 @@ class HistoryOutput(BaseTypeOutput):
         capi.check(L.akmi_history_sums(C.byref(phys.pack_c), 1 if self.is_mhd else 0, capi._p(phys.u0),
                                        *b, capi._p(out), capi._stream()), "history_sums")
         self.hdata = out
+        if self.neutral is not None:
+            ph = pk.phydro
+            nout = torch.zeros(len(self.neutral["labels"]), dtype=torch.float64, device=ph.u0.device)
+            capi.check(L.akmi_history_sums(C.byref(ph.pack_c), 0, capi._p(ph.u0), None, None, None, capi._p(nout),
+                                           capi._stream()), "history_sums")
+            self.neutral["hdata"] = nout
 
     def WriteOutputFile(self, pm, pin):
         """history.cpp:381-457"""
@@ -388,6 +414,10 @@ class HistoryOutput(BaseTypeOutput):
             if pm.my_rank == 0:
                 fname = "%s.%s.hst" % (op.file_basename, "mhd" if self.is_mhd else "hydro")
                 self.header_written = self._append(fname, pm, self.labels, h, self.header_written)
+                if self.neutral is not None:              # (one rank: ionn_deck_checks)
+                    nt = self.neutral
+                    nt["header_written"] = self._append("%s.hydro.hst" % op.file_basename, pm, nt["labels"],
+                                                        nt["hdata"].cpu().numpy(), nt["header_written"])
         if self.user_hist and pm.my_rank == 0:
             # the sums are already those of the whole mesh on every rank (turb_history_sums)
             self.user_header_written = self._append("%s.user.hst" % op.file_basename, pm, capi.TURB_HIST_LABELS,
@@ -985,6 +1015,12 @@ class Outputs:
                     setattr(op, "slice%d" % q, True)
             if op.file_type == "pdf":
                 _pdf_group_check(name, op.variable)
+            if op.file_type == "pdf" and pin.DoesBlockExist("ion-neutral"):
+                _fatal("pdf output of a run with two fluids (<ion-neutral>) is not on this path yet (output block '%s')"
+                       % name)
+            if op.file_type == "rst" and pin.DoesBlockExist("ion-neutral"):
+                _fatal("rst output with <ion-neutral>: restart files of a two-fluid run (the stiff source terms of the "
+                       "ImEx integrator) are not on this path yet (output block '%s')" % name)
             if op.file_type == "rst" and pin.DoesBlockExist("turb_driving"):
                 _fatal("rst output with <turb_driving>: restarting a driven run (force array and RNG state) is "
                        "not on this path yet (output block '%s')" % name)

@@ -131,6 +131,60 @@ def MHDEigensystemPrimIso(d, v1, b1, b2, b3, y, iso_cs):
     return ev, r
 
 
+def cshock_rhs(init, v, alpha, cis, cns):
+    """RHS of cshock.cpp:44-61: d/dx of (vix, vnx, viy, vny); init = dict(di, dn, vix, vnx, viy, vny, bx, by).
+    Section 4 of the ZEUS-2F workbook; see also Toth, ApJ 425, 171 (1994), eqs 4.2."""
+    di = init["di"]*init["vix"]/v[0]
+    dn = init["dn"]*init["vnx"]/v[1]
+    bx = init["bx"]
+    if bx == 0.0:                 # perpendicular shock
+        by = init["by"]*di/init["di"]
+    else:                         # oblique shock
+        by = init["bx"]*v[2]/v[0]
+    d0 = -alpha*dn*v[0]*(v[0] - v[1])/((v[0]*v[0]) - (cis*cis) - (by*by)/di)
+    d1 = alpha*di*v[1]*(v[0] - v[1])/((v[1]*v[1]) - (cns*cns))
+    d2 = (alpha*dn*v[0]*(v[2] - v[3]) + (bx*by/di)*d0)/((v[0]*v[0]) - (bx*bx)/di)
+    d3 = alpha*di*(v[2] - v[3])/v[1]
+    return [d0, d1, d2, d3]
+
+
+def cshock_profile(init, pert, alpha, cis, cns, npts, xmin, xmax, nfact=10):
+    """cshock.cpp:124-220: RK4 integration of the four ODEs on a mesh nfact times finer than the npts cells of the
+    shock direction, then the mean over the nfact points of each cell.  Returns (soln, shksol): soln (nfact*npts, 4) =
+    (vix, vnx, viy, vny) of the fine mesh, shksol = dict of npts-arrays di, dn, vix, vnx, viy, vny, bx, by."""
+    n = nfact*npts
+    dxshk = (xmax - xmin)/float(n)
+    soln = np.zeros((n, 4))
+    soln[0] = [init["vix"] - pert, init["vnx"], init["viy"], init["vny"]]
+    for q in range(n - 1):
+        s = [float(x) for x in soln[q]]
+        k1 = cshock_rhs(init, s, alpha, cis, cns)
+        k2 = cshock_rhs(init, [s[c] + k1[c]*dxshk/2.0 for c in range(4)], alpha, cis, cns)
+        k3 = cshock_rhs(init, [s[c] + k2[c]*dxshk/2.0 for c in range(4)], alpha, cis, cns)
+        k4 = cshock_rhs(init, [s[c] + k3[c]*dxshk for c in range(4)], alpha, cis, cns)
+        soln[q + 1] = [s[c] + dxshk*(k1[c] + 2.0*(k2[c] + k3[c]) + k4[c])/6.0 for c in range(4)]
+    keys = ("di", "dn", "vix", "vnx", "viy", "vny", "bx", "by")
+    shk = {k: np.zeros(npts) for k in keys}
+    for c in range(npts):
+        acc = dict.fromkeys(keys, 0.0)
+        for m in range(nfact):
+            vix, vnx, viy, vny = (float(x) for x in soln[m + nfact*c])
+            acc["di"] += init["di"]*init["vix"]/vix
+            acc["dn"] += init["dn"]*init["vnx"]/vnx
+            acc["vix"] += vix
+            acc["vnx"] += vnx
+            acc["viy"] += viy
+            acc["vny"] += vny
+            acc["bx"] += init["bx"]
+            if init["bx"] == 0.0:
+                acc["by"] += init["by"]*init["vix"]/vix
+            else:
+                acc["by"] += init["bx"]*viy/vix
+        for k in keys:
+            shk[k][c] = acc[k]/float(nfact)
+    return soln, shk
+
+
 class ProblemGenerator:
     def __init__(self, pin, pmesh, restart=False):
         """restart=True: the restart constructor (src/pgen/pgen.cpp:97-330) -- the dependent
@@ -144,7 +198,7 @@ class ProblemGenerator:
         self.pgen_name = name
         table = {"linear_wave": self.LinearWave, "shock_tube": self.ShockTube,
                  "orszag_tang": self.OrszagTang, "blast": self.UserProblem, "diffusion": self.Diffusion,
-                 "cpaw": self.AlfvenWave, "turb": self.Turb, "rt": self.RayleighTaylor}
+                 "cpaw": self.AlfvenWave, "turb": self.Turb, "rt": self.RayleighTaylor, "cshock": self.CShock}
         # user-defined boundary conditions (pgen.cpp:57-62): enrolled by the problem function
         self.user_bcs = any(b == capi.BC["user"] for b in pmesh.mesh_bcs)
         self.user_bcs_func = None
@@ -531,10 +585,9 @@ class ProblemGenerator:
         self.set_initial_conditions = True
         return self.OutputErrors()
 
-    def OutputErrors(self):
+    def _fluid_errors(self, phys, is_mhd):
+        """the volume-weighted L1 sums and the maximum of one fluid over the active cells (pgen.cpp:697-829)"""
         pm = self.pmy_mesh_
-        phys = self._phys()
-        is_mhd = pm.pmb_pack.pmhd is not None
         ks, js, is_ = self._active()
         a = (slice(None), slice(None), ks, js, is_)
         u0 = phys.u0.cpu().numpy()[a]
@@ -560,6 +613,20 @@ class ProblemGenerator:
                 # with the isothermal EOS the B1 error (slot 4) does not enter L-infty
                 if ideal or q > 0:
                     linf = max(linf, float(e.max()))
+        return l1, linf
+
+    def OutputErrors(self):
+        pm = self.pmy_mesh_
+        pk = pm.pmb_pack
+        if pk.phydro is not None and pk.pmhd is not None:
+            # two fluids, pgen.cpp:697-848: the hydro variables first, then the MHD variables with the three cell-centred
+            # field components; the maximum is the one the second reduction leaves in linfty_err (the MHD fluid's)
+            l1, _ = self._fluid_errors(pk.phydro, False)
+            l1m, linf = self._fluid_errors(pk.pmhd, True)
+            l1 = l1[:pk.phydro.nfluid] + l1m[:pk.pmhd.nfluid] + l1m[-3:]
+        else:
+            is_mhd = pk.pmhd is not None
+            l1, linf = self._fluid_errors(self._phys(), is_mhd)
         l1 = np.array(l1, dtype=np.float64)
         linf_arr = np.array([linf])
         if pm.nranks > 1:
@@ -587,17 +654,20 @@ class ProblemGenerator:
         the RMS-L1 error the reference's regression tests read (testutils.py:273-276)"""
         import os
         pm = self.pmy_mesh_
-        is_mhd = pm.pmb_pack.pmhd is not None
+        pk = pm.pmb_pack
         fname = self.pin.GetString("job", "basename") + "-errs.dat"
         new = not os.path.exists(fname)
         with open(fname, "a") as f:
             if new:
                 f.write("# Nx1  Nx2  Nx3   Ncycle   RMS-L1       L-infty       ")
-                f.write("d_L1          M1_L1         M2_L1         M3_L1         ")
-                if self._phys().peos.eos_data.is_ideal:
-                    f.write("E_L1          ")
-                if is_mhd:
-                    f.write("B1_L1         B2_L1         B3_L1")
+                for phys in (pk.phydro, pk.pmhd):                  # pgen.cpp:872-885: one group per fluid
+                    if phys is None:
+                        continue
+                    f.write("d_L1          M1_L1         M2_L1         M3_L1         ")
+                    if phys.peos.eos_data.is_ideal:
+                        f.write("E_L1          ")
+                    if phys is pk.pmhd:
+                        f.write("B1_L1         B2_L1         B3_L1")
                 f.write("\n")
             mi = pm.mesh_indcs
             f.write("%04d  %04d  %04d  %05d  %e %e" % (mi.nx1, mi.nx2, mi.nx3, pm.ncycle, errs[0], errs[1]))
@@ -660,6 +730,88 @@ class ProblemGenerator:
                 bf[2][m][ks, js, is_] = v3
                 bf[2][m][ks.stop, js, is_] = v3[-1, :, :]
         self._store(w, bf)
+
+    # ---- C-shock of two-fluid MHD, src/pgen/tests/cshock.cpp ----------------------------------
+    def CShock(self, pin, restart):
+        """steady perpendicular or oblique C-shock along x1, x2 or x3: the profile from the host ODE integration, the
+        upstream state as the inflow state of the inner face; the same profile in the second registers when computing
+        errors (the error is small only if the shock stays steady)"""
+        self.pgen_final_func = self.CShockErrors
+        if restart:
+            return
+        pm = self.pmy_mesh_
+        pk = pm.pmb_pack
+        if pk.phydro is None or pk.pmhd is None:
+            raise RuntimeError("### FATAL ERROR C-shock problem requires both Hydro and MHD")
+        if pk.phydro.peos.eos_data.is_ideal:
+            raise RuntimeError("### FATAL ERROR C-shock problem requires isothermal EOS for Hydro")
+        if pk.pmhd.peos.eos_data.is_ideal:
+            raise RuntimeError("### FATAL ERROR C-shock problem requires isothermal EOS for MHD")
+        if getattr(pk, "pionn", None) is None:
+            raise RuntimeError("### FATAL ERROR C-shock problem requires the <ion-neutral> block (its drag_coeff)")
+        shk_dir = pin.GetInteger("problem", "shock_dir")
+        if shk_dir < 1 or shk_dir > 3:
+            raise RuntimeError("### FATAL ERROR shock_dir=%d must be either 1,2, or 3" % shk_dir)
+        g = pin.GetReal
+        init = {k: g("problem", k + "0") for k in ("di", "dn", "vix", "vnx", "viy", "vny", "bx", "by")}
+        pert = pin.GetOrAddReal("problem", "pert", 1.0e-4)
+        alpha = pk.pionn.drag_coeff
+        cns = pk.phydro.peos.eos_data.iso_cs
+        cis = pk.pmhd.peos.eos_data.iso_cs
+        ms, mi, ind = pm.mesh_size, pm.mesh_indcs, pm.mb_indcs
+        npts = (mi.nx1, mi.nx2, mi.nx3)[shk_dir - 1]
+        xmin = (ms.x1min, ms.x2min, ms.x3min)[shk_dir - 1]
+        xmax = (ms.x1max, ms.x2max, ms.x3max)[shk_dir - 1]
+        _, shk = cshock_profile(init, pert, alpha, cis, cns, npts, xmin, xmax)
+        # inflow state of the inner face of the shock direction (cshock.cpp:224-264); momenta and field components
+        # rotate with the direction: x -> shk_dir, y -> the next one
+        ix = shk_dir                               # IM1..IM3 of the shock-normal momentum
+        iy = 1 + shk_dir % 3
+        face = 2*(shk_dir - 1)
+        un_in, ui_in, bi_in = pk.phydro.pbval_u.u_in, pk.pmhd.pbval_u.u_in, pk.pmhd.pbval_b.b_in
+        un_in[IDN, face], ui_in[IDN, face] = init["dn"], init["di"]
+        un_in[ix, face], ui_in[ix, face] = init["dn"]*init["vnx"], init["di"]*init["vix"]
+        un_in[iy, face], ui_in[iy, face] = init["dn"]*init["vny"], init["di"]*init["viy"]
+        bi_in[ix - 1, face], bi_in[iy - 1, face], bi_in[(iy % 3), face] = init["bx"], init["by"], 0.0
+        n3, n2, n1 = ind.ncells
+        nmb = pk.nmb_thispack
+        un = np.zeros((nmb, pk.phydro.nvars, n3, n2, n1))
+        ui = np.zeros((nmb, pk.pmhd.nvars, n3, n2, n1))
+        bf = (np.zeros((nmb, n3, n2, n1 + 1)), np.zeros((nmb, n3, n2 + 1, n1)), np.zeros((nmb, n3 + 1, n2, n1)))
+        ks, js, is_ = self._active()
+        nxb = (ind.nx1, ind.nx2, ind.nx3)[shk_dir - 1]
+        bshape = [1, 1, 1]
+        bshape[3 - shk_dir] = nxb                  # the profile runs along axis (k, j, i)[3 - shk_dir]
+        act = [slice(ks.start, ks.stop), slice(js.start, js.stop), slice(is_.start, is_.stop)]
+        for m in range(nmb):
+            off = pm.lloc_eachmb[pk.gids + m][shk_dir - 1]*nxb
+            p = {k: v[off:off + nxb].reshape(bshape) for k, v in shk.items()}
+            ui[m, IDN][ks, js, is_] = p["di"]
+            un[m, IDN][ks, js, is_] = p["dn"]
+            ui[m, ix][ks, js, is_] = p["di"]*p["vix"]
+            un[m, ix][ks, js, is_] = p["dn"]*p["vnx"]
+            ui[m, iy][ks, js, is_] = p["di"]*p["viy"]
+            un[m, iy][ks, js, is_] = p["dn"]*p["vny"]
+            # faces: the normal component is uniform, the y component is the profile, the third is zero; each array
+            # over its active faces incl. the upper one (the profile does not vary along a transverse axis, and the
+            # face array of the y component is staggered along a transverse axis)
+            for q, val in ((ix - 1, init["bx"]), (iy - 1, p["by"])):
+                sl = list(act)
+                sl[2 - q] = slice(sl[2 - q].start, sl[2 - q].stop + 1)
+                bf[q][m][tuple(sl)] = val
+        to_u1 = not self.set_initial_conditions
+        self._upload_cc(pk.phydro.u1 if to_u1 else pk.phydro.u0, un)
+        self._upload_cc(pk.pmhd.u1 if to_u1 else pk.pmhd.u0, ui)
+        dst = pk.pmhd.b1 if to_u1 else pk.pmhd.b0
+        for q, name in enumerate(("x1f", "x2f", "x3f")):
+            self._upload_cc(getattr(dst, name), bf[q])
+
+    def CShockErrors(self):
+        """cshock.cpp:382-389"""
+        self.set_initial_conditions = False
+        self.CShock(self.pin, False)
+        self.set_initial_conditions = True
+        return self.OutputErrors()
 
     # ---- Gaussian-pulse diffusion tests (src/pgen/tests/diffusion.cpp) --------------------------
     def _diff_gaussian(self, coef, time, x1, x2, x3):

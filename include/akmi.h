@@ -979,6 +979,24 @@ int akmi_amr_regrid_fc(const akmi_pack *old_pack, const akmi_pack *new_pack, con
 int akmi_amr_repair_fc(const akmi_pack *p, const int *repair, double *bx1f, double *bx2f, double *bx3f,
                        void *stream);
 
+/* ---- two-fluid (ion-neutral) MHD, implicit part of the ImEx integrators (akmi_ionn.hip) -----
+ * IonNeutral::ImpRKUpdate, src/ion-neutral/ion-neutral_tasks.cpp:144-292, in ONE launch over every cell of the pack
+ * (ghost zones included).  ui = ion (MHD) u0, (nmb, nvar_i, ncell); un = neutral (hydro) u0, (nmb, nvar_n, ncell);
+ * ru = Driver::impl_src, (nimp_stages, nmb, 8, ncell); ncell = N1*N2*N3 of a MeshBlock.  Only the planes IDN, IM1..IM3
+ * of ui / un are read or written.  istage = estage + 2 = 1 .. nimp_stages+1.  Per cell, in this order:
+ *  (a) for s = 0 .. istage-2, ascending: the eight values += adt[s]*ru[s] (adt: HOST array of istage-1 doubles,
+ *      a_twid[istage-2][s]*dt; may be NULL for istage = 1).  An s with adt[s] == 0.0 exactly is skipped: its slab is
+ *      not read (the reference adds 0.0*ru[s]; the results compare equal, a -0.0 keeps its sign);
+ *  (b) do_solve != 0 (the reference's estage < nexp_stages): the analytic solution of the implicit equations with
+ *      gamma_adt, xi_adt, alpha_adt (the sqrt branch iff alpha_adt > 0);
+ *  (c) do_solve != 0: ru[istage-1] = R(U) of the values of (b), with drag_coeff, ionization_coeff, recombination_coeff.
+ * Every other plane of ui / un and every other slab of ru is left as it is.  A call with nothing to do (do_solve == 0
+ * and all coefficients zero) launches nothing. */
+int akmi_ionn_imp_update(int nmb, long long ncell, int nvar_i, int nvar_n, int nimp_stages, int istage, int do_solve,
+                         const double *adt, double gamma_adt, double xi_adt, double alpha_adt, double drag_coeff,
+                         double ionization_coeff, double recombination_coeff, double *ui, double *un, double *ru,
+                         void *stream);
+
 #ifdef __cplusplus
 }
 #endif
