@@ -189,6 +189,10 @@ class MeshBoundaryValues:
         import os
         self.fold_bcs = (not self.peers and not pm.multilevel and not pm.strictly_periodic
                          and os.environ.get("AKMI_FOLD_BCS", "1") != "0" and hasattr(getattr(self.k, "L", None), "akmi_bvals_cc_local_bcs"))
+        self.BeginStage()
+
+    def BeginStage(self):
+        """the hand-shakes between PackAndSend* and HydroBCs / BFieldBCs live inside one stage"""
         self._u_bcs_done = self._b_bcs_done = False
 
     # ------------------------------------------------------------------------------

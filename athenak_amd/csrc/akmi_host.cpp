@@ -459,7 +459,8 @@ static int ReconFlag(const std::string &r) {
   AKMI_FATAL("reconstruct = '" + r + "' not implemented on this path");
 }
 
-FluidBase::FluidBase(MeshBlockPack *pp, ParameterInput *pin, const std::string &blk) : pmy_pack(pp) {
+FluidBase::FluidBase(MeshBlockPack *pp, ParameterInput *pin, const std::string &blk, int face_shaped_)
+    : pmy_pack(pp), face_shaped(face_shaped_) {
   peos = std::make_unique<EquationOfState>();
   EOS_Data &e = peos->eos_data;
   const std::string eqn_of_state = pin->GetString(blk, "eos");     // hydro.cpp:52-72
@@ -530,8 +531,7 @@ FluidBase::FluidBase(MeshBlockPack *pp, ParameterInput *pin, const std::string &
   pack_c.gamma = e.gamma; pack_c.dfloor = e.dfloor; pack_c.pfloor = e.pfloor;
   pack_c.tfloor = e.tfloor; pack_c.sfloor = e.sfloor; pack_c.sigma_max = e.sigma_max;
   pack_c.iso_cs = e.iso_cs; pack_c.is_ideal = e.is_ideal ? 1 : 0;
-  const size_t n1 = ind.nx1 + 2*ind.ng, n2 = ind.nx2 > 1 ? ind.nx2 + 2*ind.ng : 1,
-               n3 = ind.nx3 > 1 ? ind.nx3 + 2*ind.ng : 1;
+  const auto [n3, n2, n1] = ind.ncells();
   const size_t ncc = static_cast<size_t>(pp->nmb_thispack)*nvars*n3*n2*n1;
   u0.Realloc(ncc); w0.Realloc(ncc); u1.Realloc(ncc);
   counters.Realloc(3); dt3.Realloc(3);
@@ -587,7 +587,7 @@ bool FluidBase::FoldBCs() {
 // same-rank gather of the conserved variables; on meshes with physical boundaries the boundary functions ride along
 void FluidBase::GatherU(Driver *d, int stage) {
   if (want_ghost_c2p_) {
-    // the stage kernel has converted the active cells (akmi_hydro_stage_w): ghost zones of u0 AND of the new primitive array
+    // the stage kernel has converted the active cells (LaunchStage, write_prims): ghost zones of u0 AND of the new primitive array
     // by the same gather + boundary functions, one launch, nothing converted twice (see akmi_hydro_ghost_uw)
     want_ghost_c2p_ = false;
     AKCHK(akmi_hydro_ghost_uw(&pack_c, pmy_pack->pmb->d_nghbr.p, pmy_pack->pmb->d_bcs.p, pmy_pack->pmb->mb_bcs.data(), u0.p,
@@ -628,11 +628,11 @@ void FluidBase::FinishNewDt() {        // hydro_newdt.cpp:121-124
   if (pm->three_d) dtnew = std::min(dtnew, d[2]);
 }
 
-void FluidBase::AddDiffusionFluxes(DvceFaceFld &flx, int fs) {   // hydro_tasks.cpp:183-189, mhd_tasks.cpp:198-203
+void FluidBase::AddDiffusionFluxes() {   // hydro_tasks.cpp:183-189, mhd_tasks.cpp:198-203
   if (has_cond && alpha_iso != 0.0)
-    AKCHK(akmi_heat_fluxes(&pack_c, alpha_iso, w0.p, flx.x1f.p, flx.x2f.p, flx.x3f.p, fs, stream));
+    AKCHK(akmi_heat_fluxes(&pack_c, alpha_iso, w0.p, uflx.x1f.p, uflx.x2f.p, uflx.x3f.p, face_shaped, stream));
   if (has_visc && nu_iso != 0.0)
-    AKCHK(akmi_viscous_fluxes(&pack_c, nu_iso, w0.p, flx.x1f.p, flx.x2f.p, flx.x3f.p, fs, stream));
+    AKCHK(akmi_viscous_fluxes(&pack_c, nu_iso, w0.p, uflx.x1f.p, uflx.x2f.p, uflx.x3f.p, face_shaped, stream));
 }
 void FluidBase::DiffusionNewDt() {     // viscosity.cpp:232-251, conduction.cpp:314-377, resistivity.cpp:291-311
   Mesh *pm = pmy_pack->pmesh;
@@ -675,7 +675,7 @@ static void FaceAlloc(DvceFaceFld &f, size_t nmb, size_t nv, size_t n3, size_t n
 }
 
 namespace hydro {
-Hydro::Hydro(MeshBlockPack *pp, ParameterInput *pin) : FluidBase(pp, pin, "hydro") {
+Hydro::Hydro(MeshBlockPack *pp, ParameterInput *pin) : FluidBase(pp, pin, "hydro", 0) {
   const std::string rs = pin->GetString("hydro", "rsolver");
   // dynamic problems: llf/hlle/hllc/roe; kinematic problems: advect (hydro.cpp:244-278)
   kinematic = pin->GetOrAddString("time", "evolution", "dynamic") == "kinematic";
@@ -687,14 +687,12 @@ Hydro::Hydro(MeshBlockPack *pp, ParameterInput *pin) : FluidBase(pp, pin, "hydro
   else if (rs == "hllc") rsolver_method = AKMI_RS_HLLC;
   else if (rs == "roe") rsolver_method = AKMI_RS_ROE;
   else AKMI_FATAL("<hydro> rsolver = '" + rs + "' not implemented (llf, hlle, hllc, roe)");
-  const RegionIndcs &ind = pp->pmesh->mb_indcs;
-  const size_t n1 = ind.nx1 + 2*ind.ng, n2 = ind.nx2 > 1 ? ind.nx2 + 2*ind.ng : 1,
-               n3 = ind.nx3 > 1 ? ind.nx3 + 2*ind.ng : 1;
+  const auto [n3, n2, n1] = pp->pmesh->mb_indcs.ncells();
   if (fused) ws.Realloc(static_cast<size_t>(akmi_stage_workspace_bytes(&pack_c, 0)));
   else FaceAlloc(uflx, pp->nmb_thispack, nvars, n3, n2, n1, 0);  // hydro.cpp:290-292
   if (StageWritesPrims()) w1.Realloc(w0.n);
 }
-// hydro: ConsToPrim of the active cells inside the stage kernel (akmi_hydro_stage_w; the library's answer carries the A/B
+// hydro: ConsToPrim of the active cells inside the stage kernel (LaunchStage, write_prims; the library's answer carries the A/B
 // switches).  Nothing here changes after construction; RKUpdate adds what the Driver decides (no captured cycle graph)
 bool Hydro::StageWritesPrims() const {
   return fused && !peers() && BcsCommuteWithC2P() && !SrcActive() &&
@@ -724,7 +722,7 @@ void Hydro::AssembleHydroTasks(std::map<std::string, std::shared_ptr<TaskList>> 
 }  // namespace hydro
 
 namespace mhd {
-MHD::MHD(MeshBlockPack *pp, ParameterInput *pin) : FluidBase(pp, pin, "mhd") {
+MHD::MHD(MeshBlockPack *pp, ParameterInput *pin) : FluidBase(pp, pin, "mhd", 1) {
   const std::string rs = pin->GetString("mhd", "rsolver");
   // dynamic problems: llf/hlle/hlld; kinematic problems: advect (mhd.cpp:292-326)
   kinematic = pin->GetOrAddString("time", "evolution", "dynamic") == "kinematic";
@@ -737,8 +735,7 @@ MHD::MHD(MeshBlockPack *pp, ParameterInput *pin) : FluidBase(pp, pin, "mhd") {
   else AKMI_FATAL("<mhd> rsolver = '" + rs + "' not implemented (llf, hlle, hlld)");
   const RegionIndcs &ind = pp->pmesh->mb_indcs;
   const size_t nmb = pp->nmb_thispack;
-  const size_t n1 = ind.nx1 + 2*ind.ng, n2 = ind.nx2 > 1 ? ind.nx2 + 2*ind.ng : 1,
-               n3 = ind.nx3 > 1 ? ind.nx3 + 2*ind.ng : 1;
+  const auto [n3, n2, n1] = ind.ncells();
   bcc0.Realloc(nmb*3*n3*n2*n1);
   bcc_cells = bcc0.p;
   FaceAlloc(b0, nmb, 1, n3, n2, n1, 1);
@@ -1012,7 +1009,7 @@ int Driver::Execute(Mesh *pm, int max_cycles) {            // driver.cpp:380-459
       last_cycle_of_call = (max_cycles >= 0 && n + 1 >= max_cycles) || (nlim >= 0 && pm->ncycle + 1 >= nlim);
       {
         // the host's dt is the one of the cycle BEFORE the one being enqueued: every eligible task takes dt from device
-        // memory (stage_phase_dt / stage_fused_dt); a task that formed beta*pm->dt on the host would silently use the old
+        // memory (FluidBase::LaunchStage passes dt_dev); a task that formed beta*pm->dt on the host would silently use the old
         // value, so the field holds a NaN while the cycle is enqueued -- such a use shows in the first comparison.
         // The guard puts both back, on a throw as well: host assignments only, it may run while the stack unwinds
         struct Restore {
@@ -1086,10 +1083,13 @@ int Driver::Execute(Mesh *pm, int max_cycles) {            // driver.cpp:380-459
 // registers are swapped afterwards (no CopyCons traffic).  The C2P part alone sees swapped pointers
 // already; RK4's second register is updated by CopyCons itself; a captured cycle graph has the
 // pointers baked in -- those keep the folded copy.
+static bool KeepsFoldedCopy(const Driver *d) {      // no stage of this run may trade the registers
+  static const bool off = std::getenv("AKMI_OUT_OF_PLACE") && std::atoi(std::getenv("AKMI_OUT_OF_PLACE")) == 0;   // A/B switch
+  return d->integrator == "rk4" || d->use_graph || off;
+}
 static int CopyFlag(const Driver *d, int stage, int phases) {
   if (stage != 1) return 0;
-  static const bool off = std::getenv("AKMI_OUT_OF_PLACE") && std::atoi(std::getenv("AKMI_OUT_OF_PLACE")) == 0;   // A/B switch
-  if (d->integrator == "rk4" || d->use_graph || off) return 1;
+  if (KeepsFoldedCopy(d)) return 1;
   return (phases & (AKMI_PHASE_SWEEPS | AKMI_PHASE_EMF_CT)) ? 2 : 0;
 }
 static bool MergeC2P() {      // A/B switch, profiles/r03_whatif_merge_c2p.txt
@@ -1097,6 +1097,8 @@ static bool MergeC2P() {      // A/B switch, profiles/r03_whatif_merge_c2p.txt
   return on;
 }
 template <typename T> static void SwapArr(DvceArray<T> &a, DvceArray<T> &b) { std::swap(a.p, b.p); std::swap(a.n, b.n); }
+void FluidBase::SwapU() { SwapArr(u0, u1); u_swapped = !u_swapped; }
+void mhd::MHD::SwapB() { SwapArr(b0.x1f, b1.x1f); SwapArr(b0.x2f, b1.x2f); SwapArr(b0.x3f, b1.x3f); b_swapped = !b_swapped; }
 // Task-granular path, first stage: CopyCons folded into an out-of-place RKUpdate / CT (akmi_rk_update_oop,
 // akmi_mhd_ct_oop), registers swapped afterwards -- no copy traffic.  Not with FOFC (its trial update reads u1/b1
 // before RKUpdate), RK4 (CopyCons updates the second register itself), the update-in-the-sweeps option.
@@ -1136,8 +1138,7 @@ void FluidBase::RestoreRegisters() {
   // u1 (the creation-time u0 buffer) holds a state nothing reads any more: the first stage of the next cycle
   // overwrites it.  Current state -> that buffer, then the names trade places again.
   HIPCHK(hipMemcpyAsync(u1.p, u0.p, u0.n*sizeof(Real), hipMemcpyDeviceToDevice, stream));
-  SwapArr(u0, u1);
-  u_swapped = false;
+  SwapU();
   // akmi_sim_execute returns with every array complete, as it did when each cycle ended in the dt read-back: a
   // caller may read the akmi_sim_array pointers on a stream of its own
   HIPCHK(hipStreamSynchronize(stream));
@@ -1152,17 +1153,15 @@ namespace mhd {
 // its window with the last two cells of the chunk below, which an in-place stage has overwritten in u0 by then.
 // RK4, captured cycle graphs, AKMI_OUT_OF_PLACE=0 and ranks with off-rank neighbours keep the form they had.
 int MHD::U0Copy(const Driver *d, int stage, int phases, int copy) const {
-  if (!u0_sweeps || !(phases & AKMI_PHASE_SWEEPS) || stage < 1 || peers()) return copy;
-  static const bool off = std::getenv("AKMI_OUT_OF_PLACE") && std::atoi(std::getenv("AKMI_OUT_OF_PLACE")) == 0;
-  if (d->integrator == "rk4" || d->use_graph || off) return copy;
+  if (!u0_sweeps || !(phases & AKMI_PHASE_SWEEPS) || stage < 1 || peers() || KeepsFoldedCopy(d)) return copy;
   if (copy == 2) return copy | AKMI_COPY_X3_U0 | lean_flags;
   if (copy == 0 && stage > 1 && stage == d->nexp_stages) return 3 | AKMI_COPY_X3_U0 | lean_flags;
   return copy;
 }
-// stale: what of w0 / bcc0 a lean conversion had left unwritten when the sweeps ran
-void MHD::NoteForms(int stage, int phases, int stale) {
+// prims_stale: what of w0 / bcc0 a lean conversion had left unwritten when the sweeps ran
+void MHD::NoteForms(int stage, int phases) {
   if ((phases & AKMI_PHASE_SWEEPS) && stage >= 1 && stage <= 4)
-    stage_forms[stage - 1] = akmi_stage_last_forms() | (stale ? AKMI_FORM_LEAN_C2P : 0);
+    stage_forms[stage - 1] = akmi_stage_last_forms() | (prims_stale ? AKMI_FORM_LEAN_C2P : 0);
 }
 // What the conversion that ends `stage` may leave unwritten: the arrays the NEXT sweeps do not read, when those sweeps are
 // certain to come within this akmi_sim_execute call -- the next stage of the cycle, or the first stage of the next cycle
@@ -1185,19 +1184,138 @@ static int FormsCover(int copy_arg) {
   return ((copy_arg & AKMI_COPY_X3_U0) && (copy_arg & AKMI_COPY_X12_U0) ? AKMI_DROP_W03 : 0) |
          ((copy_arg & AKMI_COPY_BCC_FACES) ? AKMI_DROP_BCC : 0);
 }
+int MHD::StageCopyArg(const Driver *d, int stage, int phases, int copy) {
+  const int copy_arg = U0Copy(d, stage, phases, copy);
+  if (prims_stale & ~FormsCover(copy_arg)) FillPrims();
+  return copy_arg;
+}
 
 void MHD::RestoreRegisters() {
   FluidBase::RestoreRegisters();
   if (!b_swapped) return;
   DvceArray<Real> *cur[3] = {&b0.x1f, &b0.x2f, &b0.x3f}, *old[3] = {&b1.x1f, &b1.x2f, &b1.x3f};
-  for (int q = 0; q < 3; ++q) {
+  for (int q = 0; q < 3; ++q)
     HIPCHK(hipMemcpyAsync(old[q]->p, cur[q]->p, cur[q]->n*sizeof(Real), hipMemcpyDeviceToDevice, stream));
-    SwapArr(*cur[q], *old[q]);
-  }
-  b_swapped = false;
+  SwapB();
   HIPCHK(hipStreamSynchronize(stream));
 }
 }  // namespace mhd
+
+// ---- the stage call ---------------------------------------------------------------------------------
+// At the ABI a stage call is one thing: the phase entry that takes dt_dev (CallStage), with the phase mask (all three = the
+// whole stage) and dt either folded into beta (dt_dev == nullptr) or read from device memory; hydro's other entry is the
+// whole stage with the second primitive array (tests/test_gpu_stage_entries.py pins that the library's remaining entries
+// are the same call).
+void FluidBase::LaunchStage(Driver *d, int stage, int phases, bool write_prims) {
+  // stage 0 = Driver::InitBoundaryValuesAndPrimitives: only the c2p part may run then
+  if (stage < 1 && phases != AKMI_PHASE_C2P) AKMI_FATAL("stage 0 has no RK weights");
+  const bool rk = stage >= 1;
+  const Real *dtp = rk ? dt_dev : nullptr;
+  const Real g0 = rk ? d->gam0[stage - 1] : 1.0, g1 = rk ? d->gam1[stage - 1] : 0.0;
+  const Real beta = !rk ? 0.0 : (dtp ? d->beta[stage - 1] : d->beta[stage - 1]*pmy_pack->pmesh->dt);
+  const int do_dt = (stage == d->nexp_stages);
+  // (run-ahead cycles: k_mesh_newdt leaves the minima reset for the scan inside the stage kernel)
+  const int do_newdt = (write_prims && do_dt && d->ra_active) ? 2 : do_dt;
+  const int copy_arg = StageCopyArg(d, stage, phases, CopyFlag(d, stage, phases));
+  const int copy = copy_arg & AKMI_COPY_MASK;
+  int wrote = 0;
+  d->ProfMark(stream);
+  CallStage(g0, g1, beta, dtp, copy_arg, do_newdt, phases, write_prims ? &wrote : nullptr);
+  d->ProfMark(stream);
+  NoteForms(stage, phases);
+  // out-of-place stages trade the registers: the first (copy 2: u by the sweeps, b by CT), and the last one of the u0
+  // form (copy 3: u only)
+  if ((copy == 2 || copy == 3) && (phases & AKMI_PHASE_SWEEPS)) SwapU();
+  if (copy == 2 && (phases & AKMI_PHASE_EMF_CT)) SwapB();
+  if (wrote) { SwapArr(w0, w1); w_swapped = !w_swapped; }
+  if (phases & AKMI_PHASE_C2P) { interior_done_ = true; dt_ready_ = do_dt; }
+  if (write_prims) want_ghost_c2p_ = wrote != 0;     // (0: converted in place, the ghost shell takes the usual path)
+}
+
+// ---- task bodies both fluids share ----------------------------------------------------------------------
+TaskStatus FluidBase::SendFlux(Driver *d, int stage) {
+  if (multilevel) {
+    AKCHK(akmi_smr_pack_flux_cc(&pack_c, &psmr->smr_c, nvars, face_shaped, uflx.x1f.p, uflx.x2f.p, uflx.x3f.p,
+                                psmr->buf[1].p, stream));
+    psmr->Post(1, stream);
+  }
+  return TaskStatus::complete;
+}
+TaskStatus FluidBase::RecvFlux(Driver *d, int stage) {
+  if (multilevel) {
+    psmr->Wait(1, stream);
+    AKCHK(akmi_smr_unpack_flux_cc(&pack_c, &psmr->smr_c, nvars, face_shaped, psmr->buf[1].p, uflx.x1f.p, uflx.x2f.p,
+                                  uflx.x3f.p, stream));
+  }
+  return TaskStatus::complete;
+}
+TaskStatus FluidBase::RestrictU(Driver *d, int stage) {
+  if (multilevel) AKCHK(akmi_restrict_cc_masked(&pack_c, nvars, psmr->smr_c.needs_coarse, u0.p, coarse_u0.p, stream));
+  return TaskStatus::complete;
+}
+void FluidBase::SendCC(Driver *d, int stage) {
+  if (multilevel) {
+    if (!psmr->cc_map_on)
+      AKCHK(akmi_smr_pack_cc(&pack_c, &psmr->smr_c, nvars, u0.p, coarse_u0.p, psmr->buf[0].p, stream));
+    psmr->Post(0, stream);
+  } else if (pbval) {
+    pbval->PackAndSendCC(u0.p, stream);
+  } else {
+    GatherU(d, stage);
+  }
+}
+void FluidBase::RecvCC() {
+  if (multilevel) {
+    psmr->Wait(0, stream);
+    if (psmr->cc_map_on) {
+      AKCHK(akmi_smr_cc_copy(&pack_c, nvars, psmr->d_cc_map.p, psmr->cc_np, psmr->cc_tail, u0.p, coarse_u0.p, stream));
+    } else {
+      AKCHK(akmi_smr_unpack_cc(&pack_c, &psmr->smr_c, nvars, psmr->buf[0].p, u0.p, coarse_u0.p, stream));
+      if (psmr->smr_c.direct_same) AKCHK(akmi_bvals_cc_local(&pack_c, nvars, psmr->d_same.p, u0.p, stream));
+    }
+  } else if (pbval) {
+    pbval->RecvAndUnpackCC(u0.p, stream);
+  }
+}
+void FluidBase::FillCoarseCC() {
+  AKCHK(akmi_smr_fill_coarse_cc(&pack_c, &psmr->smr_c, nvars, u0.p, coarse_u0.p, stream));
+}
+void FluidBase::CoarseBCsCC() {                            // HydroBCsCoarse: the BC helper on coarse indices
+  AKCHK(akmi_hydro_bcs_dirs(&cpack_c, nvars, pmy_pack->pmb->d_bcs.p, pmy_pack->pmb->bc_dirs, nullptr, coarse_u0.p, stream));
+}
+bool FluidBase::ProlongateCC(const DvceFaceFld *cb) {
+  if (!pmy_pack->pmesh->prolong_prims) {
+    AKCHK(akmi_smr_prolong_cc(&pack_c, &psmr->smr_c, nvars, coarse_u0.p, u0.p, stream));
+    return false;
+  }
+  if (!coarse_w0.p) coarse_w0.Realloc(coarse_u0.n);        // hydro_tasks.cpp:388-392, mhd_tasks.cpp:539-544
+  AKCHK(akmi_smr_c2p_coarse(&pack_c, &psmr->smr_c, nvars, coarse_u0.p, cb ? cb->x1f.p : nullptr, cb ? cb->x2f.p : nullptr,
+                            cb ? cb->x3f.p : nullptr, coarse_w0.p, stream));
+  AKCHK(akmi_smr_prolong_cc(&pack_c, &psmr->smr_c, nvars, coarse_w0.p, w0.p, stream));
+  return true;
+}
+void FluidBase::PrimToConsFine(const DvceFaceFld *b) {
+  AKCHK(akmi_smr_p2c_fine(&pack_c, &psmr->smr_c, nvars, w0.p, b ? b->x1f.p : nullptr, b ? b->x2f.p : nullptr,
+                          b ? b->x3f.p : nullptr, u0.p, stream));
+}
+void FluidBase::RKUpdateFromFluxes(Driver *d, int stage) {  // hydro_update.cpp:23-83, mhd_update.cpp:24-84
+  const Real g0 = d->gam0[stage - 1], g1 = d->gam1[stage - 1], beta_dt = d->beta[stage - 1]*pmy_pack->pmesh->dt;
+  if (OopFirst(d, stage)) {
+    AKCHK(akmi_rk_update_oop(&pack_c, g0, g1, beta_dt, u0.p, u1.p, uflx.x1f.p, uflx.x2f.p, uflx.x3f.p, face_shaped, stream));
+    SwapU();
+  } else {
+    AKCHK(akmi_rk_update(&pack_c, g0, g1, beta_dt, u0.p, u1.p, uflx.x1f.p, uflx.x2f.p, uflx.x3f.p, face_shaped, stream));
+  }
+}
+TaskStatus FluidBase::FinishTimeStep(Driver *d) {
+  dt_ready_ = false;
+  if (d->capturing) return TaskStatus::complete;   // the Driver reads dt3 after the graph launch
+  if (d->ra_active) { d->EnqueueMeshNewDt(this); return TaskStatus::complete; }
+  FinishNewDt();
+  DiffusionNewDt();
+  SrcNewDt();
+  return TaskStatus::complete;
+}
 
 // ---- task bodies: one C-ABI call each ------------------------------------------------------------
 namespace hydro {
@@ -1215,7 +1333,7 @@ TaskStatus Hydro::Fluxes(Driver *d, int stage) {           // hydro_tasks.cpp:15
   else
     AKCHK(akmi_hydro_fluxes(&pack_c, recon_method, rsolver_method, w0.p, uflx.x1f.p, uflx.x2f.p,
                             uflx.x3f.p, 0, stream));
-  AddDiffusionFluxes(uflx, 0);                              // hydro_tasks.cpp:183-189
+  AddDiffusionFluxes();                            // hydro_tasks.cpp:183-189
   if (use_fofc) {                                           // hydro_tasks.cpp:192-194
     AKCHK(akmi_hydro_fofc(&pack_c, d->gam0[stage - 1], d->gam1[stage - 1],
                           d->beta[stage - 1]*pmy_pack->pmesh->dt, w0.p, u0.p, u1.p, uflx.x1f.p,
@@ -1224,136 +1342,46 @@ TaskStatus Hydro::Fluxes(Driver *d, int stage) {           // hydro_tasks.cpp:15
   return TaskStatus::complete;
 }
 TaskStatus Hydro::RKUpdate(Driver *d, int stage) {         // hydro_update.cpp:23-83
-  Real beta_dt = d->beta[stage - 1]*pmy_pack->pmesh->dt;
-  if (fused && peers()) {
+  if (!fused) {
+    RKUpdateFromFluxes(d, stage);
+  } else if (peers()) {
     // off-rank neighbours: only the sweeps + update here, so that SendU can post the halo messages
     // before the c2p of the active cells is enqueued
-    StagePhase(d, stage, AKMI_PHASE_SWEEPS);
+    LaunchStage(d, stage, AKMI_PHASE_SWEEPS);
   } else if (!d->use_graph && StageWritesPrims()) {
     // the stage kernel converts the cells it finishes (their new state is in its registers) into the second primitive
     // array; ConToPrim then only has the ghost shell left (after the ghost fill): no pass that reads u0 back
-    const int do_dt = (stage == d->nexp_stages);
-    const int copy = CopyFlag(d, stage, AKMI_PHASE_ALL);
-    int wrote = 0;
-    d->ProfMark(stream);
-    AKCHK(akmi_hydro_stage_w(&pack_c, recon_method, rsolver_method, d->gam0[stage - 1], d->gam1[stage - 1],
-                             dt_dev ? d->beta[stage - 1] : beta_dt, dt_dev, copy, w0.p, w1.p, u0.p, u1.p,
-                             do_dt ? (d->ra_active ? 2 : 1) : 0, counters.p, dt3.p, ws.p, stream, &wrote));
-    d->ProfMark(stream);
-    if (copy == 2) { SwapArr(u0, u1); u_swapped = !u_swapped; }
-    if (wrote) { SwapArr(w0, w1); w_swapped = !w_swapped; }
-    interior_done_ = true; dt_ready_ = do_dt;
-    want_ghost_c2p_ = wrote != 0;       // (0: converted in place, the ghost shell takes the usual path)
-  } else if (fused && ((!d->use_graph && MergeC2P()) || SrcActive())) {
+    LaunchStage(d, stage, AKMI_PHASE_ALL, true);
+  } else if ((!d->use_graph && MergeC2P()) || SrcActive()) {
     // no off-rank neighbour: ONE ConsToPrim over all cells after the ghost fill (ConToPrim) instead of c2p of the
     // active cells here + c2p of the ghost shell there (thin slabs): 512 blocks of 32^3 1518 -> 1726 Mcell-updates/s.
     // With source terms always (captured cycles too): they change u0 after this call and before it is converted.
-    StagePhase(d, stage, AKMI_PHASE_SWEEPS);
-  } else if (fused) {
-    int do_dt = (stage == d->nexp_stages);
-    const int copy = CopyFlag(d, stage, AKMI_PHASE_ALL);
-    d->ProfMark(stream);
-    if (dt_dev)
-      AKCHK(akmi_hydro_stage_fused_dt(&pack_c, recon_method, rsolver_method, d->gam0[stage - 1],
-                                      d->gam1[stage - 1], d->beta[stage - 1], dt_dev, copy, w0.p, u0.p,
-                                      u1.p, do_dt, counters.p, dt3.p, ws.p, stream));
-    else
-    AKCHK(akmi_hydro_stage_fused(&pack_c, recon_method, rsolver_method, d->gam0[stage - 1],
-                                 d->gam1[stage - 1], beta_dt, copy, w0.p, u0.p, u1.p, do_dt,
-                                 counters.p, dt3.p, ws.p, stream));
-    d->ProfMark(stream);
-    if (copy == 2) { SwapArr(u0, u1); u_swapped = !u_swapped; }
-    interior_done_ = true; dt_ready_ = do_dt;
-  } else if (OopFirst(d, stage)) {
-    AKCHK(akmi_rk_update_oop(&pack_c, d->gam0[stage - 1], d->gam1[stage - 1], beta_dt, u0.p, u1.p,
-                             uflx.x1f.p, uflx.x2f.p, uflx.x3f.p, 0, stream));
-    SwapArr(u0, u1); u_swapped = !u_swapped;
+    LaunchStage(d, stage, AKMI_PHASE_SWEEPS);
   } else {
-    AKCHK(akmi_rk_update(&pack_c, d->gam0[stage - 1], d->gam1[stage - 1], beta_dt, u0.p, u1.p,
-                         uflx.x1f.p, uflx.x2f.p, uflx.x3f.p, 0, stream));
+    LaunchStage(d, stage, AKMI_PHASE_ALL);
   }
   return TaskStatus::complete;
 }
-void Hydro::StagePhase(Driver *d, int stage, int phases) {
-  // stage 0 = Driver::InitBoundaryValuesAndPrimitives: only the c2p part may run then
-  if (stage < 1 && phases != AKMI_PHASE_C2P) AKMI_FATAL("stage 0 has no RK weights");
-  const Real g0 = stage >= 1 ? d->gam0[stage - 1] : 1.0, g1 = stage >= 1 ? d->gam1[stage - 1] : 0.0;
-  const Real beta_dt = stage >= 1 ? d->beta[stage - 1]*pmy_pack->pmesh->dt : 0.0;
-  const int do_dt = (stage == d->nexp_stages);
-  const int copy = CopyFlag(d, stage, phases);
-  d->ProfMark(stream);
-  if (dt_dev && stage >= 1)
-    AKCHK(akmi_hydro_stage_phase_dt(&pack_c, recon_method, rsolver_method, g0, g1, d->beta[stage - 1], dt_dev, copy, w0.p,
-                                    u0.p, u1.p, do_dt, counters.p, dt3.p, phases, ws.p, stream));
+void Hydro::CallStage(Real g0, Real g1, Real beta, const Real *dtp, int copy_arg, int do_newdt, int phases, int *wrote) {
+  if (wrote)
+    AKCHK(akmi_hydro_stage_w(&pack_c, recon_method, rsolver_method, g0, g1, beta, dtp, copy_arg, w0.p, w1.p, u0.p, u1.p,
+                             do_newdt, counters.p, dt3.p, ws.p, stream, wrote));
   else
-  AKCHK(akmi_hydro_stage_phase(&pack_c, recon_method, rsolver_method, g0, g1, beta_dt, copy, w0.p,
-                               u0.p, u1.p, do_dt, counters.p, dt3.p, phases, ws.p, stream));
-  d->ProfMark(stream);
-  if (copy == 2) { SwapArr(u0, u1); u_swapped = !u_swapped; }
-  if (phases & AKMI_PHASE_C2P) { interior_done_ = true; dt_ready_ = do_dt; }
+    AKCHK(akmi_hydro_stage_phase_dt(&pack_c, recon_method, rsolver_method, g0, g1, beta, dtp, copy_arg, w0.p, u0.p, u1.p,
+                                    do_newdt, counters.p, dt3.p, phases, ws.p, stream));
 }
 TaskStatus Hydro::SendU(Driver *d, int stage) {            // hydro_tasks.cpp:308-320
-  if (multilevel) {
-    if (!psmr->cc_map_on)
-      AKCHK(akmi_smr_pack_cc(&pack_c, &psmr->smr_c, nvars, u0.p, coarse_u0.p, psmr->buf[0].p, stream));
-    psmr->Post(0, stream);
-  } else if (pbval) {
-    pbval->PackAndSendCC(u0.p, stream);
-    // the messages are in flight on the communicator's stream: convert the active cells (they do
-    // not depend on the halo) underneath them
-    if (fused && peers()) StagePhase(d, stage, AKMI_PHASE_C2P);
-  } else {
-    GatherU(d, stage);
-  }
-  return TaskStatus::complete;
-}
-TaskStatus Hydro::RecvU(Driver *d, int stage) {            // hydro_tasks.cpp:327-339
-  if (multilevel) {
-    psmr->Wait(0, stream);
-    if (psmr->cc_map_on) {
-      AKCHK(akmi_smr_cc_copy(&pack_c, nvars, psmr->d_cc_map.p, psmr->cc_np, psmr->cc_tail, u0.p, coarse_u0.p, stream));
-    } else {
-      AKCHK(akmi_smr_unpack_cc(&pack_c, &psmr->smr_c, nvars, psmr->buf[0].p, u0.p, coarse_u0.p, stream));
-      if (psmr->smr_c.direct_same) AKCHK(akmi_bvals_cc_local(&pack_c, nvars, psmr->d_same.p, u0.p, stream));
-    }
-  } else if (pbval) {
-    pbval->RecvAndUnpackCC(u0.p, stream);
-  }
-  return TaskStatus::complete;
-}
-TaskStatus Hydro::RecvFlux(Driver *d, int stage) {         // hydro_tasks.cpp:222-232
-  if (multilevel) {
-    psmr->Wait(1, stream);
-    AKCHK(akmi_smr_unpack_flux_cc(&pack_c, &psmr->smr_c, nvars, 0, psmr->buf[1].p, uflx.x1f.p, uflx.x2f.p,
-                                  uflx.x3f.p, stream));
-  }
-  return TaskStatus::complete;
-}
-TaskStatus Hydro::SendFlux(Driver *d, int stage) {         // hydro_tasks.cpp:206-215
-  if (multilevel) {
-    AKCHK(akmi_smr_pack_flux_cc(&pack_c, &psmr->smr_c, nvars, 0, uflx.x1f.p, uflx.x2f.p, uflx.x3f.p,
-                                psmr->buf[1].p, stream));
-    psmr->Post(1, stream);
-  }
-  return TaskStatus::complete;
-}
-TaskStatus Hydro::RestrictU(Driver *d, int stage) {        // hydro_tasks.cpp:291-300
-  if (multilevel) AKCHK(akmi_restrict_cc_masked(&pack_c, nvars, psmr->smr_c.needs_coarse, u0.p, coarse_u0.p, stream));
+  SendCC(d, stage);
+  // the messages are in flight on the communicator's stream: convert the active cells (they do
+  // not depend on the halo) underneath them
+  if (fused && peers()) LaunchStage(d, stage, AKMI_PHASE_C2P);
   return TaskStatus::complete;
 }
 TaskStatus Hydro::Prolongate(Driver *d, int stage) {       // hydro_tasks.cpp:381-400
   if (!multilevel) return TaskStatus::complete;
-  AKCHK(akmi_smr_fill_coarse_cc(&pack_c, &psmr->smr_c, nvars, u0.p, coarse_u0.p, stream));
-  if (!pmy_pack->pmesh->strictly_periodic)               // HydroBCsCoarse: the BC helper on coarse indices
-    AKCHK(akmi_hydro_bcs_dirs(&cpack_c, nvars, pmy_pack->pmb->d_bcs.p, pmy_pack->pmb->bc_dirs, nullptr, coarse_u0.p, stream));
-  if (pmy_pack->pmesh->prolong_prims) {                   // hydro_tasks.cpp:388-392
-    if (!coarse_w0.p) coarse_w0.Realloc(coarse_u0.n);
-    AKCHK(akmi_smr_c2p_coarse(&pack_c, &psmr->smr_c, nvars, coarse_u0.p, nullptr, nullptr, nullptr, coarse_w0.p, stream));
-    AKCHK(akmi_smr_prolong_cc(&pack_c, &psmr->smr_c, nvars, coarse_w0.p, w0.p, stream));
-    AKCHK(akmi_smr_p2c_fine(&pack_c, &psmr->smr_c, nvars, w0.p, nullptr, nullptr, nullptr, u0.p, stream));
-    return TaskStatus::complete;
-  }
-  AKCHK(akmi_smr_prolong_cc(&pack_c, &psmr->smr_c, nvars, coarse_u0.p, u0.p, stream));
+  FillCoarseCC();
+  if (!pmy_pack->pmesh->strictly_periodic) CoarseBCsCC();
+  if (ProlongateCC(nullptr)) PrimToConsFine(nullptr);
   return TaskStatus::complete;
 }
 TaskStatus Hydro::ApplyPhysicalBCs(Driver *d, int stage) { // hydro_tasks.cpp:357-375
@@ -1363,9 +1391,7 @@ TaskStatus Hydro::ApplyPhysicalBCs(Driver *d, int stage) { // hydro_tasks.cpp:35
   return TaskStatus::complete;
 }
 TaskStatus Hydro::ConToPrim(Driver *d, int stage) {        // hydro_tasks.cpp:404-412
-  const RegionIndcs &ind = pmy_pack->pmesh->mb_indcs;
-  const int n1 = ind.nx1 + 2*ind.ng, n2 = ind.nx2 > 1 ? ind.nx2 + 2*ind.ng : 1,
-            n3 = ind.nx3 > 1 ? ind.nx3 + 2*ind.ng : 1;
+  const auto [n3, n2, n1] = pmy_pack->pmesh->mb_indcs.ncells();
   if (fused && interior_done_) {
     interior_done_ = false;
     if (!shell_done_) AKCHK(akmi_hydro_c2p_shell(&pack_c, u0.p, w0.p, counters.p, stream));
@@ -1394,13 +1420,7 @@ TaskStatus Hydro::NewTimeStep(Driver *d, int stage) {      // hydro_newdt.cpp:30
   if (stage != d->nexp_stages) return TaskStatus::complete;
   if (kinematic) AKCHK(akmi_kinematic_newdt(&pack_c, w0.p, dt3.p, stream));      // hydro_newdt.cpp:55-72
   else if (!dt_ready_) AKCHK(akmi_hydro_newdt(&pack_c, w0.p, dt3.p, stream));
-  dt_ready_ = false;
-  if (d->capturing) return TaskStatus::complete;   // the Driver reads dt3 after the graph launch
-  if (d->ra_active) { d->EnqueueMeshNewDt(this); return TaskStatus::complete; }
-  FinishNewDt();
-  DiffusionNewDt();
-  SrcNewDt();
-  return TaskStatus::complete;
+  return FinishTimeStep(d);
 }
 }  // namespace hydro
 
@@ -1424,7 +1444,7 @@ TaskStatus MHD::Fluxes(Driver *d, int stage) {             // mhd_tasks.cpp:177-
     AKCHK(akmi_mhd_fluxes(&pack_c, recon_method, rsolver_method, w0.p, bcc0.p, b0.x1f.p, b0.x2f.p,
                           b0.x3f.p, uflx.x1f.p, uflx.x2f.p, uflx.x3f.p, e3x1.p, e2x1.p, e1x2.p,
                           e3x2.p, e2x3.p, e1x3.p, stream));
-  AddDiffusionFluxes(uflx, 1);                              // mhd_tasks.cpp:198-203
+  AddDiffusionFluxes();                            // mhd_tasks.cpp:198-203
   if (has_resist && eta_ohm != 0.0 && peos->eos_data.is_ideal)   // mhd_tasks.cpp:204-206
     AKCHK(akmi_resistive_fluxes(&pack_c, eta_ohm, b0.x1f.p, b0.x2f.p, b0.x3f.p, uflx.x1f.p,
                                 uflx.x2f.p, uflx.x3f.p, stream));
@@ -1441,112 +1461,29 @@ TaskStatus MHD::Fluxes(Driver *d, int stage) {             // mhd_tasks.cpp:177-
   return TaskStatus::complete;
 }
 TaskStatus MHD::RKUpdate(Driver *d, int stage) {           // mhd_update.cpp:24-84
-  Real beta_dt = d->beta[stage - 1]*pmy_pack->pmesh->dt;
-  if (fused && peers()) {
-    StagePhase(d, stage, AKMI_PHASE_SWEEPS);
-  } else if (fused && ((!d->use_graph && MergeC2P()) || SrcActive())) {
+  if (!fused) {
+    RKUpdateFromFluxes(d, stage);
+  } else if (peers()) {
+    LaunchStage(d, stage, AKMI_PHASE_SWEEPS);
+  } else if ((!d->use_graph && MergeC2P()) || SrcActive()) {
     // see Hydro::RKUpdate.  Source terms run after this call: CornerE and CT neither read nor write u0, so that gives the
     // bits of applying them between the two phases.
-    StagePhase(d, stage, AKMI_PHASE_SWEEPS | AKMI_PHASE_EMF_CT);
-  } else if (fused) {
-    int do_dt = (stage == d->nexp_stages);
-    const int copy_arg = U0Copy(d, stage, AKMI_PHASE_ALL, CopyFlag(d, stage, AKMI_PHASE_ALL));
-    const int copy = copy_arg & AKMI_COPY_MASK;
-    if (prims_stale & ~FormsCover(copy_arg)) FillPrims();
-    const int stale = prims_stale;
-    d->ProfMark(stream);
-    if (dt_dev)
-      AKCHK(akmi_mhd_stage_fused_dt(&pack_c, recon_method, rsolver_method, d->gam0[stage - 1],
-                                    d->gam1[stage - 1], d->beta[stage - 1], dt_dev, copy_arg, w0.p, bcc0.p,
-                                    u0.p, u1.p, b0.x1f.p, b0.x2f.p, b0.x3f.p, b1.x1f.p, b1.x2f.p, b1.x3f.p,
-                                    do_dt, counters.p, dt3.p, ws.p, stream));
-    else
-    AKCHK(akmi_mhd_stage_fused(&pack_c, recon_method, rsolver_method, d->gam0[stage - 1],
-                               d->gam1[stage - 1], beta_dt, copy_arg, w0.p, bcc0.p, u0.p, u1.p,
-                               b0.x1f.p, b0.x2f.p, b0.x3f.p, b1.x1f.p, b1.x2f.p, b1.x3f.p, do_dt,
-                               counters.p, dt3.p, ws.p, stream));
-    d->ProfMark(stream);
-    NoteForms(stage, AKMI_PHASE_ALL, stale);
-    if (copy == 2) {
-      SwapArr(u0, u1); u_swapped = !u_swapped;
-      SwapArr(b0.x1f, b1.x1f); SwapArr(b0.x2f, b1.x2f); SwapArr(b0.x3f, b1.x3f); b_swapped = !b_swapped;
-    } else if (copy == 3) {
-      SwapArr(u0, u1); u_swapped = !u_swapped;
-    }
-    interior_done_ = true; dt_ready_ = do_dt;
-  } else if (OopFirst(d, stage)) {
-    AKCHK(akmi_rk_update_oop(&pack_c, d->gam0[stage - 1], d->gam1[stage - 1], beta_dt, u0.p, u1.p,
-                             uflx.x1f.p, uflx.x2f.p, uflx.x3f.p, 1, stream));
-    SwapArr(u0, u1); u_swapped = !u_swapped;
+    LaunchStage(d, stage, AKMI_PHASE_SWEEPS | AKMI_PHASE_EMF_CT);
   } else {
-    AKCHK(akmi_rk_update(&pack_c, d->gam0[stage - 1], d->gam1[stage - 1], beta_dt, u0.p, u1.p,
-                         uflx.x1f.p, uflx.x2f.p, uflx.x3f.p, 1, stream));
+    LaunchStage(d, stage, AKMI_PHASE_ALL);
   }
   return TaskStatus::complete;
 }
-void MHD::StagePhase(Driver *d, int stage, int phases) {
-  if (stage < 1 && phases != AKMI_PHASE_C2P) AKMI_FATAL("stage 0 has no RK weights");
-  const Real g0 = stage >= 1 ? d->gam0[stage - 1] : 1.0, g1 = stage >= 1 ? d->gam1[stage - 1] : 0.0;
-  const Real beta_dt = stage >= 1 ? d->beta[stage - 1]*pmy_pack->pmesh->dt : 0.0;
-  const int do_dt = (stage == d->nexp_stages);
-  const int copy_arg = U0Copy(d, stage, phases, CopyFlag(d, stage, phases));
-  const int copy = copy_arg & AKMI_COPY_MASK;
-  if (prims_stale & ~FormsCover(copy_arg)) FillPrims();
-  const int stale = prims_stale;
-  d->ProfMark(stream);
-  if (dt_dev && stage >= 1)
-    AKCHK(akmi_mhd_stage_phase_dt(&pack_c, recon_method, rsolver_method, g0, g1, d->beta[stage - 1], dt_dev, copy_arg, w0.p,
-                                  bcc0.p, u0.p, u1.p, b0.x1f.p, b0.x2f.p, b0.x3f.p, b1.x1f.p, b1.x2f.p,
-                                  b1.x3f.p, do_dt, counters.p, dt3.p, phases, ws.p, stream));
-  else
-  AKCHK(akmi_mhd_stage_phase(&pack_c, recon_method, rsolver_method, g0, g1, beta_dt, copy_arg, w0.p,
-                             bcc0.p, u0.p, u1.p, b0.x1f.p, b0.x2f.p, b0.x3f.p, b1.x1f.p, b1.x2f.p,
-                             b1.x3f.p, do_dt, counters.p, dt3.p, phases, ws.p, stream));
-  d->ProfMark(stream);
-  NoteForms(stage, phases, stale);
-  if (copy == 3 && (phases & AKMI_PHASE_SWEEPS)) { SwapArr(u0, u1); u_swapped = !u_swapped; }
-  if (copy == 2) {
-    if (phases & AKMI_PHASE_SWEEPS) { SwapArr(u0, u1); u_swapped = !u_swapped; }
-    if (phases & AKMI_PHASE_EMF_CT) {
-      SwapArr(b0.x1f, b1.x1f); SwapArr(b0.x2f, b1.x2f); SwapArr(b0.x3f, b1.x3f); b_swapped = !b_swapped;
-    }
-  }
-  if (phases & AKMI_PHASE_C2P) { interior_done_ = true; dt_ready_ = do_dt; }
+void MHD::CallStage(Real g0, Real g1, Real beta, const Real *dtp, int copy_arg, int do_newdt, int phases, int *) {
+  AKCHK(akmi_mhd_stage_phase_dt(&pack_c, recon_method, rsolver_method, g0, g1, beta, dtp, copy_arg, w0.p, bcc0.p, u0.p, u1.p,
+                                b0.x1f.p, b0.x2f.p, b0.x3f.p, b1.x1f.p, b1.x2f.p, b1.x3f.p, do_newdt, counters.p, dt3.p,
+                                phases, ws.p, stream));
 }
 // Off-rank neighbours and the fused stage: sweeps+update -> pack+send U -> CornerE+CT -> pack+send B
 // -> c2p of the active cells (+dt) -> wait/unpack U, B -> BCs -> c2p of the ghost shell: the reference's
 // task order (mhd_tasks.cpp:48-75) with the transfers underneath the kernels that do not need them
-TaskStatus MHD::SendU(Driver *d, int stage) {
-  if (multilevel) {
-    if (!psmr->cc_map_on)
-      AKCHK(akmi_smr_pack_cc(&pack_c, &psmr->smr_c, nvars, u0.p, coarse_u0.p, psmr->buf[0].p, stream));
-    psmr->Post(0, stream);
-  } else if (pbval)
-    pbval->PackAndSendCC(u0.p, stream);
-  else
-    GatherU(d, stage);
-  return TaskStatus::complete;
-}
 TaskStatus MHD::RecvU(Driver *d, int stage) {
-  if (multilevel) {
-    psmr->Wait(0, stream);
-    if (psmr->cc_map_on) {
-      AKCHK(akmi_smr_cc_copy(&pack_c, nvars, psmr->d_cc_map.p, psmr->cc_np, psmr->cc_tail, u0.p, coarse_u0.p, stream));
-    } else {
-      AKCHK(akmi_smr_unpack_cc(&pack_c, &psmr->smr_c, nvars, psmr->buf[0].p, u0.p, coarse_u0.p, stream));
-      if (psmr->smr_c.direct_same) AKCHK(akmi_bvals_cc_local(&pack_c, nvars, psmr->d_same.p, u0.p, stream));
-    }
-  } else if (pbval && !(fused && peers())) {
-    pbval->RecvAndUnpackCC(u0.p, stream);                                     // else: in RecvB
-  }
-  return TaskStatus::complete;
-}
-TaskStatus MHD::RecvFlux(Driver *d, int stage) {           // mhd_tasks.cpp:240-250
-  if (multilevel) {
-    psmr->Wait(1, stream);
-    AKCHK(akmi_smr_unpack_flux_cc(&pack_c, &psmr->smr_c, nvars, 1, psmr->buf[1].p, uflx.x1f.p, uflx.x2f.p,
-                                  uflx.x3f.p, stream));
-  }
+  if (!(fused && peers())) RecvCC();                       // else: in RecvB
   return TaskStatus::complete;
 }
 TaskStatus MHD::RecvE(Driver *d, int stage) {              // mhd_tasks.cpp:410-417
@@ -1570,20 +1507,8 @@ TaskStatus MHD::RecvB(Driver *d, int stage) {
     return TaskStatus::complete;
   }
   if (!pbval) return TaskStatus::complete;
-  if (fused && peers()) pbval->RecvAndUnpackCC(u0.p, stream);
+  if (fused && peers()) RecvCC();
   pbval->RecvAndUnpackFC(b0, stream);
-  return TaskStatus::complete;
-}
-TaskStatus MHD::SendFlux(Driver *d, int stage) {           // mhd_tasks.cpp:225-233
-  if (multilevel) {
-    AKCHK(akmi_smr_pack_flux_cc(&pack_c, &psmr->smr_c, nvars, 1, uflx.x1f.p, uflx.x2f.p, uflx.x3f.p,
-                                psmr->buf[1].p, stream));
-    psmr->Post(1, stream);
-  }
-  return TaskStatus::complete;
-}
-TaskStatus MHD::RestrictU(Driver *d, int stage) {          // mhd_tasks.cpp:315-322
-  if (multilevel) AKCHK(akmi_restrict_cc_masked(&pack_c, nvars, psmr->smr_c.needs_coarse, u0.p, coarse_u0.p, stream));
   return TaskStatus::complete;
 }
 TaskStatus MHD::RestrictB(Driver *d, int stage) {          // mhd_tasks.cpp:691-697
@@ -1606,27 +1531,18 @@ TaskStatus MHD::SendE(Driver *d, int stage) {
 TaskStatus MHD::Prolongate(Driver *d, int stage) {         // mhd_tasks.cpp:527-552
   if (!multilevel) return TaskStatus::complete;
   const akmi_smr *t = &psmr->smr_c;
-  AKCHK(akmi_smr_fill_coarse_cc(&pack_c, t, nvars, u0.p, coarse_u0.p, stream));
+  FillCoarseCC();
   AKCHK(akmi_smr_fill_coarse_fc(&pack_c, t, b0.x1f.p, b0.x2f.p, b0.x3f.p, coarse_b0.x1f.p, coarse_b0.x2f.p,
                                 coarse_b0.x3f.p, stream));
   if (!pmy_pack->pmesh->strictly_periodic) {
-    AKCHK(akmi_hydro_bcs_dirs(&cpack_c, nvars, pmy_pack->pmb->d_bcs.p, pmy_pack->pmb->bc_dirs, nullptr, coarse_u0.p, stream));
+    CoarseBCsCC();
     AKCHK(akmi_bfield_bcs_dirs(&cpack_c, pmy_pack->pmb->d_bcs.p, pmy_pack->pmb->bc_dirs, nullptr, coarse_b0.x1f.p, coarse_b0.x2f.p, coarse_b0.x3f.p,
                           stream));
   }
-  if (pmy_pack->pmesh->prolong_prims) {                   // mhd_tasks.cpp:539-544
-    if (!coarse_w0.p) coarse_w0.Realloc(coarse_u0.n);
-    AKCHK(akmi_smr_c2p_coarse(&pack_c, t, nvars, coarse_u0.p, coarse_b0.x1f.p, coarse_b0.x2f.p, coarse_b0.x3f.p,
-                              coarse_w0.p, stream));
-    AKCHK(akmi_smr_prolong_cc(&pack_c, t, nvars, coarse_w0.p, w0.p, stream));
-    AKCHK(akmi_smr_prolong_fc(&pack_c, t, coarse_b0.x1f.p, coarse_b0.x2f.p, coarse_b0.x3f.p, b0.x1f.p, b0.x2f.p,
-                              b0.x3f.p, stream));
-    AKCHK(akmi_smr_p2c_fine(&pack_c, t, nvars, w0.p, b0.x1f.p, b0.x2f.p, b0.x3f.p, u0.p, stream));
-    return TaskStatus::complete;
-  }
-  AKCHK(akmi_smr_prolong_cc(&pack_c, t, nvars, coarse_u0.p, u0.p, stream));
+  const bool prims = ProlongateCC(&coarse_b0);
   AKCHK(akmi_smr_prolong_fc(&pack_c, t, coarse_b0.x1f.p, coarse_b0.x2f.p, coarse_b0.x3f.p, b0.x1f.p, b0.x2f.p,
                             b0.x3f.p, stream));
+  if (prims) PrimToConsFine(&b0);
   return TaskStatus::complete;
 }
 TaskStatus MHD::EField(Driver *d, int stage) {             // mhd_corner_e.cpp:26-417
@@ -1643,12 +1559,12 @@ TaskStatus MHD::EField(Driver *d, int stage) {             // mhd_corner_e.cpp:2
   return TaskStatus::complete;
 }
 TaskStatus MHD::CT(Driver *d, int stage) {                 // mhd_ct.cpp:23-80
-  if (fused && peers()) StagePhase(d, stage, AKMI_PHASE_EMF_CT);
+  if (fused && peers()) LaunchStage(d, stage, AKMI_PHASE_EMF_CT);
   if (!fused && OopFirst(d, stage)) {
     AKCHK(akmi_mhd_ct_oop(&pack_c, d->gam0[stage - 1], d->gam1[stage - 1],
                           d->beta[stage - 1]*pmy_pack->pmesh->dt, efld.x1e.p, efld.x2e.p, efld.x3e.p,
                           b0.x1f.p, b0.x2f.p, b0.x3f.p, b1.x1f.p, b1.x2f.p, b1.x3f.p, stream));
-    SwapArr(b0.x1f, b1.x1f); SwapArr(b0.x2f, b1.x2f); SwapArr(b0.x3f, b1.x3f); b_swapped = !b_swapped;
+    SwapB();
   } else if (!fused) {
     AKCHK(akmi_mhd_ct(&pack_c, d->gam0[stage - 1], d->gam1[stage - 1],
                       d->beta[stage - 1]*pmy_pack->pmesh->dt, efld.x1e.p, efld.x2e.p, efld.x3e.p,
@@ -1668,7 +1584,7 @@ TaskStatus MHD::SendB(Driver *d, int stage) {
     psmr->Post(2, stream);
   } else if (pbval) {
     pbval->PackAndSendFC(b0, stream);
-    if (fused && peers()) StagePhase(d, stage, AKMI_PHASE_C2P);
+    if (fused && peers()) LaunchStage(d, stage, AKMI_PHASE_C2P);
   } else if (FoldBCs() && !pmy_pack->pmesh->strictly_periodic) {
     AKCHK(akmi_bvals_fc_local_bcs(&pack_c, pmy_pack->pmb->d_nghbr.p, pmy_pack->pmb->d_bcs.p, nullptr, b0.x1f.p, b0.x2f.p,
                                   b0.x3f.p, stream));
@@ -1688,9 +1604,7 @@ TaskStatus MHD::ApplyPhysicalBCs(Driver *d, int stage) {   // mhd_tasks.cpp:501-
   return TaskStatus::complete;
 }
 TaskStatus MHD::ConToPrim(Driver *d, int stage) {
-  const RegionIndcs &ind = pmy_pack->pmesh->mb_indcs;
-  const int n1 = ind.nx1 + 2*ind.ng, n2 = ind.nx2 > 1 ? ind.nx2 + 2*ind.ng : 1,
-            n3 = ind.nx3 > 1 ? ind.nx3 + 2*ind.ng : 1;
+  const auto [n3, n2, n1] = pmy_pack->pmesh->mb_indcs.ncells();
   if (fused && interior_done_) {
     interior_done_ = false;
     FillPrims();                       // (this path never converts lean: nothing to do unless the path changed mid-run)
@@ -1721,13 +1635,7 @@ TaskStatus MHD::NewTimeStep(Driver *d, int stage) {        // mhd_newdt.cpp:31-1
   if (stage != d->nexp_stages) return TaskStatus::complete;
   if (kinematic) AKCHK(akmi_kinematic_newdt(&pack_c, w0.p, dt3.p, stream));      // mhd_newdt.cpp:56-73
   else if (!dt_ready_) { FillPrims(); AKCHK(akmi_mhd_newdt(&pack_c, w0.p, bcc0.p, dt3.p, stream)); }
-  dt_ready_ = false;
-  if (d->capturing) return TaskStatus::complete;   // the Driver reads dt3 after the graph launch
-  if (d->ra_active) { d->EnqueueMeshNewDt(this); return TaskStatus::complete; }
-  FinishNewDt();
-  DiffusionNewDt();
-  SrcNewDt();
-  return TaskStatus::complete;
+  return FinishTimeStep(d);
 }
 }  // namespace mhd
 
@@ -1818,7 +1726,7 @@ int akmi_sim_execute(void *h, int max_cycles) {
 }
 
 /* live timing of the fused-stage launch group: on != 0 starts recording a HIP event pair on the launch stream
- * around every akmi_*_stage_fused / akmi_*_stage_phase call; akmi_sim_profile_read waits for the recorded
+ * around every stage call (FluidBase::LaunchStage); akmi_sim_profile_read waits for the recorded
  * events, returns their summed duration and count, and clears the record */
 /* host-only: the C++ host's reading of the source-term block of `fluid` ("hydro" | "mhd") */
 int akmi_srcterms_from_deck(const char *deck_text, const char *fluid, akmi_srcterms *out) {

@@ -142,6 +142,10 @@ struct RegionSize {     // mesh.hpp:25-29
 };
 struct RegionIndcs {    // mesh.hpp:35-41
   int ng, nx1, nx2, nx3, is, ie, js, je, ks, ke;
+  // cells of one block with its ghost zones, {n3, n2, n1}: a direction that is not active has one
+  std::array<int, 3> ncells() const {
+    return {nx3 > 1 ? nx3 + 2*ng : 1, nx2 > 1 ? nx2 + 2*ng : 1, nx1 + 2*ng};
+  }
 };
 
 template <typename T>
@@ -390,14 +394,16 @@ struct EquationOfState { EOS_Data eos_data; };
 
 class FluidBase {
  public:
-  FluidBase(MeshBlockPack *pp, ParameterInput *pin, const std::string &blk);
+  FluidBase(MeshBlockPack *pp, ParameterInput *pin, const std::string &blk, int face_shaped);
   virtual ~FluidBase() = default;
   MeshBlockPack *pmy_pack;
+  const int face_shaped;                // the flux arrays carry one face more than cells along their direction: 0 hydro, 1 MHD
   std::unique_ptr<EquationOfState> peos;
   int recon_method, rsolver_method;
   bool fused;
   akmi_pack pack_c;
   DvceArray<Real> u0, w0, u1;
+  DvceFaceFld uflx;                     // task-granular path (hydro.cpp:290-292, mhd.cpp:341-343)
   DvceArray<Real> w1;                   // second primitive array: akmi_hydro_stage_w writes the new primitives of the active cells
                                         // there while neighbours still read w0; then the two trade places.  Allocated by Hydro's
                                         // constructor when the stage may take that path (Hydro::StageWritesPrims); a 3-D deck with
@@ -442,14 +448,40 @@ class FluidBase {
   // the out-of-place first stage trades the two registers; true while u0 / b0 live in the buffers that were
   // u1 / b1 when the arrays were created (akmi_sim_execute copies back so that akmi_sim_array pointers stay valid)
   bool u_swapped = false, b_swapped = false;
+  void SwapU();
+  virtual void SwapB() {}               // (hydro has no face field)
   virtual void RestoreRegisters();
+  // "run the parts `phases` of stage `stage`": the ONE place that forms the arguments of a stage call (weights, dt in
+  // device memory or not, copy flag, do_newdt), brackets it for akmi_sim_profile, trades the registers afterwards and
+  // leaves the hand-shake flags for SendU / ConToPrim / NewTimeStep.  write_prims: akmi_hydro_stage_w
+  void LaunchStage(Driver *d, int stage, int phases, bool write_prims = false);
+  // task bodies both fluids share (face_shaped and nothing else tells their calls apart); Hydro::X / MHD::X name them
+  TaskStatus SendFlux(Driver *d, int stage);       // hydro_tasks.cpp:206-215, mhd_tasks.cpp:225-233
+  TaskStatus RecvFlux(Driver *d, int stage);       // hydro_tasks.cpp:222-232, mhd_tasks.cpp:240-250
+  TaskStatus RestrictU(Driver *d, int stage);      // hydro_tasks.cpp:291-300, mhd_tasks.cpp:315-322
   // forms (AKMI_FORM_* of include/akmi.h) the stages of the last cycle took, by stage - 1; -1: no such stage has run
   int stage_forms[4] = {-1, -1, -1, -1};
  public:
   void FinishNewDtPublic() { FinishNewDt(); }
  protected:
+  // the library's stage entry of this fluid, with the arrays only it has; wrote != nullptr: akmi_hydro_stage_w
+  virtual void CallStage(Real g0, Real g1, Real beta, const Real *dtp, int copy_arg, int do_newdt, int phases,
+                         int *wrote) = 0;
+  // MHD's extras around the call: the u0 / lean forms added to the copy flag (+ FillPrims where the call reads what a
+  // lean conversion left unwritten), and the record of the forms the sweeps took
+  virtual int StageCopyArg(const Driver *d, int stage, int phases, int copy) { return copy; }
+  virtual void NoteForms(int stage, int phases) {}
+  // the cell-centred parts of the tasks of the same names
+  void SendCC(Driver *d, int stage);
+  void RecvCC();
+  void FillCoarseCC();                             // Prolongate: coarse buffer from the fine cells,
+  void CoarseBCsCC();                              //   its physical boundaries (HydroBCsCoarse),
+  bool ProlongateCC(const DvceFaceFld *coarse_b);  //   conserved or primitive (returns true) variables into the fine ghosts,
+  void PrimToConsFine(const DvceFaceFld *b);       //   and back to conserved ones
+  void RKUpdateFromFluxes(Driver *d, int stage);   // akmi_rk_update[_oop] on the flux arrays
+  TaskStatus FinishTimeStep(Driver *d);            // NewTimeStep once dt3 holds (or will hold) the CFL minima
   void FinishNewDt();
-  void AddDiffusionFluxes(DvceFaceFld &flx, int face_shaped);   // hydro_tasks.cpp:183-189
+  void AddDiffusionFluxes();                                    // hydro_tasks.cpp:183-189
   void DiffusionNewDt();                                        // hydro_newdt.cpp:128-133
   bool interior_done_ = false, dt_ready_ = false;
   // single-rank uniform meshes: the gather of SendU / SendB applies the physical boundary functions as well
@@ -474,26 +506,24 @@ namespace hydro {
 class Hydro : public FluidBase {    // hydro.hpp:73-154
  public:
   Hydro(MeshBlockPack *pp, ParameterInput *pin);
-  DvceFaceFld uflx;
   bool StageWritesPrims() const;   // what of RKUpdate's choice of akmi_hydro_stage_w is known at construction
   void AssembleHydroTasks(std::map<std::string, std::shared_ptr<TaskList>> tl);
-  void StagePhase(Driver *d, int stage, int phases);   // akmi_hydro_stage_phase
   TaskStatus InitRecv(Driver *d, int stage) { return TaskStatus::complete; }
   TaskStatus CopyCons(Driver *d, int stage);
   TaskStatus Fluxes(Driver *d, int stage);
-  TaskStatus SendFlux(Driver *d, int stage);
-  TaskStatus RecvFlux(Driver *d, int stage);
   TaskStatus RKUpdate(Driver *d, int stage);
   TaskStatus HydroSrcTerms(Driver *d, int stage) { return ApplySrcTerms(d, stage); }   // hydro_tasks.cpp:237-241
-  TaskStatus RestrictU(Driver *d, int stage);
   TaskStatus SendU(Driver *d, int stage);
-  TaskStatus RecvU(Driver *d, int stage);
+  TaskStatus RecvU(Driver *d, int stage) { RecvCC(); return TaskStatus::complete; }     // hydro_tasks.cpp:327-339
   TaskStatus Prolongate(Driver *d, int stage);
   TaskStatus ApplyPhysicalBCs(Driver *d, int stage);
   TaskStatus ConToPrim(Driver *d, int stage);
   TaskStatus NewTimeStep(Driver *d, int stage);
   TaskStatus ClearSend(Driver *d, int stage) { return TaskStatus::complete; }
   TaskStatus ClearRecv(Driver *d, int stage) { return TaskStatus::complete; }
+ protected:
+  void CallStage(Real g0, Real g1, Real beta, const Real *dtp, int copy_arg, int do_newdt, int phases,
+                 int *wrote) override;
 };
 }  // namespace hydro
 
@@ -502,17 +532,16 @@ class MHD : public FluidBase {      // mhd.hpp:93-199
  public:
   MHD(MeshBlockPack *pp, ParameterInput *pin);
   DvceArray<Real> bcc0;
-  DvceFaceFld b0, b1, uflx, coarse_b0;
+  DvceFaceFld b0, b1, coarse_b0;
   DvceEdgeFld efld;
   DvceArray<Real> e3x1, e2x1, e1x2, e3x2, e2x3, e1x3;
   void AssembleMHDTasks(std::map<std::string, std::shared_ptr<TaskList>> tl);
-  void StagePhase(Driver *d, int stage, int phases);   // akmi_mhd_stage_phase
+  void SwapB() override;
   void RestoreRegisters() override;
   // <mhd>/u0_sweeps = auto | false: the sweeps read what u0 holds from u0 instead of its copy in w0 wherever the stage
   // does not write the array it reads (U0Copy, akmi_host.cpp); false keeps every stage in the form it had before
   bool u0_sweeps = false;
   int U0Copy(const Driver *d, int stage, int phases, int copy) const;
-  void NoteForms(int stage, int phases, int stale);
   // <mhd>/lean_prims = auto | true | false.  lean_flags: what U0Copy adds beside AKMI_COPY_X3_U0 (AKMI_COPY_X12_U0,
   // AKMI_COPY_BCC_FACES); lean_drop: the arrays (AKMI_DROP_*) a stage with those flags does not read, which ConToPrim
   // leaves unwritten when the next sweeps are certain to run in the same akmi_sim_execute call and to take the flags
@@ -525,12 +554,9 @@ class MHD : public FluidBase {      // mhd.hpp:93-199
   TaskStatus InitRecv(Driver *d, int stage) { return TaskStatus::complete; }
   TaskStatus CopyCons(Driver *d, int stage);
   TaskStatus Fluxes(Driver *d, int stage);
-  TaskStatus SendFlux(Driver *d, int stage);
-  TaskStatus RecvFlux(Driver *d, int stage);
   TaskStatus RKUpdate(Driver *d, int stage);
   TaskStatus MHDSrcTerms(Driver *d, int stage) { return ApplySrcTerms(d, stage); }     // mhd_tasks.cpp:254-258
-  TaskStatus RestrictU(Driver *d, int stage);
-  TaskStatus SendU(Driver *d, int stage);
+  TaskStatus SendU(Driver *d, int stage) { SendCC(d, stage); return TaskStatus::complete; }
   TaskStatus RecvU(Driver *d, int stage);
   TaskStatus EField(Driver *d, int stage);
   TaskStatus SendE(Driver *d, int stage);      // identity on uniform meshes, EMF correction with levels
@@ -545,6 +571,11 @@ class MHD : public FluidBase {      // mhd.hpp:93-199
   TaskStatus NewTimeStep(Driver *d, int stage);
   TaskStatus ClearSend(Driver *d, int stage) { return TaskStatus::complete; }
   TaskStatus ClearRecv(Driver *d, int stage) { return TaskStatus::complete; }
+ protected:
+  void CallStage(Real g0, Real g1, Real beta, const Real *dtp, int copy_arg, int do_newdt, int phases,
+                 int *wrote) override;
+  int StageCopyArg(const Driver *d, int stage, int phases, int copy) override;
+  void NoteForms(int stage, int phases) override;
 };
 }  // namespace mhd
 
@@ -564,11 +595,11 @@ class Driver {          // driver.cpp
   // One cycle (all stages) captured into a hipGraph and replayed: on small packs a cycle is a chain of
   // dependent launches of a few microseconds each and the host cannot issue them fast enough.  Nothing
   // in the captured calls changes from cycle to cycle except dt, which the kernels read from d_dt
-  // (akmi_*_stage_fused_dt).  Eligible: fused stage, one rank, uniform mesh.  <time>/cycle_graph = auto
+  // (akmi_*_stage_phase_dt).  Eligible: fused stage, one rank, uniform mesh.  <time>/cycle_graph = auto
   // (1-D packs) | true | false; AKMI_CYCLE_GRAPH=0/1 overrides.
   bool use_graph = false, capturing = false;
-  // akmi_sim_profile: live timing of the fused-stage launch group -- a HIP event pair on the launch stream
-  // around every akmi_*_stage_fused / akmi_*_stage_phase call of the cycles that follow (bench.py's roofline entry)
+  // akmi_sim_profile: live timing of the fused-stage launch group -- a HIP event pair on the launch stream around
+  // every stage call (FluidBase::LaunchStage) and whole-pack ConToPrim of the cycles that follow (bench.py's roofline entry)
   bool prof_on = false;
   std::vector<HipHandle<hipEvent_t>> prof_ev;
   size_t prof_used = 0;

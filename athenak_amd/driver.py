@@ -162,18 +162,10 @@ class Driver:
 
     @staticmethod
     def _begin_stage(pm):
-        """the hand-shake flags between SendU / SendB and ApplyPhysicalBCs / ConToPrim live inside one stage: none may be
-        left standing for the next one (a task list that drops the consumer)"""
-        pk = pm.pmb_pack
-        for ph in (getattr(pk, "phydro", None), getattr(pk, "pmhd", None)):
-            if ph is None:
-                continue
-            ph._dt3_reset = False
-            ph._want_ghost_c2p = False
-            ph._shell_done = False
-            for bv in (getattr(ph, "pbval_u", None), getattr(ph, "pbval_b", None)):
-                if bv is not None and hasattr(bv, "_u_bcs_done"):
-                    bv._u_bcs_done = bv._b_bcs_done = False
+        """FluidBase.BeginStage of every fluid: no hand-shake flag of one stage is left standing for the next"""
+        for ph in (pm.pmb_pack.phydro, pm.pmb_pack.pmhd):
+            if ph is not None:
+                ph.BeginStage()
 
     def _cycle(self, pm):
         self.ExecuteTaskList(pm, "before_timeintegrator", 0)

@@ -6,6 +6,7 @@ dependency chain (AssembleHydroTasks, hydro_tasks.cpp:48-80), each task body red
 call through the C ABI (include/akmi.h).  Device arrays are torch.float64 CUDA tensors in the
 reference's (m,n,k,j,i) LayoutRight order; torch is memory/stream plumbing only.
 """
+import contextlib
 import ctypes as C
 import os
 
@@ -162,6 +163,11 @@ class FluidBase:
         self.dt3 = torch.zeros(3, dtype=torch.float64, device=device)
         self.dtnew = FLT_MAX
         self.ws = None
+        self.w1 = None                # second primitive array of akmi_hydro_stage_w, allocated by its first call
+        # hand-shakes between the tasks of one stage: the stage call has converted the active cells / scanned the CFL
+        # minima; the gather of SendU has reset the minima / is asked to convert the ghost shell / has done so
+        self._interior_done = self._dt_ready = False
+        self._dt3_reset = self._want_ghost_c2p = self._shell_done = False
         self.multilevel = pm.multilevel
         if pm.multilevel:
             # the restricted fluxes of finer neighbours replace face fluxes between Fluxes and
@@ -234,6 +240,26 @@ class FluidBase:
         return (stage == 1 and not self.fused and not self.use_fofc and not self.turb_driving
                 and not self.ion_neutral and pdrive.integrator != "rk4" and _TASK_OOP)
 
+    def BeginStage(self):
+        """the hand-shakes between SendU / SendB and ApplyPhysicalBCs / ConToPrim live inside one stage: none may be left
+        standing for the next one (a task list that drops the consumer)"""
+        self._dt3_reset = self._want_ghost_c2p = self._shell_done = False
+        self.pbval_u.BeginStage()         # (MHD: pbval_b is the same object)
+
+    @contextlib.contextmanager
+    def _timed(self):
+        """a HIP event pair around one launch group of the stage, appended to the list bench.py hangs on the object as
+        stage_events for the cycles it times (no such attribute, or None: nothing is recorded)"""
+        ev = getattr(self, "stage_events", None)
+        if ev is None:
+            yield
+            return
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ev.append((e0, e1))
+        e0.record()
+        yield
+        e1.record()
+
     @staticmethod
     def _copy_flag(pdrive, stage, phases):
         """copy_u1 of include/akmi.h: the first stage writes its result into the second register and
@@ -245,10 +271,40 @@ class FluidBase:
             return 1
         return 2 if phases & (capi.PHASE_SWEEPS | capi.PHASE_EMF_CT) else 0
 
+    def _swap_b(self):
+        pass                               # (hydro has no face field)
 
-import os as _os
-_MERGE_C2P = _os.environ.get("AKMI_MERGE_C2P", "1") != "0"      # A/B switch (profiles/r03_whatif_merge_c2p.txt)
-_TASK_OOP = _os.environ.get("AKMI_TASK_OOP", "1") != "0"        # A/B switch: first stage of the task path out of place
+    def _stage_phase(self, pdrive, stage, phases, write_prims=False):
+        """the parts of the fused stage named by the mask `phases`, through the fluid's _call_stage (akmi_*_stage_phase;
+        write_prims: akmi_hydro_stage_w); then the register swaps and the hand-shake flags"""
+        # stage 0 = Driver::InitBoundaryValuesAndPrimitives: only the c2p part may run then (the RK
+        # weights of "stage 0" do not exist; [stage - 1] would silently pick the last stage's)
+        assert stage >= 1 or phases == capi.PHASE_C2P, (stage, phases)
+        if stage >= 1:
+            gam0, gam1 = pdrive.gam0[stage - 1], pdrive.gam1[stage - 1]
+            beta_dt = pdrive.beta[stage - 1]*self.pmy_pack.pmesh.dt
+        else:
+            gam0, gam1, beta_dt = 1.0, 0.0, 0.0
+        do_dt = 1 if stage == pdrive.nexp_stages else 0
+        copy = self._copy_flag(pdrive, stage, phases)
+        with self._timed():
+            wrote = self._call_stage(gam0, gam1, beta_dt, copy, do_dt, phases, write_prims)
+        if copy == 2:                      # out-of-place first stage: the registers trade places
+            if phases & capi.PHASE_SWEEPS:
+                self.u0, self.u1 = self.u1, self.u0
+            if phases & capi.PHASE_EMF_CT:
+                self._swap_b()
+        if wrote:
+            self.w0, self.w1 = self.w1, self.w0
+        if phases & capi.PHASE_C2P:
+            self._interior_done = True
+            self._dt_ready = bool(do_dt)
+        if write_prims:
+            self._want_ghost_c2p = bool(wrote)    # (0: converted in place, the ghost shell takes the usual path)
+
+
+_MERGE_C2P = os.environ.get("AKMI_MERGE_C2P", "1") != "0"      # A/B switch (profiles/r03_whatif_merge_c2p.txt)
+_TASK_OOP = os.environ.get("AKMI_TASK_OOP", "1") != "0"        # A/B switch: first stage of the task path out of place
 
 
 class Hydro(FluidBase):
@@ -350,7 +406,6 @@ class Hydro(FluidBase):
                                          self.pbval_u.u_in)
             if self.pmy_pack.pmesh.prolong_prims:          # hydro_tasks.cpp:388-392
                 if getattr(self, "coarse_w0", None) is None:
-                    import torch
                     self.coarse_w0 = torch.zeros_like(self.coarse_u0)
                 self.psmr.ConsToPrimCoarseBndry(self.coarse_u0, None, self.coarse_w0)
                 self.psmr.ProlongateCC(self.w0, self.coarse_w0)
@@ -447,70 +502,31 @@ class Hydro(FluidBase):
     def _stage_w(self, pdrive, stage):
         """akmi_hydro_stage_w: the whole stage, ConsToPrim of the active cells inside the update kernel, the new
         primitives in the second primitive array (the two trade places afterwards)"""
-        import torch
-        gam0, gam1 = pdrive.gam0[stage - 1], pdrive.gam1[stage - 1]
-        beta_dt = pdrive.beta[stage - 1]*self.pmy_pack.pmesh.dt
-        do_dt = 1 if stage == pdrive.nexp_stages else 0
-        copy = self._copy_flag(pdrive, stage, capi.PHASE_ALL)
-        if getattr(self, "w1", None) is None:
+        if self.w1 is None:
             self.w1 = torch.zeros_like(self.w0)
-        ev = getattr(self, "stage_events", None)     # bench.py: HIP event pair around the launch group
-        if ev is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev.append((e0, e1))
-            e0.record()
+        self._stage_phase(pdrive, stage, capi.PHASE_ALL, write_prims=True)
+
+    def _call_stage(self, gam0, gam1, beta_dt, copy, do_dt, phases, write_prims):
+        if not write_prims:
+            capi.check(self.L.akmi_hydro_stage_phase(
+                C.byref(self.pack_c), self.recon_method, self.rsolver_method, capi.d(gam0),
+                capi.d(gam1), capi.d(beta_dt), copy, capi._p(self.w0),
+                capi._p(self.u0), capi._p(self.u1), do_dt, capi._p(self.counters),
+                capi._p(self.dt3), phases, capi._p(self._workspace(0)), capi._stream()),
+                "hydro_stage_phase")
+            return 0
         wrote = C.c_int(0)
         capi.check(self.L.akmi_hydro_stage_w(
             C.byref(self.pack_c), self.recon_method, self.rsolver_method, capi.d(gam0), capi.d(gam1), capi.d(beta_dt),
             None, copy, capi._p(self.w0), capi._p(self.w1), capi._p(self.u0), capi._p(self.u1), do_dt,
             capi._p(self.counters), capi._p(self.dt3), capi._p(self._workspace(0)), capi._stream(), C.byref(wrote)),
             "hydro_stage_w")
-        if ev is not None:
-            e1.record()
-        if copy == 2:                      # out-of-place first stage: the registers trade places
-            self.u0, self.u1 = self.u1, self.u0
-        if wrote.value:
-            self.w0, self.w1 = self.w1, self.w0
-        self._interior_done = True
-        self._dt_ready = bool(do_dt)
-        self._want_ghost_c2p = bool(wrote.value)    # (0: converted in place, the ghost shell takes the usual path)
-
-    def _stage_phase(self, pdrive, stage, phases):
-        """akmi_hydro_stage_phase: the parts of the fused stage named by the mask `phases`"""
-        # stage 0 = Driver::InitBoundaryValuesAndPrimitives: only the c2p part may run then (the RK
-        # weights of "stage 0" do not exist; [stage - 1] would silently pick the last stage's)
-        assert stage >= 1 or phases == capi.PHASE_C2P, (stage, phases)
-        if stage >= 1:
-            gam0, gam1 = pdrive.gam0[stage - 1], pdrive.gam1[stage - 1]
-            beta_dt = pdrive.beta[stage - 1]*self.pmy_pack.pmesh.dt
-        else:
-            gam0, gam1, beta_dt = 1.0, 0.0, 0.0
-        do_dt = 1 if stage == pdrive.nexp_stages else 0
-        copy = self._copy_flag(pdrive, stage, phases)
-        ev = getattr(self, "stage_events", None)     # bench.py: HIP event pair around the launch group
-        if ev is not None:
-            import torch
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev.append((e0, e1))
-            e0.record()
-        capi.check(self.L.akmi_hydro_stage_phase(
-            C.byref(self.pack_c), self.recon_method, self.rsolver_method, capi.d(gam0),
-            capi.d(gam1), capi.d(beta_dt), copy, capi._p(self.w0),
-            capi._p(self.u0), capi._p(self.u1), do_dt, capi._p(self.counters),
-            capi._p(self.dt3), phases, capi._p(self._workspace(0)), capi._stream()),
-            "hydro_stage_phase")
-        if ev is not None:
-            e1.record()
-        if copy == 2:                      # out-of-place first stage: the registers trade places
-            self.u0, self.u1 = self.u1, self.u0
-        if phases & capi.PHASE_C2P:
-            self._interior_done = True
-            self._dt_ready = bool(do_dt)
+        return wrote.value
 
     def SendU(self, pdrive, stage):
         if self.multilevel:
             return self.psmr.PackAndSendCC(self.u0, self.coarse_u0)
-        if getattr(self, "_want_ghost_c2p", False):
+        if self._want_ghost_c2p:
             # the stage kernel has converted the active cells (akmi_hydro_stage_w): ghost zones of u0 AND of the new primitive
             # array by the same gather + boundary functions, one launch, nothing converted twice (akmi_hydro_ghost_uw)
             self._want_ghost_c2p = False
@@ -525,7 +541,7 @@ class Hydro(FluidBase):
             return TaskStatus.complete
         reset = None
         if (self.fused and self.pbval_u.fold_bcs and stage >= 1 and stage == pdrive.nexp_stages
-                and not getattr(self, "_interior_done", False)):
+                and not self._interior_done):
             reset = self.dt3                 # the gather of the last stage also resets the CFL minima
         st = self.pbval_u.PackAndSendCC(self.u0, reset)
         self._dt3_reset = reset is not None
@@ -554,9 +570,9 @@ class Hydro(FluidBase):
         """hydro_tasks.cpp:404-412: all cells including ghosts (the fused path also performs
         the CFL scan of NewTimeStep in the same kernel on the last stage)"""
         n3, n2, n1 = self.pmy_pack.pmesh.mb_indcs.ncells
-        if self.fused and getattr(self, "_interior_done", False):
+        if self.fused and self._interior_done:
             self._interior_done = False
-            if not getattr(self, "_shell_done", False):
+            if not self._shell_done:
                 capi.check(self.L.akmi_hydro_c2p_shell(
                     C.byref(self.pack_c), capi._p(self.u0), capi._p(self.w0), capi._p(self.counters),
                     capi._stream()), "hydro_c2p_shell")
@@ -564,19 +580,12 @@ class Hydro(FluidBase):
             return TaskStatus.complete
         if self.fused:
             do_dt = 1 if stage == pdrive.nexp_stages else 0
-            ev = getattr(self, "stage_events", None)     # bench.py: the conversion belongs to the stage's launch group
-            if ev is not None:
-                import torch
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                ev.append((e0, e1))
-                e0.record()
-            capi.check(self.L.akmi_hydro_c2p_newdt(
-                C.byref(self.pack_c), capi._p(self.u0), capi._p(self.w0),
-                2 if (do_dt and getattr(self, "_dt3_reset", False)) else do_dt,
-                capi._p(self.counters), capi._p(self.dt3), capi._stream()), "hydro_c2p_newdt")
+            with self._timed():          # bench.py: the conversion belongs to the stage's launch group
+                capi.check(self.L.akmi_hydro_c2p_newdt(
+                    C.byref(self.pack_c), capi._p(self.u0), capi._p(self.w0),
+                    2 if (do_dt and self._dt3_reset) else do_dt,
+                    capi._p(self.counters), capi._p(self.dt3), capi._stream()), "hydro_c2p_newdt")
             self._dt3_reset = False
-            if ev is not None:
-                e1.record()
             self._dt_ready = bool(do_dt)
             return TaskStatus.complete
         if self.multilevel and not self.kinematic:
@@ -600,7 +609,7 @@ class Hydro(FluidBase):
         if self.kinematic:                                       # hydro_newdt.cpp:55-72
             capi.check(self.L.akmi_kinematic_newdt(C.byref(self.pack_c), capi._p(self.w0),
                                                    capi._p(self.dt3), capi._stream()), "kinematic_newdt")
-        elif not getattr(self, "_dt_ready", False):
+        elif not self._dt_ready:
             capi.check(self.L.akmi_hydro_newdt(C.byref(self.pack_c), capi._p(self.w0),
                                                capi._p(self.dt3), capi._stream()), "hydro_newdt")
         self._dt_ready = False

@@ -10,12 +10,8 @@ import torch
 
 from . import capi
 from .bvals import MeshBoundaryValues
-from .hydro import EdgeFld, FaceFld, FluidBase
+from .hydro import _MERGE_C2P, EdgeFld, FaceFld, FluidBase
 from .tasklist import TaskID, TaskStatus
-
-
-import os as _os
-_MERGE_C2P = _os.environ.get("AKMI_MERGE_C2P", "1") != "0"      # A/B switch (profiles/r03_whatif_merge_c2p.txt)
 
 
 class MHD(FluidBase):
@@ -151,7 +147,6 @@ class MHD(FluidBase):
                                 self.coarse_b0.x3f, pb.b_in)
             if self.pmy_pack.pmesh.prolong_prims:          # mhd_tasks.cpp:539-544
                 if getattr(self, "coarse_w0", None) is None:
-                    import torch
                     self.coarse_w0 = torch.zeros_like(self.coarse_u0)
                 ps.ConsToPrimCoarseBndry(self.coarse_u0, self.coarse_b0, self.coarse_w0)
                 ps.ProlongateCC(self.w0, self.coarse_w0)
@@ -233,40 +228,17 @@ class MHD(FluidBase):
                 capi._p(self.u1), *self._b(self.uflx), 1, capi._stream()), "rk_update")
         return TaskStatus.complete
 
-    def _stage_phase(self, pdrive, stage, phases):
-        """akmi_mhd_stage_phase: the parts of the fused stage named by the mask `phases`"""
-        # stage 0 = Driver::InitBoundaryValuesAndPrimitives: only the c2p part may run then (the RK
-        # weights of "stage 0" do not exist; [stage - 1] would silently pick the last stage's)
-        assert stage >= 1 or phases == capi.PHASE_C2P, (stage, phases)
-        if stage >= 1:
-            gam0, gam1 = pdrive.gam0[stage - 1], pdrive.gam1[stage - 1]
-            beta_dt = pdrive.beta[stage - 1]*self.pmy_pack.pmesh.dt
-        else:
-            gam0, gam1, beta_dt = 1.0, 0.0, 0.0
-        do_dt = 1 if stage == pdrive.nexp_stages else 0
-        copy = self._copy_flag(pdrive, stage, phases)
-        ev = getattr(self, "stage_events", None)     # bench.py: HIP event pair around the launch group
-        if ev is not None:
-            import torch
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev.append((e0, e1))
-            e0.record()
+    def _call_stage(self, gam0, gam1, beta_dt, copy, do_dt, phases, write_prims):
         capi.check(self.L.akmi_mhd_stage_phase(
             C.byref(self.pack_c), self.recon_method, self.rsolver_method, capi.d(gam0),
             capi.d(gam1), capi.d(beta_dt), copy, capi._p(self.w0),
             capi._p(self.bcc0), capi._p(self.u0), capi._p(self.u1), *self._b(self.b0),
             *self._b(self.b1), do_dt, capi._p(self.counters), capi._p(self.dt3), phases,
             capi._p(self._workspace(1)), capi._stream()), "mhd_stage_phase")
-        if ev is not None:
-            e1.record()
-        if copy == 2:                      # out-of-place first stage: the registers trade places
-            if phases & capi.PHASE_SWEEPS:
-                self.u0, self.u1 = self.u1, self.u0
-            if phases & capi.PHASE_EMF_CT:
-                self.b0, self.b1 = self.b1, self.b0
-        if phases & capi.PHASE_C2P:
-            self._interior_done = True
-            self._dt_ready = bool(do_dt)
+        return 0
+
+    def _swap_b(self):
+        self.b0, self.b1 = self.b1, self.b0
 
     def SendU(self, pdrive, stage):
         if self.multilevel:
@@ -304,7 +276,7 @@ class MHD(FluidBase):
                     C.byref(self.pack_c), capi.d(gam0), capi.d(gam1), capi.d(beta_dt),
                     capi._p(self.efld.x1e), capi._p(self.efld.x2e), capi._p(self.efld.x3e),
                     *self._b(self.b0), *self._b(self.b1), capi._stream()), "mhd_ct_oop")
-                self.b0, self.b1 = self.b1, self.b0
+                self._swap_b()
                 return TaskStatus.complete
             capi.check(self.L.akmi_mhd_ct(
                 C.byref(self.pack_c), capi.d(gam0), capi.d(gam1), capi.d(beta_dt),
@@ -341,7 +313,7 @@ class MHD(FluidBase):
     def ConToPrim(self, pdrive, stage):
         """mhd_tasks.cpp: all cells incl. ghosts; fused path: + CFL scan on the last stage"""
         n3, n2, n1 = self.pmy_pack.pmesh.mb_indcs.ncells
-        if self.fused and getattr(self, "_interior_done", False):
+        if self.fused and self._interior_done:
             self._interior_done = False
             capi.check(self.L.akmi_mhd_c2p_shell(
                 C.byref(self.pack_c), capi._p(self.u0), *self._b(self.b0), capi._p(self.w0),
@@ -349,18 +321,11 @@ class MHD(FluidBase):
             return TaskStatus.complete
         if self.fused:
             do_dt = 1 if stage == pdrive.nexp_stages else 0
-            ev = getattr(self, "stage_events", None)     # bench.py: the conversion belongs to the stage's launch group
-            if ev is not None:
-                import torch
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                ev.append((e0, e1))
-                e0.record()
-            capi.check(self.L.akmi_mhd_c2p_newdt(
-                C.byref(self.pack_c), capi._p(self.u0), *self._b(self.b0), capi._p(self.w0),
-                capi._p(self.bcc0), do_dt, capi._p(self.counters), capi._p(self.dt3),
-                capi._stream()), "mhd_c2p_newdt")
-            if ev is not None:
-                e1.record()
+            with self._timed():          # bench.py: the conversion belongs to the stage's launch group
+                capi.check(self.L.akmi_mhd_c2p_newdt(
+                    C.byref(self.pack_c), capi._p(self.u0), *self._b(self.b0), capi._p(self.w0),
+                    capi._p(self.bcc0), do_dt, capi._p(self.counters), capi._p(self.dt3),
+                    capi._stream()), "mhd_c2p_newdt")
             self._dt_ready = bool(do_dt)
             return TaskStatus.complete
         if self.multilevel and not self.kinematic:
@@ -388,7 +353,7 @@ class MHD(FluidBase):
         if self.kinematic:                                       # mhd_newdt.cpp:56-73
             capi.check(self.L.akmi_kinematic_newdt(C.byref(self.pack_c), capi._p(self.w0),
                                                    capi._p(self.dt3), capi._stream()), "kinematic_newdt")
-        elif not getattr(self, "_dt_ready", False):
+        elif not self._dt_ready:
             capi.check(self.L.akmi_mhd_newdt(C.byref(self.pack_c), capi._p(self.w0),
                                              capi._p(self.bcc0), capi._p(self.dt3), capi._stream()),
                        "mhd_newdt")
