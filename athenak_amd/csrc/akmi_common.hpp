@@ -256,7 +256,8 @@ void set_error(const char *fmt, ...);
 
 inline int cdiv(int a, int b) { return (a + b - 1)/b; }
 
-// akmi_stage.hip: the flux kernels of the task-granular entry points by the sweeps of the fused stage
+// akmi_stage.hip (launching k_sweep of akmi_stage_sweeps.hip and the storing marches of akmi_stage_march_x2/_x3.hip):
+// the flux kernels of the task-granular entry points by the sweeps of the fused stage
 // (bcc0 == nullptr: hydro).  AKMI_COMPLETE / AKMI_FAIL, or -1 when the pack is outside what the sweeps
 // address (the caller then uses its own kernels).
 int sweeps_store_fluxes(const akmi_pack *p, int recon, int rsolver, const double *w0, const double *bcc0,

@@ -1,5 +1,6 @@
 // akmi_hydro_stage3d2.hpp -- hydro, 3-D, DC/PLM: the three sweeps and the RK update of a stage in ONE kernel
-// (k_hydro_stage3d2, its tile chooser and LDS layout; included by akmi_stage.hip inside namespace akmi).
+// (k_hydro_stage3d2, its tile chooser and LDS layout; akmi_stage_hydro.hip instantiates the kernel and defines its
+// launcher, akmi_stage.hip takes the tile chooser and the argument types for the plan of a stage).
 //
 // A workgroup owns a tile of (tw-1) x (th-1) cell columns (lanes flattened over the tw x th positions; the last
 // column / row of positions only provides the face on its low side) and marches along k.  Per step k (two barriers):
@@ -21,8 +22,9 @@
 // HBM traffic per cell: w0 once (+halo, L2 hits: neighbouring tiles share an XCD, xcd_order), u0 (+u1) once --
 // no flux or partial divergence arrays.  The CT-extended ranges of MHD do not apply (faces is..ie+1 only).
 //
-// Where the marching state lives and when memory is touched -- the findings of k_mhd_stage3d
-// (profiles/r06_mhd_stage3d.txt) applied to the kernel that has the registers for three waves per SIMD:
+// Where the marching state lives and when memory is touched -- the findings of the MHD analogue k_mhd_stage3d (built in
+// round 6, slower than the kernels it would replace and removed: profiles/r06_mhd_stage3d.txt) applied to the kernel
+// that has the registers for three waves per SIMD:
 //   * with both planes in LDS the cells k-1 and k of the position's own column are read from there for the x3 face, so
 //     the ten doubles W0 / W1 stay out of the register file -- no scratch (the one-plane kernel of round 5, removed, saved
 //     and restored three doubles per step through scratch, each reload an `s_waitcnt vmcnt(0)`);
@@ -31,6 +33,12 @@
 //   * the loads of plane k+1 are issued after the x1 solve and consumed after the x2 solve, the operands of the update
 //     after the x2 solve and consumed after the x3 solve; the stores of a step (u0, mass fluxes) all come after its last
 //     wait for a load (with loads and stores both outstanding the compiler's wait for a load is `vmcnt(0)`).
+#ifndef AKMI_HYDRO_STAGE3D2_HPP_
+#define AKMI_HYDRO_STAGE3D2_HPP_
+#include "akmi_stage.hpp"
+
+namespace akmi {
+
 struct HydTile { int tw, th, n1, n2, threads; };
 constexpr int HS_THREADS = 512;
 #ifndef AKMI_HS2_WAVES
@@ -39,9 +47,9 @@ constexpr int HS_THREADS = 512;
 
 // LDS of a workgroup, in doubles: the two planes with their halo and two face-shaped arrays
 constexpr int HS_ES = 5;                   // doubles per LDS entry (a padded 48-byte stride measured slower: profiles/r05_hydro_ab.txt)
-static size_t hyd_lds_doubles(int tw, int th) { return HS_ES*(2*(size_t)(tw + 3)*(th + 3) + 2*(size_t)tw*th); }
+inline size_t hyd_lds_doubles(int tw, int th) { return HS_ES*(2*(size_t)(tw + 3)*(th + 3) + 2*(size_t)tw*th); }
 
-static HydTile hyd_tile(int c1, int c2) {
+inline HydTile hyd_tile(int c1, int c2) {
   // The kernel is bound by the issue of dependent fp64 chains (1 330 VALU instructions per cell, three waves per SIMD), so
   // what a shape costs is the lanes it launches per owned column, not the length of its rows:
   //   cost = lanes launched (tiles x padded workgroup)
@@ -105,6 +113,22 @@ struct HydC2P {
   int *counters;
   double *dt3;
 };
+
+// the launcher (akmi_stage_hydro.hip).  tl: the tile of the stage's plan; cpa: ConsToPrim of the finished cells inside the
+// kernel, nullptr: update only
+template <bool MASS>
+int launch_hydro_stage3d(const Geo &g, const Scheme &sc, const HydTile &tl, const double *w0, const UpdArgs &u, int kA,
+                         int kB, hipStream_t st, Mass3 ms, const HydC2P *cpa = nullptr);
+
+// Workgroup -> tile order.  Workgroup b of a launch runs on XCD b % 8 (observed placement; nothing below depends on
+// it for correctness), and each XCD has its own L2.  A tile kernel whose neighbouring tiles re-read each other's edge
+// rows wants neighbours on the SAME XCD at about the same time: XCD x takes the x-th contiguous eighth of the tile
+// list, in list order.  The map is a bijection of [0, n) for every n.
+__device__ __forceinline__ unsigned xcd_order(unsigned b, unsigned n) {
+  const unsigned xcd = b & 7u, slot = b >> 3, q = n >> 3, rem = n & 7u;
+  return (xcd < rem ? xcd*(q + 1u) : rem*(q + 1u) + (xcd - rem)*q) + slot;
+}
+
 template <int RECON, int RS, bool MASS = false, bool C2P = false>
 __global__ void __launch_bounds__(HS_THREADS, AKMI_HS2_WAVES)
 k_hydro_stage3d2(Geo g, FaceEos eos, const double *__restrict__ w0, UpdArgs u, int kA, int kB,
@@ -386,3 +410,6 @@ k_hydro_stage3d2(Geo g, FaceEos eos, const double *__restrict__ w0, UpdArgs u, i
   }
 #undef ISOSKIP
 }
+
+}  // namespace akmi
+#endif

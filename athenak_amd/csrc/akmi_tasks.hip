@@ -1,7 +1,7 @@
 // akmi_tasks.hip -- one HIP kernel (family) per reference task body, behind the C ABI of
 // include/akmi.h.  These are the task-granular entry points (drop-in for the bodies of
 // Hydro::Fluxes, RKUpdate, ConToPrim, NewTimeStep, MHD::Fluxes, CornerE, CT ...); the fused
-// per-stage fast path lives in akmi_stage.hip and must reproduce these bit for bit.
+// per-stage fast path lives in the akmi_stage*.hip units (akmi_stage.hpp) and must reproduce these bit for bit.
 //
 // Thread mapping everywhere: threadIdx.x runs along i (the contiguous index of the
 // (m,n,k,j,i) LayoutRight arrays) so every global access of a wave is a 512-B coalesced
@@ -1027,7 +1027,8 @@ int akmi_rk4_copy_cons(const akmi_pack *p, double delta, const double *u0, doubl
 static int fofc_checks(const akmi_pack *p, int recon, const char *what, bool ideal_only);
 
 // The flux kernels below are thread-per-face; the sweeps of the fused stage compute the same fluxes with
-// the reconstruction of a cell done once (akmi_stage.hip, sweeps_store_fluxes) and take over wherever they
+// the reconstruction of a cell done once (sweeps_store_fluxes in akmi_stage.hip, kernels in akmi_stage_sweeps.hip and
+// the two march units) and take over wherever they
 // cover the request: no passive scalars (those ride on the stored mass flux in the fused path), not the
 // kinematic "advect" solver, not the FOFC-extended ranges.
 static bool use_sweeps(const akmi_pack *p, int rsolver, int ext) {

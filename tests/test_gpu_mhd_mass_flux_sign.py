@@ -1,4 +1,4 @@
-"""GPU tests of the byte form of the mass-flux sign (AKMI_MF_BYTES, akmi_stage.hip): on the fused 3-D MHD paths without
+"""GPU tests of the byte form of the mass-flux sign (AKMI_MF_BYTES, akmi_stage.hpp): on the fused 3-D MHD paths without
 passive scalars the sweeps leave `(unsigned char)(mass flux >= 0.0)` per face instead of the mass flux, and k_corner_ct,
 their only reader, tests the byte.  Results may not move by a bit, -0.0 counts as non-negative, and the paths on which
 k_scalar_update reads the fluxes keep doubles.  Everything is compared bit for bit, ghost zones included: u0, the three

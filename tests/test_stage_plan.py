@@ -1,5 +1,5 @@
 """not gpu: which kernels a stage runs is one function of the pack, the scheme and the environment switches (plan_stage in
-csrc/akmi_stage.hip).  Its two public answers, akmi_hydro_stage_w_eligible and akmi_mhd_u0_sweeps_eligible, read the pack
+csrc/akmi_stage.hip, the unit of the fused stage that holds the plan and the entry points and no kernel).  Its two public answers, akmi_hydro_stage_w_eligible and akmi_mhd_u0_sweeps_eligible, read the pack
 and the environment only -- no device call -- so they are compared here against a table written out by hand.  The switches
 are read once per process: every set of rows runs in a process of its own, with exactly the switches it names."""
 import ctypes as C
@@ -16,8 +16,7 @@ pytestmark = pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.ex
 
 DC, PLM, PPM4 = 0, 1, 2
 LLF, HLLE, HLLC, HLLD, ROE = 0, 1, 2, 3, 4
-SWITCHES = ("AKMI_FUSE_C2P", "AKMI_HYDRO_ONE_KERNEL", "AKMI_MHD_ONE_KERNEL", "AKMI_HS_LDS", "AKMI_HS_MAXT", "AKMI_HS_TILE",
-            "AKMI_MS_LDS", "AKMI_MS_TILE")
+SWITCHES = ("AKMI_FUSE_C2P", "AKMI_HYDRO_ONE_KERNEL", "AKMI_HS_LDS", "AKMI_HS_MAXT", "AKMI_HS_TILE")
 
 
 def answers(rows):
@@ -101,8 +100,6 @@ def test_eligibility_answers_match_the_table():
     ({"AKMI_FUSE_C2P": "0"}, [(W16, 0), (U16, 1)]),
     ({"AKMI_HYDRO_ONE_KERNEL": "0"}, [(W16, 0), (U16, 1)]),
     ({"AKMI_HS_LDS": "20000"}, [(W16, 1), (W3, 0), (W2, 0)]),                # a tile fits / fits no more / never did
-    ({"AKMI_MHD_ONE_KERNEL": "1"}, [(U16, 0), (W16, 1)]),
-    ({"AKMI_MHD_ONE_KERNEL": "1", "AKMI_MS_LDS": "1"}, [(U16, 1)]),          # no tile: the stage takes k_sweep12s
-], ids=["FUSE_C2P=0", "HYDRO_ONE_KERNEL=0", "HS_LDS=20000", "MHD_ONE_KERNEL=1", "MHD_ONE_KERNEL=1,MS_LDS=1"])
+], ids=["FUSE_C2P=0", "HYDRO_ONE_KERNEL=0", "HS_LDS=20000"])
 def test_switched_eligibility_answers(env, table):
     check(env, table)

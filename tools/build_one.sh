@@ -1,6 +1,8 @@
 #!/bin/bash
-# usage: tools/build_one.sh akmi_stage.hip [akmi_tasks.hip ...]  -- recompile the named translation units and relink
-# libakmi.so (the flags of __graft_entry__.build; the other objects must exist from a full build)
+# usage: tools/build_one.sh akmi_stage_mhd.hip [akmi_tasks.hip ...]  -- recompile the named translation units and relink
+# libakmi.so (the flags of __graft_entry__.build; the other objects must exist from a full build).  The fused stage is
+# one unit per kernel family (akmi_stage.hpp lists them); a change to akmi_stage.hpp or akmi_stage_march.hpp needs every
+# unit that includes it, which the check below enforces.
 root=$(cd $(dirname $0)/.. && pwd)
 cs=$root/athenak_amd/csrc; od=$root/athenak_amd/lib/obj
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -Wno-unused-value -mllvm -amdgpu-schedule-relaxed-occupancy=true $AKMI_EXTRA_FLAGS"
