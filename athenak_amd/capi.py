@@ -63,6 +63,12 @@ SYMBOLS = [
     "akmi_mhd_c2p_newdt_lean", "akmi_mhd_prims_fill", "akmi_mhd_c2p_takes_pairs",
     "akmi_amr_check", "akmi_amr_regrid_cc", "akmi_amr_regrid_fc", "akmi_amr_repair_fc",
     "akmi_ionn_imp_update",
+    "akmi_mg_smooth", "akmi_mg_defect", "akmi_mg_fas_rhs", "akmi_mg_restrict", "akmi_mg_prolongate_correct",
+    "akmi_mg_fmg_prolongate", "akmi_mg_store_old", "akmi_mg_correction", "akmi_mg_zero_clear", "akmi_mg_copy_source",
+    "akmi_mg_load_source", "akmi_mg_load_finest", "akmi_mg_retrieve", "akmi_mg_reduce_scratch_doubles",
+    "akmi_mg_average", "akmi_mg_subtract_average", "akmi_mg_defect_norm", "akmi_mg_exchange", "akmi_mg_root_boundary",
+    "akmi_mg_blocks_to_root", "akmi_mg_set_from_root", "akmi_mg_selfgravity", "akmi_mg_workspace_doubles",
+    "akmi_mg_level_offset", "akmi_mg_solve", "akmi_mg_launch_count",
 ]
 
 AMR_METHOD = {"min_max": 0, "slope": 1, "second_deriv": 2}               # AKMI_AMR_* of include/akmi.h
@@ -112,6 +118,19 @@ class CoarsenVar(C.Structure):
     _fields_ = [("array", C.c_void_p), ("nvar", C.c_int), ("comp", C.c_int)]
 
 
+class MgPlan(C.Structure):
+    """struct akmi_mg_plan (include/akmi.h)"""
+    _fields_ = [("nmb", C.c_int), ("nxb", C.c_int), ("nrx1", C.c_int), ("nrx2", C.c_int), ("nrx3", C.c_int),
+                ("nmblevel", C.c_int), ("nrootlevel", C.c_int), ("ng", C.c_int), ("nvar", C.c_int),
+                ("npresmooth", C.c_int), ("npostsmooth", C.c_int), ("niter", C.c_int), ("full_multigrid", C.c_int),
+                ("fmg_ncycle", C.c_int), ("subtract_average", C.c_int), ("show_defect", C.c_int),
+                ("rdx", C.c_double), ("root_dx", C.c_double), ("omega", C.c_double), ("four_pi_G", C.c_double),
+                ("eps", C.c_double), ("vol", C.c_double), ("nghbr", C.c_void_p), ("lloc", C.c_void_p),
+                ("ws", C.c_void_p)]
+
+
+MG_NNORMS = 42                  # AKMI_MG_NNORMS of include/akmi.h
+
 TURB_NHIST = 11                 # AKMI_TURB_NHIST of include/akmi.h
 TURB_HIST_LABELS = ["Bx", "By", "Bz", "B^2", "B^4", "dB^2", "BdB^2", "|BxJ|^2", "|B.J|^2", "U^2", "dU"]   # turb.cpp:249-259
 
@@ -146,6 +165,9 @@ def lib():
             getattr(L, f).restype = C.c_double
             getattr(L, f).argtypes = [C.POINTER(RngState)]
         L.akmi_turb_workspace_bytes.restype = C.c_longlong
+        for f in ("akmi_mg_reduce_scratch_doubles", "akmi_mg_workspace_doubles", "akmi_mg_level_offset",
+                  "akmi_mg_launch_count"):
+            getattr(L, f).restype = C.c_longlong
         L.akmi_turb_history_workspace_bytes.restype = C.c_longlong
         for f in ("akmi_sim_time", "akmi_sim_dt", "akmi_sim_tlim"):
             getattr(L, f).restype = C.c_double

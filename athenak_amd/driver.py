@@ -172,6 +172,8 @@ class Driver:
         for stage in range(1, self.nexp_stages + 1):
             self._begin_stage(pm)
             self.ExecuteTaskList(pm, "before_stagen", stage)
+            if pm.pmb_pack.pgrav is not None:                          # driver.cpp:403-411: every stage, not at t = 0
+                pm.pmb_pack.pgrav.pmgd.Solve(stage, self)
             self.ExecuteTaskList(pm, "stagen", stage)
             self.ExecuteTaskList(pm, "after_stagen", stage)
         self.ExecuteTaskList(pm, "after_timeintegrator", 1)

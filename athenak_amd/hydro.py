@@ -159,6 +159,8 @@ class FluidBase:
         if pin.DoesBlockExist(blk + "_srcterms"):
             from .srcterms import SourceTerms
             self.psrc = SourceTerms(blk + "_srcterms", self, pin)
+            if self.psrc.self_gravity:
+                self.fused = False   # SelfGravity reads the mass fluxes: the flux arrays of the task path
         self.counters = torch.zeros(3, dtype=torch.int32, device=device)
         self.dt3 = torch.zeros(3, dtype=torch.float64, device=device)
         self.dtnew = FLT_MAX

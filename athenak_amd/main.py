@@ -19,6 +19,9 @@ class Simulation:
         if restart is not None and pin.DoesBlockExist("ion-neutral"):
             raise RuntimeError("### FATAL ERROR -r of a deck with <ion-neutral>: restarting a two-fluid run is not on "
                                "this path yet")
+        if restart is not None and pin.DoesBlockExist("gravity"):
+            raise RuntimeError("### FATAL ERROR -r of a deck with <gravity>: restarting a self-gravitating run is not on "
+                               "this path yet")
         self.pmesh = Mesh(pin, my_rank, nranks)
         if restart is not None and self.pmesh.adaptive:
             raise RuntimeError("### FATAL ERROR -r of a deck with <mesh_refinement>/refinement = adaptive: the restart "
@@ -67,6 +70,22 @@ class Simulation:
     def phys(self):
         pk = self.pmesh.pmb_pack
         return pk.phydro if pk.phydro is not None else pk.pmhd
+
+    def phi(self):
+        """the gravitational potential of the last Solve, (nmb, 1, N3, N2, N1); zero before the first cycle"""
+        pg = self.pmesh.pmb_pack.pgrav
+        if pg is None:
+            raise RuntimeError("### FATAL ERROR the gravitational potential needs a <gravity> block")
+        return pg.phi
+
+    @property
+    def omega_measured(self):
+        """pgen_name = gravity: the frequency / growth rate its final function measured (None before it has run)"""
+        return getattr(self.pmesh.pgen, "omega_measured", None)
+
+    @property
+    def omega_analytical(self):
+        return getattr(self.pmesh.pgen, "omega_analytical", None)
 
     def derived(self, name):
         """a derived output variable of the present state ("mhd_j2", "hydro_wz", ... or "temperature") as a

@@ -201,6 +201,7 @@ class MeshBlockPack:
         self.pmhd = None
         self.pionn = None
         self.pturb = None
+        self.pgrav = None
         self.tl_map = {}
         for name in ("before_timeintegrator", "after_timeintegrator", "before_stagen",
                      "stagen", "after_stagen"):
@@ -219,6 +220,8 @@ class MeshBlockPack:
         srcterms_deck_checks(pin)
         from .ion_neutral import IonNeutral, ionn_deck_checks
         ionn_deck_checks(pin, getattr(getattr(self, "pmesh", None), "nranks", 1))
+        from .gravity import Gravity, gravity_deck_checks
+        gravity_deck_checks(pin, getattr(getattr(self, "pmesh", None), "nranks", 1))
         # (1) units, meshblock_pack.cpp:108-112: created iff the block exists
         self.punit = None
         if pin.DoesBlockExist("units"):
@@ -246,6 +249,9 @@ class MeshBlockPack:
         # (6) turbulence driver, meshblock_pack.cpp:177-189
         from .turb_driver import add_turbulence_driver
         self.pturb = add_turbulence_driver(self, pin)
+        # gravity, meshblock_pack.cpp:243-252: created iff the block exists
+        if pin.DoesBlockExist("gravity"):
+            self.pgrav = Gravity(self, pin)
 
     def RebuildAfterRegrid(self, pin):
         """the MeshBlocks, the fluid's arrays, the level-aware boundary tables and the task lists of the new mesh,

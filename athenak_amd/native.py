@@ -45,6 +45,9 @@ class NativeSimulation:
         if pin.DoesBlockExist("ion-neutral"):
             raise RuntimeError("### FATAL ERROR <ion-neutral> runs on the Python host only (--host python): the C++ host "
                                "(--host native) has neither the two-fluid task list nor the ImEx integrators")
+        if pin.DoesBlockExist("gravity"):
+            raise RuntimeError("### FATAL ERROR <gravity> runs on the Python host only (--host python): the C++ host "
+                               "(--host native) has no multigrid driver")
         self.L = capi.lib()
         stream = capi._stream()
         h = self.L.akmi_sim_create(pin.Dump().encode(), stream)

@@ -148,6 +148,14 @@ def _scalars(nfluid, nscalars):
 
 # variable groups of basetype_output.cpp:196-620 for Newtonian hydro/MHD:
 # name -> list of (label, component, array); array "dv:<which>" is computed at output time
+def _grav_phi_outvars(have_grav, block_name):
+    """variable = grav_phi, basetype_output.cpp:172-178,620-623: Gravity::phi"""
+    if not have_grav:
+        _fatal("Output of gravity potential requested in <output> block '%s' but gravity object not constructed."
+               "\nInput file is likely missing a <gravity> block" % block_name)
+    return [("grav_phi", 0, "phi")]
+
+
 def _outvars(variable, is_mhd, is_ideal=True, turb=False, nscalars=0):
     blk = "mhd" if is_mhd else "hydro"
     u = [("dens", 0, "u0"), ("mom1", 1, "u0"), ("mom2", 2, "u0"), ("mom3", 3, "u0"), ("ener", 4, "u0")]
@@ -198,6 +206,12 @@ class BaseTypeOutput:
                 _fatal("%s output of a run with two fluids is not on this path yet (output block '%s'): tab, bin and hst"
                        % (op.file_type, op.block_name))
             phys, is_mhd = _out_fluid(pk, op.variable)
+            if op.variable == "grav_phi":
+                if op.file_type not in ("tab", "bin"):
+                    _fatal("%s output of grav_phi is not on this path (output block '%s'): tab and bin"
+                           % (op.file_type, op.block_name))
+                self.outvars = _grav_phi_outvars(getattr(pk, "pgrav", None) is not None, op.block_name)
+                return
             self.outvars = _outvars(op.variable, is_mhd, phys.peos.eos_data.is_ideal,
                                     getattr(pk, "pturb", None) is not None and not two, getattr(phys, "nscalars", 0))
 
@@ -260,7 +274,7 @@ class BaseTypeOutput:
                     if arr in derived:
                         host[key] = _to_numpy(derived[arr][m, comp])
                     else:
-                        src = pk.pturb if arr == "force" else phys
+                        src = pk.pturb if arr == "force" else (pk.pgrav if arr == "phi" else phys)
                         host[key] = _to_numpy(getattr(src, arr)[m, comp])
                 out[n, mi] = host[key][o.oks:o.oke + 1, o.ojs:o.oje + 1, o.ois:o.oie + 1]
         self.outarray = out

@@ -198,7 +198,8 @@ class ProblemGenerator:
         self.pgen_name = name
         table = {"linear_wave": self.LinearWave, "shock_tube": self.ShockTube,
                  "orszag_tang": self.OrszagTang, "blast": self.UserProblem, "diffusion": self.Diffusion,
-                 "cpaw": self.AlfvenWave, "turb": self.Turb, "rt": self.RayleighTaylor, "cshock": self.CShock}
+                 "cpaw": self.AlfvenWave, "turb": self.Turb, "rt": self.RayleighTaylor, "cshock": self.CShock,
+                 "gravity": self.SelfGravity}
         # user-defined boundary conditions (pgen.cpp:57-62): enrolled by the problem function
         self.user_bcs = any(b == capi.BC["user"] for b in pmesh.mesh_bcs)
         self.user_bcs_func = None
@@ -1080,6 +1081,125 @@ class ProblemGenerator:
             self._upload_cc(phys.b0.x1f, bf[0])
             self._upload_cc(phys.b0.x2f, bf[1])
             self._upload_cc(phys.b0.x3f, bf[2])
+
+    # ---- Jeans wave, src/pgen/tests/jeans_wave.cpp:78-280,355-447 -----------------------
+    def SelfGravity(self, pin, restart):
+        """pgen_name = gravity: a sinusoidal density perturbation along the box diagonal in a uniform self-gravitating
+        medium.  <problem>/n_jeans > 0 rescales four_pi_G so that lambda/lambda_Jeans = n_jeans.  The AMR criterion of
+        that file is not on this path."""
+        pm = self.pmy_mesh_
+        pk = pm.pmb_pack
+        use_mhd = pk.pmhd is not None
+        soe = "mhd" if use_mhd else "hydro"
+        four_pi_G = pin.GetOrAddReal("gravity", "four_pi_G", 1.0)
+        rho0 = pin.GetOrAddReal("problem", "rho0", 1.0)
+        n_jeans = pin.GetOrAddReal("problem", "n_jeans", -1.0)
+        is_isothermal = pin.GetString(soe, "eos") == "isothermal"
+        gamma = gm1 = p0 = 0.0
+        if is_isothermal:
+            cs = pin.GetReal(soe, "iso_sound_speed")
+        else:
+            gamma = pin.GetOrAddReal(soe, "gamma", 5.0/3.0)
+            gm1 = gamma - 1.0
+            p0 = pin.GetOrAddReal("problem", "p0", 1.0)
+            cs = math.sqrt(gamma*p0/rho0)
+        self.pgen_final_func = self.JeansWaveErrors
+        self.omega_measured = self.omega_analytical = None
+        if restart:
+            return
+        amp = pin.GetOrAddReal("problem", "amp", 1.0e-6)
+        v0 = pin.GetOrAddReal("problem", "v0", 0.0)
+        Lx1 = pin.GetReal("mesh", "x1max") - pin.GetReal("mesh", "x1min")
+        Lx2 = pin.GetReal("mesh", "x2max") - pin.GetReal("mesh", "x2min")
+        Lx3 = pin.GetReal("mesh", "x3max") - pin.GetReal("mesh", "x3min")
+        ang_3 = math.atan(Lx1/Lx2)
+        sin_a3, cos_a3 = math.sin(ang_3), math.cos(ang_3)
+        ang_2 = math.atan(0.5*(Lx1*cos_a3 + Lx2*sin_a3)/Lx3)
+        sin_a2, cos_a2 = math.sin(ang_2), math.cos(ang_2)
+        x1, x2, x3 = Lx1*cos_a2*cos_a3, Lx2*cos_a2*sin_a3, Lx3*sin_a2
+        lam = min(x1, min(x2, x3))
+        lambda_jeans = lam/n_jeans
+        if n_jeans > 0.0:
+            G = math.pi*(cs*cs)/(rho0*lambda_jeans*lambda_jeans)
+            four_pi_G = 4*math.pi*G
+            pin.SetReal("gravity", "four_pi_G", four_pi_G)
+            if pk.pgrav is not None:
+                pk.pgrav.four_pi_G = four_pi_G
+                pk.pgrav.pmgd.SetFourPiG(four_pi_G)
+        k_wave = 2.0*math.pi/lam
+        k_jeans = 2.0*math.pi/lambda_jeans
+        omega2 = k_wave**2*cs*cs*(1.0 - n_jeans**2)
+        omega = math.sqrt(abs(omega2))
+        self._jw = dict(rho0=rho0, amp=amp, k_wave=k_wave, omega=omega, n_jeans=n_jeans, cos_a2=cos_a2, cos_a3=cos_a3,
+                        sin_a2=sin_a2, sin_a3=sin_a3, v0=v0)
+        self.omega_analytical = omega
+        self.four_pi_G = four_pi_G
+        phys = self._phys()
+        n3, n2, n1 = pm.mb_indcs.ncells
+        nmb = pk.nmb_thispack
+        ks, js, is_ = self._active()
+        u = np.zeros((nmb, phys.nvars, n3, n2, n1))
+        b0_val = pin.GetOrAddReal("problem", "b0", 0.0) if use_mhd else 0.0
+        for m in range(nmb):
+            x1v, x2v, x3v = self._coords(m)[:3]
+            X3, X2, X1 = np.meshgrid(x3v, x2v, x1v, indexing="ij")
+            x = cos_a2*(X1*cos_a3 + X2*sin_a3) + X3*sin_a2
+            sinkx, coskx = np.sin(x*k_wave), np.cos(x*k_wave)
+            M = rho0*(omega/k_wave)*amp*coskx if n_jeans > 1.0 else np.zeros_like(x)
+            dens = rho0*(1.0 + amp*sinkx + amp*amp*np.sin(X1*k_wave))
+            m1 = M*cos_a3*cos_a2 + dens*v0*cos_a3*cos_a2
+            m2 = M*sin_a3*cos_a2 + dens*v0*sin_a3*cos_a2
+            m3 = M*sin_a2 + dens*v0*sin_a2
+            u[m, IDN][ks, js, is_] = dens
+            u[m, 1][ks, js, is_], u[m, 2][ks, js, is_], u[m, 3][ks, js, is_] = m1, m2, m3
+            if not is_isothermal:
+                e = p0/gm1*(1.0 + gamma*amp*sinkx)
+                e = e + 0.5*m1**2/dens
+                e = e + 0.5*m2**2/dens
+                e = e + 0.5*m3**2/dens
+                if use_mhd:
+                    e = e + 0.5*b0_val**2
+                u[m, IEN][ks, js, is_] = e
+        self._upload_cc(phys.u0, u)
+        if use_mhd:
+            _, bf = self._alloc_host()
+            bf[0][:, ks, js, is_.start:is_.stop + 1] = b0_val
+            self._upload_cc(phys.b0.x1f, bf[0])
+            self._upload_cc(phys.b0.x2f, bf[1])
+            self._upload_cc(phys.b0.x3f, bf[2])
+
+    def JeansWaveErrors(self):
+        """jeans_wave.cpp:355-447: the projection of the density perturbation on sin(k x) gives the frequency (stable)
+        or the growth rate (unstable)"""
+        pm = self.pmy_mesh_
+        pk = pm.pmb_pack
+        q = self._jw
+        ks, js, is_ = self._active()
+        u0 = self._phys().u0[:, IDN].cpu().numpy()
+        t = pm.time
+        sin_proj = 0.0
+        for m in range(pk.nmb_thispack):
+            x1v, x2v, x3v = self._coords(m)[:3]
+            sz = pk.pmb.mb_size[m]
+            vol = sz.dx1*sz.dx2*sz.dx3
+            X3, X2, X1 = np.meshgrid(x3v, x2v, x1v, indexing="ij")
+            x = q["cos_a2"]*(X1*q["cos_a3"] + X2*q["sin_a3"]) + X3*q["sin_a2"]
+            sin_proj += float(np.sum((u0[m][ks, js, is_]/q["rho0"] - 1.0)*np.sin(q["k_wave"]*(x - q["v0"]*t))*vol))
+        ms = pm.mesh_size
+        tvol = (ms.x1max - ms.x1min)*(ms.x2max - ms.x2min)*(ms.x3max - ms.x3min)
+        A_sin = 2.0*sin_proj/tvol
+        if q["n_jeans"] > 1.0:
+            omega_measured = math.log(abs(A_sin)/q["amp"])/t
+        else:
+            omega_measured = math.acos(max(-1.0, min(1.0, A_sin/q["amp"])))/t
+        self.omega_measured = omega_measured
+        print("=====================================================")
+        print("Jeans wave mode amplitude  : %.16e" % A_sin)
+        print("Jeans wave growth (A/amp)  : %.16e" % (A_sin/q["amp"]))
+        print("Jeans wave omega measured  : %.16e" % omega_measured)
+        print("Jeans wave omega analytical: %.16e" % q["omega"])
+        print("=====================================================")
+        return None
 
     # ---- Rayleigh-Taylor instability, src/pgen/fluids/rt.cpp:53-252 -------------------
     def RayleighTaylor(self, pin, restart):

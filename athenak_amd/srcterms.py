@@ -4,7 +4,8 @@
 On this path: const_accel (constant acceleration) and ism_cooling (optically thin ISM cooling and heating, ideal gas,
 needs <units>).  Both are applied by one kernel launch per stage (akmi_srcterms_apply, csrc/akmi_srcterms.hip) from
 the task `srctrms` between the RK update and the send of the conserved variables; the cooling time step comes from
-akmi_srcterms_newdt.  rel_cooling, self_gravity and rad_beam stop with a message.
+akmi_srcterms_newdt.  self_gravity (akmi_mg_selfgravity, csrc/akmi_mg.hip) comes after them and needs the <gravity>
+block (gravity.py); rel_cooling and rad_beam stop with a message, and so does self_gravity without <gravity>.
 """
 import ctypes as C
 
@@ -23,6 +24,8 @@ def srcterms_deck_checks(pin):
         if not (pin.DoesBlockExist(fluid) and pin.DoesBlockExist(blk)):
             continue
         for key in REFUSED:
+            if key == "self_gravity" and pin.DoesBlockExist("gravity"):
+                continue             # (the reference exits on the null pgrav without the block; with it the term is built)
             if pin.DoesParameterExist(blk, key) and pin.GetBoolean(blk, key):
                 raise RuntimeError("### FATAL ERROR <%s>/%s = true is not on this path (const_accel and ism_cooling "
                                    "are)" % (blk, key))
@@ -83,13 +86,30 @@ class SourceTerms:
 
     @property
     def active(self):
-        return self.const_accel or self.ism_cooling
+        return self.const_accel or self.ism_cooling or self.self_gravity
 
     def ApplySrcTerms(self, w0, bdt_beta, dt, u0):
-        """srcterms.cpp:93-101: bdt = beta*dt, formed in the kernel"""
+        """srcterms.cpp:93-101: bdt = beta*dt, formed in the kernel; SelfGravity last"""
         f = self.pmy_fluid
-        capi.check(f.L.akmi_srcterms_apply(C.byref(f.pack_c), C.byref(self.c), capi.d(bdt_beta), capi.d(dt), None,
-                                           capi._p(w0), capi._p(u0), capi._stream()), "srcterms_apply")
+        if self.const_accel or self.ism_cooling:
+            capi.check(f.L.akmi_srcterms_apply(C.byref(f.pack_c), C.byref(self.c), capi.d(bdt_beta), capi.d(dt), None,
+                                               capi._p(w0), capi._p(u0), capi._stream()), "srcterms_apply")
+        if self.self_gravity:
+            self.SelfGravity(w0, bdt_beta*dt, u0)
+
+    def SelfGravity(self, w0, bdt, u0):
+        """srcterms.cpp:215-310: phi of the last Solve, the Godunov mass fluxes of this stage (ideal gas)"""
+        f = self.pmy_fluid
+        pgrav = getattr(f.pmy_pack, "pgrav", None)
+        if pgrav is None:
+            raise RuntimeError("### ERROR in SourceTerms::SelfGravity\nself_gravity source term enabled but pgrav is null")
+        fl = f.uflx
+        if fl is None:
+            raise RuntimeError("### FATAL ERROR self_gravity needs the flux arrays of the task-granular path")
+        face = 1 if fl.x1f.shape[-1] == u0.shape[-1] + 1 else 0
+        capi.check(f.L.akmi_mg_selfgravity(C.byref(f.pack_c), face, capi.d(bdt), capi._p(w0), capi._p(pgrav.phi),
+                                           capi._p(fl.x1f), capi._p(fl.x2f), capi._p(fl.x3f), capi._p(u0),
+                                           capi._stream()), "mg_selfgravity")
 
     def NewTimeStep(self, w0):
         """srcterms_newdt.cpp:25-72"""

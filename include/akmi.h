@@ -997,6 +997,96 @@ int akmi_ionn_imp_update(int nmb, long long ncell, int nvar_i, int nvar_n, int n
                          double ionization_coeff, double recombination_coeff, double *ui, double *un, double *ru,
                          void *stream);
 
+/* ---- self-gravity: multigrid Poisson solver and its source term (akmi_mg.hip) ------------------
+ * One MG level is an array (nmb, 1, nz+2, ny+2, nx+2) of doubles: (nz, ny, nx) active cells and ONE ghost layer
+ * (mg_nghost = 1).  The MeshBlock levels have nz = ny = nx; the root grid is the same with nmb = 1.  dx is the cell
+ * width OF THAT LEVEL (block_rdx * 2^ll, multigrid.hpp:638).  Every operator keeps the roundings of the reference
+ * lines named with it and writes nothing but what is said. */
+/* Multigrid::Smooth + GravityStencil (multigrid.hpp:622-647, mg_gravity.hpp:25-36): the active cells with
+ * i = 1 + c, 3 + c, ..., c = ((color ^ coffset) + k + j) & 1 (k, j: array indices): u -= (lap - src*dx^2)*(omega/6) */
+int akmi_mg_smooth(int nmb, int nz, int ny, int nx, double dx, double omega, int color, int coffset, double *u,
+                   const double *src, void *stream);
+/* CalculateDefect / CalculateFASRHS (multigrid.hpp:271-312), active cells: def = src - lap*(1/(dx*dx));
+ * src += lap*(1/(dx*dx)) */
+int akmi_mg_defect(int nmb, int nz, int ny, int nx, double dx, const double *u, const double *src, double *def,
+                   void *stream);
+int akmi_mg_fas_rhs(int nmb, int nz, int ny, int nx, double dx, const double *u, double *src, void *stream);
+/* (nz, ny, nx) are the active cells of the COARSE level in the next three; the fine level has twice as many.
+ * Restrict (multigrid.cpp:874-894): coarse active cells; ProlongateAndCorrect, trilinear (:1053-1092): fine active
+ * cells +=, reads the coarse ghosts; FMGProlongate, tricubic (:1116-1218): fine active cells =, reads coarse ghosts */
+int akmi_mg_restrict(int nmb, int nz, int ny, int nx, const double *fine, double *coarse, void *stream);
+int akmi_mg_prolongate_correct(int nmb, int nz, int ny, int nx, const double *coarse, double *fine, void *stream);
+int akmi_mg_fmg_prolongate(int nmb, int nz, int ny, int nx, const double *coarse, double *fine, void *stream);
+/* StoreOldData (uold = u), ComputeCorrection (u -= uold), ZeroClearData, CopySourceToData (u = src): all n cells */
+int akmi_mg_store_old(long long n, double *uold, const double *u, void *stream);
+int akmi_mg_correction(long long n, double *u, const double *uold, void *stream);
+int akmi_mg_zero_clear(long long n, double *u, void *stream);
+int akmi_mg_copy_source(long long n, double *u, const double *src, void *stream);
+/* LoadSource (multigrid.cpp:289-320): src(all cells, ghosts included) = u0(variable 0)*fac, u0 (nmb, nvar, n+2ng..);
+ * LoadFinestData (:261-281): u(active) = phi; RetrieveResult (:420-451): phi(n+2 cells per direction) = u.
+ * phi: (nmb, 1, nz+2ng, ny+2ng, nx+2ng) */
+int akmi_mg_load_source(int nmb, int nz, int ny, int nx, int ng, int nvar, double fac, const double *u0, double *src,
+                        void *stream);
+int akmi_mg_load_finest(int nmb, int nz, int ny, int nx, int ng, const double *phi, double *u, void *stream);
+int akmi_mg_retrieve(int nmb, int nz, int ny, int nx, int ng, const double *u, double *phi, void *stream);
+/* The sums have one order: a row (m, k, j) ascending in i, the rows of a plane ascending in j, the planes of a block
+ * ascending in k, the blocks ascending in m.  scratch: akmi_mg_reduce_scratch_doubles() doubles; out: one double.
+ * CalculateAverage (multigrid.cpp:763-818): sum(a*dx^3)/(nmb*len^3), len = edge of a block as the reference forms it;
+ * SubtractAverage (:824-852): a[0..n) -= *ave; defect norm, l2 (:683-757, multigrid_driver.cpp:908-937):
+ * sqrt(sum(def^2)/vol) */
+long long akmi_mg_reduce_scratch_doubles(int nmb, int nz, int ny, int nx);
+int akmi_mg_average(int nmb, int nz, int ny, int nx, double dx, double len, const double *a, double *scratch,
+                    double *out, void *stream);
+int akmi_mg_subtract_average(long long n, double *a, const double *ave, void *stream);
+int akmi_mg_defect_norm(int nmb, int nz, int ny, int nx, double vol, const double *def, double *scratch, double *out,
+                        void *stream);
+/* periodic ghost exchange of one level, one launch: every ghost cell (faces, edges, corners) = the active cell it is
+ * the image of in MeshBlock nghbr[m*27 + (ox3+1)*9 + (ox2+1)*3 + (ox1+1)] (device ints; the block itself where it is
+ * its own neighbour; < 0: left alone).  MGRootBoundary for periodic faces is the same with the grid as its own
+ * neighbour everywhere (multigrid_driver.cpp:1835-1930). */
+int akmi_mg_exchange(int nmb, int nz, int ny, int nx, const int *nghbr, double *u, void *stream);
+int akmi_mg_root_boundary(int nz, int ny, int nx, double *u, void *stream);
+/* TransferFromBlocksToRoot (multigrid_driver.cpp:479-548) / SetFromRootGrid (multigrid.cpp:617-676): (nz, ny, nx) the
+ * root grid, lloc device ints (lx1, lx2, lx3) per block; the blocks' arrays are those of the 1-cell level (27 doubles
+ * per block).  initflag: the source alone; folddata: uold too */
+int akmi_mg_blocks_to_root(int nmb, int nz, int ny, int nx, const int *lloc, int initflag, const double *bsrc,
+                           const double *bu, double *rsrc, double *ru, void *stream);
+int akmi_mg_set_from_root(int nmb, int nz, int ny, int nx, const int *lloc, int folddata, const double *ru,
+                          const double *ruold, double *bu, double *buold, void *stream);
+/* SourceTerms::SelfGravity (srcterms.cpp:215-310), one launch, per cell x1 then x2 then x3.  phi: (nmb, 1, cells of
+ * the pack); flx*: the mass fluxes are variable 0 of the flux arrays of the task-granular path, face_shaped != 0:
+ * (.., n1+1) / (.., n2+1, n1) / (n3+1, ..); read for the ideal gas only */
+int akmi_mg_selfgravity(const akmi_pack *p, int face_shaped, double bdt, const double *w0, const double *phi,
+                        const double *flx1, const double *flx2, const double *flx3, double *u0, void *stream);
+
+#define AKMI_MG_NNORMS 42
+/* one rank, uniform mesh, periodic: the MeshBlocks tile the root grid nrx1 x nrx2 x nrx3 */
+typedef struct akmi_mg_plan {
+  int nmb, nxb;                        /* MeshBlocks of the pack; edge of a MeshBlock (power of two) */
+  int nrx1, nrx2, nrx3;                /* root grid */
+  int nmblevel, nrootlevel;            /* multigrid.cpp:100-145 */
+  int ng, nvar;                        /* ghost cells and variables of the fluid's u0 (phi: same ng) */
+  int npresmooth, npostsmooth, niter, full_multigrid, fmg_ncycle, subtract_average, show_defect;
+  double rdx, root_dx;                 /* cell width of the finest block level / of the finest root level */
+  double omega, four_pi_G, eps, vol;   /* eps: threshold (< 0: niter V-cycles); vol: volume of the mesh */
+  const int *nghbr;                    /* device, nmb*27, as akmi_mg_exchange */
+  const int *lloc;                     /* device, nmb*3 */
+  double *ws;                          /* device, akmi_mg_workspace_doubles(); keeps u between calls */
+} akmi_mg_plan;
+long long akmi_mg_workspace_doubles(const akmi_mg_plan *plan);
+/* offset (doubles) into ws of array `which` (0 u, 1 src, 2 def, 3 uold) of MeshBlock level / root level `level` */
+long long akmi_mg_level_offset(const akmi_mg_plan *plan, int is_root, int level, int which);
+/* MGGravityDriver::Solve (mg_gravity.cpp:177-245) enqueued as a whole: LoadSource(-four_pi_G), the initial guess from
+ * phi unless full_multigrid, SolveFMG / SolveMG, RetrieveResult into phi.  *coffset: the red-black offset, carried
+ * from call to call.  norms (host, AKMI_MG_NNORMS doubles, -1 = not computed): [0] initial defect, [1 + n] after
+ * V-cycle n of SolveMG (threshold >= 0, or show_defect >= 2), [41] final (show_defect >= 1).  *ncycles: V-cycles of
+ * SolveMG; 40 with the last norm above eps = the reference's "Failed to converge".  The stream is synchronised only
+ * where a norm is read. */
+int akmi_mg_solve(const akmi_mg_plan *plan, const double *u0, double *phi, int *coffset, double *norms, int *ncycles,
+                  void *stream);
+/* kernel launches this unit has enqueued since the last reset */
+long long akmi_mg_launch_count(int reset);
+
 #ifdef __cplusplus
 }
 #endif
