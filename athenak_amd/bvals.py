@@ -11,8 +11,6 @@ Segment order inside a peer message is fixed by (receiver gid, receiver directio
 to both sides from the block tables alone, which replaces the reference's one-shot header
 exchange (src/bvals/bvals.cpp:248-270).
 """
-import ctypes as C
-
 import numpy as np
 import torch
 
@@ -27,45 +25,38 @@ class HipBvalsKernels:
         self.L = capi.lib()
 
     def cc_segsize(self, pack, d):
-        return int(self.L.akmi_bvals_cc_segsize(C.byref(pack), d))
+        return int(self.L.akmi_bvals_cc_segsize(pack, d))
 
     def fc_segsize(self, pack, d):
-        return int(self.L.akmi_bvals_fc_segsize(C.byref(pack), d))
+        return int(self.L.akmi_bvals_fc_segsize(pack, d))
 
     def cc_local(self, pack, nvar, nghbr, u):
-        capi.check(self.L.akmi_bvals_cc_local(C.byref(pack), nvar, capi._p(nghbr), capi._p(u),
-                                              capi._stream()), "bvals_cc_local")
+        capi.check(self.L.akmi_bvals_cc_local(pack, nvar, nghbr, u, capi._stream()), "bvals_cc_local")
 
     def cc_local_bcs(self, pack, nvar, nghbr, bcs, u, u_in=None, dt3_reset=None):
         """the gather and the physical boundary functions in one launch (packs without off-rank neighbours)"""
-        capi.check(self.L.akmi_bvals_cc_local_bcs(C.byref(pack), nvar, capi._p(nghbr), capi._p(bcs), capi._p(u_in),
-                                                  capi._p(u), capi._p(dt3_reset), capi._stream()), "bvals_cc_local_bcs")
+        capi.check(self.L.akmi_bvals_cc_local_bcs(pack, nvar, nghbr, bcs, u_in, u, dt3_reset, capi._stream()),
+                   "bvals_cc_local_bcs")
 
     def fc_local_bcs(self, pack, nghbr, bcs, b1, b2, b3, b_in=None):
-        capi.check(self.L.akmi_bvals_fc_local_bcs(C.byref(pack), capi._p(nghbr), capi._p(bcs), capi._p(b_in), capi._p(b1),
-                                                  capi._p(b2), capi._p(b3), capi._stream()), "bvals_fc_local_bcs")
+        capi.check(self.L.akmi_bvals_fc_local_bcs(pack, nghbr, bcs, b_in, b1, b2, b3, capi._stream()),
+                   "bvals_fc_local_bcs")
 
     def cc_pack(self, pack, nvar, nsend, tab, off, u, buf):
-        capi.check(self.L.akmi_bvals_cc_pack(C.byref(pack), nvar, nsend, capi._p(tab), capi._p(off),
-                                             capi._p(u), capi._p(buf), capi._stream()), "bvals_cc_pack")
+        capi.check(self.L.akmi_bvals_cc_pack(pack, nvar, nsend, tab, off, u, buf, capi._stream()), "bvals_cc_pack")
 
     def cc_unpack(self, pack, nvar, nghbr, seg_off, buf, u):
-        capi.check(self.L.akmi_bvals_cc_unpack(C.byref(pack), nvar, capi._p(nghbr), capi._p(seg_off),
-                                               capi._p(buf), capi._p(u), capi._stream()), "bvals_cc_unpack")
+        capi.check(self.L.akmi_bvals_cc_unpack(pack, nvar, nghbr, seg_off, buf, u, capi._stream()), "bvals_cc_unpack")
 
     def fc_local(self, pack, nghbr, b1, b2, b3):
-        capi.check(self.L.akmi_bvals_fc_local(C.byref(pack), capi._p(nghbr), capi._p(b1), capi._p(b2),
-                                              capi._p(b3), capi._stream()), "bvals_fc_local")
+        capi.check(self.L.akmi_bvals_fc_local(pack, nghbr, b1, b2, b3, capi._stream()), "bvals_fc_local")
 
     def fc_pack(self, pack, nsend, tab, off, b1, b2, b3, buf):
-        capi.check(self.L.akmi_bvals_fc_pack(C.byref(pack), nsend, capi._p(tab), capi._p(off),
-                                             capi._p(b1), capi._p(b2), capi._p(b3), capi._p(buf),
-                                             capi._stream()), "bvals_fc_pack")
+        capi.check(self.L.akmi_bvals_fc_pack(pack, nsend, tab, off, b1, b2, b3, buf, capi._stream()), "bvals_fc_pack")
 
     def fc_unpack(self, pack, nghbr, seg_off, buf, b1, b2, b3):
-        capi.check(self.L.akmi_bvals_fc_unpack(C.byref(pack), capi._p(nghbr), capi._p(seg_off),
-                                               capi._p(buf), capi._p(b1), capi._p(b2), capi._p(b3),
-                                               capi._stream()), "bvals_fc_unpack")
+        capi.check(self.L.akmi_bvals_fc_unpack(pack, nghbr, seg_off, buf, b1, b2, b3, capi._stream()),
+                   "bvals_fc_unpack")
 
     def _dirs(self, bcs):
         """bit d set: some MeshBlock has a physical boundary across direction d (anything but block / periodic); the
@@ -79,12 +70,11 @@ class HipBvalsKernels:
         return mask
 
     def hydro_bcs(self, pack, nvar, bcs, u, u_in=None):
-        capi.check(self.L.akmi_hydro_bcs_dirs(C.byref(pack), nvar, capi._p(bcs), self._dirs(bcs), capi._p(u_in),
-                                              capi._p(u), capi._stream()), "hydro_bcs")
+        capi.check(self.L.akmi_hydro_bcs_dirs(pack, nvar, bcs, self._dirs(bcs), u_in, u, capi._stream()), "hydro_bcs")
 
     def bfield_bcs(self, pack, bcs, b1, b2, b3, b_in=None):
-        capi.check(self.L.akmi_bfield_bcs_dirs(C.byref(pack), capi._p(bcs), self._dirs(bcs), capi._p(b_in), capi._p(b1),
-                                               capi._p(b2), capi._p(b3), capi._stream()), "bfield_bcs")
+        capi.check(self.L.akmi_bfield_bcs_dirs(pack, bcs, self._dirs(bcs), b_in, b1, b2, b3, capi._stream()),
+                   "bfield_bcs")
 
 
 class HaloProfile:

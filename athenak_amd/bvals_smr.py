@@ -225,92 +225,73 @@ class HipSmrKernels:
         capi.check(getattr(self.L, name)(*args), name)
 
     def exchange_cc(self, pack, smr, nvar, u, cu, buf):
-        self._call("akmi_smr_exchange_cc", C.byref(pack), C.byref(smr), nvar, capi._p(u), capi._p(cu),
-                   capi._p(buf), capi._stream())
+        self._call("akmi_smr_exchange_cc", pack, smr, nvar, u, cu, buf, capi._stream())
 
     def exchange_fc(self, pack, smr, b, cb, buf):
-        self._call("akmi_smr_exchange_fc", C.byref(pack), C.byref(smr), capi._p(b.x1f), capi._p(b.x2f),
-                   capi._p(b.x3f), capi._p(cb.x1f), capi._p(cb.x2f), capi._p(cb.x3f), capi._p(buf),
-                   capi._stream())
+        self._call("akmi_smr_exchange_fc", pack, smr, b.x1f, b.x2f, b.x3f, cb.x1f, cb.x2f, cb.x3f, buf, capi._stream())
 
     def fill_coarse_cc(self, pack, smr, nvar, u, cu):
-        self._call("akmi_smr_fill_coarse_cc", C.byref(pack), C.byref(smr), nvar, capi._p(u), capi._p(cu),
-                   capi._stream())
+        self._call("akmi_smr_fill_coarse_cc", pack, smr, nvar, u, cu, capi._stream())
 
     def fill_coarse_fc(self, pack, smr, b, cb):
-        self._call("akmi_smr_fill_coarse_fc", C.byref(pack), C.byref(smr), capi._p(b.x1f), capi._p(b.x2f),
-                   capi._p(b.x3f), capi._p(cb.x1f), capi._p(cb.x2f), capi._p(cb.x3f), capi._stream())
+        self._call("akmi_smr_fill_coarse_fc", pack, smr, b.x1f, b.x2f, b.x3f, cb.x1f, cb.x2f, cb.x3f, capi._stream())
 
     def prolong_cc(self, pack, smr, nvar, cu, u):
-        self._call("akmi_smr_prolong_cc", C.byref(pack), C.byref(smr), nvar, capi._p(cu), capi._p(u),
-                   capi._stream())
+        self._call("akmi_smr_prolong_cc", pack, smr, nvar, cu, u, capi._stream())
 
     def c2p_coarse(self, pack, smr, nvar, cu, cb, cw):
-        f = (capi._p(cb.x1f), capi._p(cb.x2f), capi._p(cb.x3f)) if cb is not None else (None, None, None)
-        self._call("akmi_smr_c2p_coarse", C.byref(pack), C.byref(smr), nvar, capi._p(cu), *f, capi._p(cw),
-                   capi._stream())
+        f = (cb.x1f, cb.x2f, cb.x3f) if cb is not None else (None, None, None)
+        self._call("akmi_smr_c2p_coarse", pack, smr, nvar, cu, *f, cw, capi._stream())
 
     def p2c_fine(self, pack, smr, nvar, w, b, u):
-        f = (capi._p(b.x1f), capi._p(b.x2f), capi._p(b.x3f)) if b is not None else (None, None, None)
-        self._call("akmi_smr_p2c_fine", C.byref(pack), C.byref(smr), nvar, capi._p(w), *f, capi._p(u),
-                   capi._stream())
+        f = (b.x1f, b.x2f, b.x3f) if b is not None else (None, None, None)
+        self._call("akmi_smr_p2c_fine", pack, smr, nvar, w, *f, u, capi._stream())
 
     def gather_same(self, pack, nvar, tab27, u):
-        self._call("akmi_bvals_cc_local", C.byref(pack), nvar, capi._p(tab27), capi._p(u), capi._stream())
+        self._call("akmi_bvals_cc_local", pack, nvar, tab27, u, capi._stream())
 
     def prolong_fc(self, pack, smr, cb, b):
-        self._call("akmi_smr_prolong_fc", C.byref(pack), C.byref(smr), capi._p(cb.x1f), capi._p(cb.x2f),
-                   capi._p(cb.x3f), capi._p(b.x1f), capi._p(b.x2f), capi._p(b.x3f), capi._stream())
+        self._call("akmi_smr_prolong_fc", pack, smr, cb.x1f, cb.x2f, cb.x3f, b.x1f, b.x2f, b.x3f, capi._stream())
 
     def flux_cc(self, pack, smr, nvar, face_shaped, flx, buf):
-        self._call("akmi_smr_flux_cc", C.byref(pack), C.byref(smr), nvar, int(face_shaped), capi._p(flx.x1f),
-                   capi._p(flx.x2f), capi._p(flx.x3f), capi._p(buf), capi._stream())
+        self._call("akmi_smr_flux_cc", pack, smr, nvar, int(face_shaped), flx.x1f, flx.x2f, flx.x3f, buf,
+                   capi._stream())
 
     def emf_exchange(self, pack, smr, nflx, efld, buf):
-        self._call("akmi_smr_emf_exchange", C.byref(pack), C.byref(smr), capi._p(nflx), capi._p(efld.x1e),
-                   capi._p(efld.x2e), capi._p(efld.x3e), capi._p(buf), capi._stream())
+        self._call("akmi_smr_emf_exchange", pack, smr, nflx, efld.x1e, efld.x2e, efld.x3e, buf, capi._stream())
 
     # the two halves of each exchange (PackAndSend* | RecvAndUnpack*): messages travel in between
     def pack_cc(self, pack, smr, nvar, u, cu, buf):
-        self._call("akmi_smr_pack_cc", C.byref(pack), C.byref(smr), nvar, capi._p(u), capi._p(cu), capi._p(buf),
-                   capi._stream())
+        self._call("akmi_smr_pack_cc", pack, smr, nvar, u, cu, buf, capi._stream())
 
     def unpack_cc(self, pack, smr, nvar, buf, u, cu):
-        self._call("akmi_smr_unpack_cc", C.byref(pack), C.byref(smr), nvar, capi._p(buf), capi._p(u), capi._p(cu),
-                   capi._stream())
+        self._call("akmi_smr_unpack_cc", pack, smr, nvar, buf, u, cu, capi._stream())
 
     def pack_fc(self, pack, smr, b, cb, buf):
-        self._call("akmi_smr_pack_fc", C.byref(pack), C.byref(smr), capi._p(b.x1f), capi._p(b.x2f), capi._p(b.x3f),
-                   capi._p(cb.x1f), capi._p(cb.x2f), capi._p(cb.x3f), capi._p(buf), capi._stream())
+        self._call("akmi_smr_pack_fc", pack, smr, b.x1f, b.x2f, b.x3f, cb.x1f, cb.x2f, cb.x3f, buf, capi._stream())
 
     def unpack_fc(self, pack, smr, buf, b, cb):
-        self._call("akmi_smr_unpack_fc", C.byref(pack), C.byref(smr), capi._p(buf), capi._p(b.x1f), capi._p(b.x2f),
-                   capi._p(b.x3f), capi._p(cb.x1f), capi._p(cb.x2f), capi._p(cb.x3f), capi._stream())
+        self._call("akmi_smr_unpack_fc", pack, smr, buf, b.x1f, b.x2f, b.x3f, cb.x1f, cb.x2f, cb.x3f, capi._stream())
 
     def pack_flux_cc(self, pack, smr, nvar, face_shaped, flx, buf):
-        self._call("akmi_smr_pack_flux_cc", C.byref(pack), C.byref(smr), nvar, 1 if face_shaped else 0,
-                   capi._p(flx.x1f), capi._p(flx.x2f), capi._p(flx.x3f), capi._p(buf), capi._stream())
+        self._call("akmi_smr_pack_flux_cc", pack, smr, nvar, 1 if face_shaped else 0, flx.x1f, flx.x2f, flx.x3f, buf,
+                   capi._stream())
 
     def unpack_flux_cc(self, pack, smr, nvar, face_shaped, buf, flx):
-        self._call("akmi_smr_unpack_flux_cc", C.byref(pack), C.byref(smr), nvar, 1 if face_shaped else 0,
-                   capi._p(buf), capi._p(flx.x1f), capi._p(flx.x2f), capi._p(flx.x3f), capi._stream())
+        self._call("akmi_smr_unpack_flux_cc", pack, smr, nvar, 1 if face_shaped else 0, buf, flx.x1f, flx.x2f, flx.x3f,
+                   capi._stream())
 
     def pack_emf(self, pack, smr, efld, buf):
-        self._call("akmi_smr_pack_emf", C.byref(pack), C.byref(smr), capi._p(efld.x1e), capi._p(efld.x2e),
-                   capi._p(efld.x3e), capi._p(buf), capi._stream())
+        self._call("akmi_smr_pack_emf", pack, smr, efld.x1e, efld.x2e, efld.x3e, buf, capi._stream())
 
     def unpack_emf(self, pack, smr, nflx, buf, efld):
-        self._call("akmi_smr_unpack_emf", C.byref(pack), C.byref(smr), capi._p(nflx), capi._p(buf),
-                   capi._p(efld.x1e), capi._p(efld.x2e), capi._p(efld.x3e), capi._stream())
+        self._call("akmi_smr_unpack_emf", pack, smr, nflx, buf, efld.x1e, efld.x2e, efld.x3e, capi._stream())
 
     def restrict_cc(self, pack, nvar, u, cu, mask=None):
-        self._call("akmi_restrict_cc_masked", C.byref(pack), nvar, capi._p(mask) if mask is not None else None,
-                   capi._p(u), capi._p(cu), capi._stream())
+        self._call("akmi_restrict_cc_masked", pack, nvar, mask, u, cu, capi._stream())
 
     def restrict_fc(self, pack, b, cb, mask=None):
-        self._call("akmi_restrict_fc_masked", C.byref(pack), capi._p(mask) if mask is not None else None,
-                   capi._p(b.x1f), capi._p(b.x2f), capi._p(b.x3f),
-                   capi._p(cb.x1f), capi._p(cb.x2f), capi._p(cb.x3f), capi._stream())
+        self._call("akmi_restrict_fc_masked", pack, mask, b.x1f, b.x2f, b.x3f, cb.x1f, cb.x2f, cb.x3f, capi._stream())
 
 
 
@@ -520,8 +501,8 @@ class MeshBoundaryValuesSMR:
             nmb = int(pack_c.nmb)
             self.t_lists = torch.zeros(2*nmb*56*6, dtype=torch.int32, device=self.device)
             cnt = (C.c_int*6)()
-            capi.check(capi.lib().akmi_smr_build_lists(C.byref(pack_c), C.byref(self.smr_c), capi._p(self.t_lists), cnt,
-                                                       capi._stream()), "smr_build_lists")
+            capi.check(capi.lib().akmi_smr_build_lists(pack_c, self.smr_c, self.t_lists, cnt, capi._stream()),
+                       "smr_build_lists")
             self.smr_c.lists = self.t_lists.data_ptr()
             for q in range(6):
                 self.smr_c.list_cnt[q] = cnt[q]
@@ -545,14 +526,12 @@ class MeshBoundaryValuesSMR:
                 def build():
                     import torch
                     L, buf = capi.lib(), self.buf[0]
-                    args = (C.byref(self.pack_c), C.byref(self.smr_c), self.nvar, capi._p(self.t_same), capi._p(buf),
-                            C.c_longlong(int(buf.numel())))
+                    args = (self.pack_c, self.smr_c, self.nvar, self.t_same, buf, int(buf.numel()))
                     tail = C.c_longlong(0)
-                    n = int(L.akmi_smr_cc_map(*args, None, C.c_longlong(0), C.byref(tail), capi._stream()))
+                    n = int(L.akmi_smr_cc_map(*args, None, 0, C.byref(tail), capi._stream()))
                     capi.check(n, "smr_cc_map")
                     m = torch.zeros(max(2*n, 2), dtype=torch.int32, device=self.device)
-                    capi.check(int(L.akmi_smr_cc_map(*args, capi._p(m), C.c_longlong(n), C.byref(tail), capi._stream())),
-                               "smr_cc_map")
+                    capi.check(int(L.akmi_smr_cc_map(*args, m, n, C.byref(tail), capi._stream())), "smr_cc_map")
                     return (m, n, int(tail.value))
                 self._ccmap = _map_or_fallback(build, "CC")
         return self._ccmap
@@ -567,8 +546,7 @@ class MeshBoundaryValuesSMR:
         self._wait(0)
         if self._cc_maps():
             m, n, tail = self._ccmap
-            capi.check(capi.lib().akmi_smr_cc_copy(C.byref(self.pack_c), self.nvar, capi._p(m), C.c_longlong(n),
-                                                   C.c_longlong(tail), capi._p(u), capi._p(cu), capi._stream()),
+            capi.check(capi.lib().akmi_smr_cc_copy(self.pack_c, self.nvar, m, n, tail, u, cu, capi._stream()),
                        "smr_cc_copy")
             return TaskStatus.complete
         self.k.unpack_cc(self.pack_c, self.smr_c, self.nvar, self.buf[0], u, cu)
@@ -590,14 +568,12 @@ class MeshBoundaryValuesSMR:
                     lo = min([a for (a, _) in self.send_slices[2].values()], default=nb) if self.peers else nb
                     maps = []
                     for which in (0, 1):
-                        args = (C.byref(self.pack_c), C.byref(self.smr_c), capi._p(buf), C.c_longlong(nb), C.c_longlong(lo),
-                                C.c_longlong(nb), which)
+                        args = (self.pack_c, self.smr_c, buf, nb, lo, nb, which)
                         tail = C.c_longlong(0)
-                        n = int(L.akmi_smr_fc_map(*args, None, C.c_longlong(0), C.byref(tail), capi._stream()))
+                        n = int(L.akmi_smr_fc_map(*args, None, 0, C.byref(tail), capi._stream()))
                         capi.check(n, "smr_fc_map")
                         m = torch.zeros(max(2*n, 2), dtype=torch.int32, device=self.device)
-                        capi.check(int(L.akmi_smr_fc_map(*args, capi._p(m), C.c_longlong(n), C.byref(tail), capi._stream())),
-                                   "smr_fc_map")
+                        capi.check(int(L.akmi_smr_fc_map(*args, m, n, C.byref(tail), capi._stream())), "smr_fc_map")
                         maps.append((m, n, int(tail.value)))
                     return maps
                 self._fcmap = _map_or_fallback(build, "FC")
@@ -606,9 +582,7 @@ class MeshBoundaryValuesSMR:
     def _fc_copy(self, which, b, cb):
         m, n, tail = self._fcmap[which]
         capi.check(capi.lib().akmi_smr_fc_copy(
-            C.byref(self.pack_c), capi._p(m), C.c_longlong(n), C.c_longlong(tail), C.c_longlong(int(self.buf[2].numel())),
-            capi._p(b.x1f),
-            capi._p(b.x2f), capi._p(b.x3f), capi._p(cb.x1f), capi._p(cb.x2f), capi._p(cb.x3f), capi._p(self.buf[2]),
+            self.pack_c, m, n, tail, int(self.buf[2].numel()), b.x1f, b.x2f, b.x3f, cb.x1f, cb.x2f, cb.x3f, self.buf[2],
             capi._stream()), "smr_fc_copy")
 
     def PackAndSendFC(self, b, cb):

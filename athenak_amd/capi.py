@@ -6,10 +6,13 @@ missing or a call fails, an exception is raised.
 """
 import ctypes as C
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # AKMI_LIB: developer override used by tools/kbench.py to A/B kernel variants
 LIB_PATH = os.environ.get("AKMI_LIB") or os.path.join(_HERE, "lib", "libakmi.so")
+# the one declaration of the C ABI: lib() types every entry from it
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "akmi.h")
 
 RECON = {"dc": 0, "plm": 1, "ppm4": 2, "ppmx": 3, "wenoz": 4, "teno": 5}
 RSOLVER = {"llf": 0, "hlle": 1, "hllc": 2, "hlld": 3, "roe": 4, "advect": 5}
@@ -29,47 +32,8 @@ class Pack(C.Structure):
 
 
 PHASE_SWEEPS, PHASE_EMF_CT, PHASE_C2P, PHASE_ALL = 1, 2, 4, 7     # AKMI_PHASE_* of include/akmi.h
-SMALL_PACK_CELLS = 375000       # AKMI_SMALL_PACK_CELLS of include/akmi.h (tests/test_capi_symbols.py compares them)
-
-# every symbol include/akmi.h declares (checked by tests/test_capi_symbols.py)
-SYMBOLS = [
-    "akmi_last_error", "akmi_version", "akmi_build_flags", "akmi_copy_cons", "akmi_rk4_copy_cons", "akmi_hydro_fluxes_fofc", "akmi_hydro_fofc", "akmi_mhd_fluxes_fofc", "akmi_mhd_fofc", "akmi_kinematic_newdt", "akmi_ambipolar_emfs", "akmi_ambipolar_fluxes", "akmi_resistive_newdt", "akmi_restrict_cc", "akmi_restrict_fc", "akmi_restrict_cc_masked", "akmi_restrict_fc_masked", "akmi_restrict_flux_cc", "akmi_restrict_emf", "akmi_prim2cons", "akmi_prolong_cc", "akmi_prolong_fc_shared", "akmi_prolong_fc_internal", "akmi_hydro_bcs_inflow", "akmi_bfield_bcs_inflow", "akmi_hydro_bcs_dirs", "akmi_bfield_bcs_dirs", "akmi_viscous_fluxes", "akmi_heat_fluxes", "akmi_conduction_newdt", "akmi_resistive_emfs", "akmi_resistive_fluxes", "akmi_hydro_fluxes", "akmi_rk_update", "akmi_rk_update_oop", "akmi_mhd_ct_oop",
-    "akmi_hydro_c2p", "akmi_hydro_newdt", "akmi_mhd_fluxes", "akmi_mhd_corner_e", "akmi_mhd_ct",
-    "akmi_mhd_c2p", "akmi_mhd_newdt", "akmi_bvals_cc_local", "akmi_bvals_cc_local_bcs", "akmi_bvals_fc_local_bcs", "akmi_bvals_cc_pack",
-    "akmi_bvals_cc_unpack", "akmi_bvals_cc_segsize", "akmi_bvals_fc_local", "akmi_bvals_fc_pack",
-    "akmi_bvals_fc_unpack", "akmi_bvals_fc_segsize", "akmi_hydro_bcs", "akmi_bfield_bcs",
-    "akmi_stage_workspace_bytes", "akmi_hydro_stage_update", "akmi_mhd_stage_update",
-    "akmi_hydro_c2p_newdt", "akmi_mhd_c2p_newdt", "akmi_calib_copy", "akmi_hydro_stage_fused", "akmi_mhd_stage_fused",
-    "akmi_hydro_stage_phase", "akmi_mhd_stage_phase", "akmi_hydro_stage_phase_dt", "akmi_mhd_stage_phase_dt", "akmi_history_sums",
-    "akmi_hydro_c2p_shell", "akmi_mhd_c2p_shell", "akmi_sim_create", "akmi_sim_initialize",
-    "akmi_sim_execute", "akmi_sim_profile", "akmi_sim_profile_read", "akmi_sim_destroy", "akmi_sim_time", "akmi_sim_dt", "akmi_sim_tlim",
-    "akmi_sim_ncycle", "akmi_sim_nmb", "akmi_sim_array", "akmi_sim_lloc", "akmi_sim_gids", "akmi_sim_nmb_thisrank",
-    "akmi_comm_unique_id", "akmi_comm_init_rccl", "akmi_comm_init_env", "akmi_comm_init_callbacks", "akmi_hydro_stage_fused_dt", "akmi_mhd_stage_fused_dt", "akmi_comm_finalize", "akmi_comm_allreduce_min",
-    "akmi_hydro_stage_w_eligible", "akmi_hydro_stage_w", "akmi_hydro_ghost_uw", "akmi_comm_rank", "akmi_comm_nranks", "akmi_comm_profile", "akmi_comm_profile_read", "akmi_host_exchange_plan", "akmi_host_device_bytes",
-    "akmi_smr_exchange_cc", "akmi_smr_exchange_fc", "akmi_smr_fill_coarse_cc", "akmi_smr_fill_coarse_fc",
-    "akmi_smr_prolong_cc", "akmi_smr_prolong_fc", "akmi_smr_c2p_coarse", "akmi_smr_p2c_fine", "akmi_smr_build_lists", "akmi_smr_flux_cc", "akmi_smr_emf_exchange", "akmi_smr_pack_cc", "akmi_smr_unpack_cc", "akmi_smr_pack_fc",
-    "akmi_selftest_fp64",
-    "akmi_smr_fc_map", "akmi_smr_fc_copy", "akmi_smr_cc_map", "akmi_smr_cc_copy",
-    "akmi_smr_unpack_fc", "akmi_smr_pack_flux_cc", "akmi_smr_unpack_flux_cc", "akmi_smr_pack_emf", "akmi_smr_unpack_emf",
-    "akmi_rng_uniform", "akmi_rng_gaussian", "akmi_rng_state_bytes", "akmi_turb_mode_count", "akmi_turb_amplitudes",
-    "akmi_turb_tables", "akmi_turb_workspace_bytes", "akmi_turb_synthesize", "akmi_turb_moments", "akmi_turb_add_forcing",
-    "akmi_turb_remove_net_mom",
-    "akmi_srcterms_apply", "akmi_srcterms_newdt", "akmi_srcterms_from_deck",
-    "akmi_derived_ncomp", "akmi_derived_var", "akmi_sim_derived",
-    "akmi_turb_history_workspace_bytes", "akmi_turb_history", "akmi_sim_turb_history", "akmi_pdf", "akmi_pdf_lds_bins",
-    "akmi_sim_pdf",
-    "akmi_coarsen", "akmi_coarsen_default_staged", "akmi_sim_coarsen",
-    "akmi_stage_last_forms", "akmi_mhd_u0_sweeps_eligible", "akmi_sim_stage_forms", "akmi_sim_counters",
-    "akmi_mhd_c2p_newdt_lean", "akmi_mhd_prims_fill", "akmi_mhd_c2p_takes_pairs",
-    "akmi_amr_check", "akmi_amr_regrid_cc", "akmi_amr_regrid_fc", "akmi_amr_repair_fc",
-    "akmi_ionn_imp_update",
-    "akmi_mg_smooth", "akmi_mg_defect", "akmi_mg_fas_rhs", "akmi_mg_restrict", "akmi_mg_prolongate_correct",
-    "akmi_mg_fmg_prolongate", "akmi_mg_store_old", "akmi_mg_correction", "akmi_mg_zero_clear", "akmi_mg_copy_source",
-    "akmi_mg_load_source", "akmi_mg_load_finest", "akmi_mg_retrieve", "akmi_mg_reduce_scratch_doubles",
-    "akmi_mg_average", "akmi_mg_subtract_average", "akmi_mg_defect_norm", "akmi_mg_exchange", "akmi_mg_root_boundary",
-    "akmi_mg_blocks_to_root", "akmi_mg_set_from_root", "akmi_mg_selfgravity", "akmi_mg_workspace_doubles",
-    "akmi_mg_level_offset", "akmi_mg_solve", "akmi_mg_launch_count",
-]
+SMALL_PACK_CELLS = 375000       # AKMI_SMALL_PACK_CELLS of include/akmi.h
+# (tests/test_capi_symbols.py compares every constant mirrored here with the header)
 
 AMR_METHOD = {"min_max": 0, "slope": 1, "second_deriv": 2}               # AKMI_AMR_* of include/akmi.h
 
@@ -139,39 +103,135 @@ class AkmiError(RuntimeError):
     pass
 
 
+_CTYPES = {"int": C.c_int, "long long": C.c_longlong, "unsigned long long": C.c_ulonglong, "double": C.c_double}
+_RESTYPES = dict(_CTYPES, **{"void": None, "void *": C.c_void_p, "const char *": C.c_char_p,
+                             "const int *": C.POINTER(C.c_int)})
+_FN_TYPEDEFS = ("akmi_comm_exchange_fn", "akmi_comm_allreduce_min_fn")
+_from_address = C.c_void_p.from_param
+_NULL, _TENSOR, _STRUCT, _ADDRESS, _REFUSED = range(5)
+_KIND = {type(None): _NULL}     # type of an argument -> how Ptr passes it; _kind() files each new type once
+
+
+def _kind(tp):
+    k = (_STRUCT if issubclass(tp, C.Structure) else _TENSOR if hasattr(tp, "data_ptr")
+         else _REFUSED if issubclass(tp, str) else _ADDRESS)
+    _KIND[tp] = k
+    return k
+
+
+class Ptr(C.c_void_p):
+    """argtype of every pointer parameter: None, a tensor (its data_ptr()), a Structure (by reference), or whatever
+    c_void_p takes (an address, bytes, c_void_p, byref(...), ctypes arrays and pointers).  One dictionary look-up on the
+    argument's type per argument: this runs for every pointer of every call."""
+
+    @classmethod
+    def from_param(cls, a, _get=_KIND.get, _byref=C.byref):
+        k = _get(type(a))
+        if k is None:
+            k = _kind(type(a))
+        if k == _TENSOR:
+            return _from_address(a.data_ptr())
+        if k == _ADDRESS:
+            return _from_address(a)
+        if k == _STRUCT:
+            return _byref(a)
+        if k == _NULL:
+            return None
+        raise TypeError("%r is not a pointer argument" % (a,))
+
+
+def parse_header(text):
+    """{name: (restype, argtypes)} of every function a header in the style of include/akmi.h declares"""
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = re.sub(r"^\s*#.*$", "", text, flags=re.M).replace('extern "C" {', "")
+    text = re.sub(r"\{[^{}]*\}", "", text)          # struct and enum bodies
+    sigs = {}
+    for stmt in text.split(";"):
+        stmt = " ".join(stmt.split())
+        if not re.search(r"\bakmi_[a-z0-9_]+ ?\(", stmt):
+            continue
+        m = re.fullmatch(r"([a-z *]+?) ?\b(akmi_[a-z0-9_]+) ?\(([^()]*)\)", stmt)
+        ret = m and re.sub(r" ?\* ?", " *", m.group(1)).strip()
+        if not m or ret not in _RESTYPES:
+            raise AkmiError("include/akmi.h: cannot type the declaration `%s`" % stmt)
+        argtypes = []
+        for prm in (s.strip() for s in m.group(3).split(",")):
+            if prm == "void" and "," not in m.group(3):
+                break
+            if "*" in prm or "[" in prm or prm.split()[0] in _FN_TYPEDEFS:
+                argtypes.append(Ptr)
+                continue
+            words = [w for w in prm.split() if w != "const"]
+            ctype = _CTYPES.get(" ".join(words)) or _CTYPES.get(" ".join(words[:-1]))     # unnamed or named
+            if ctype is None:
+                raise AkmiError("include/akmi.h: unknown type of parameter `%s` in the declaration of %s"
+                                % (prm, m.group(2)))
+            argtypes.append(ctype)
+        sigs[m.group(2)] = (_RESTYPES[ret], tuple(argtypes))
+    return sigs
+
+
+SIGNATURES = {}      # name -> (restype, argtypes) of every entry include/akmi.h declares; filled by the first lib()
+
+
+def signatures():
+    """SIGNATURES, parsed from include/akmi.h on first use"""
+    if not SIGNATURES:
+        if not os.path.exists(HEADER_PATH):
+            raise AkmiError("header %s not found: it declares the entries of %s" % (HEADER_PATH, LIB_PATH))
+        with open(HEADER_PATH) as f:
+            SIGNATURES.update(parse_header(f.read()))
+    return SIGNATURES
+
+
+class _StandIn:
+    """What lib() returns for an object that was put into _LIB from outside (tests/cpu_backend.py stands CPU code in for
+    the library): it does for that object what the typed entries do for libakmi.so.  The plain arguments of a call become
+    the ctypes values the C function would receive -- byref(struct), c_void_p(address), c_double(x), c_longlong(n) --
+    so a stand-in need not know how the host spells a call.  An int for a C int stays an int: ctypes passes it as one."""
+
+    def __init__(self, target):
+        self.target = target
+
+    def __getattr__(self, name):
+        fn = getattr(self.target, name)
+        if name not in signatures():
+            return fn
+        argtypes = SIGNATURES[name][1]
+
+        def convert(t, a):
+            if t is Ptr:        # a tensor as a c_void_p instance: stand-ins written in Python read its .value
+                return _p(a) if hasattr(a, "data_ptr") else Ptr.from_param(a)
+            return a if isinstance(a, C._SimpleCData) or (t is C.c_int and type(a) is int) else t(a)
+
+        def call(*args):
+            if len(args) != len(argtypes):
+                raise TypeError("%s takes %d arguments (%d given)" % (name, len(argtypes), len(args)))
+            return fn(*map(convert, argtypes, args))
+        return call
+
+
+_LOADED = None       # the library lib() loaded and typed itself
+_STANDIN = None      # the _StandIn around what _LIB holds otherwise
+
+
 def lib():
-    """Load libakmi.so (fails loudly when it has not been built)."""
-    global _LIB
+    """Load libakmi.so (fails loudly when it has not been built) and type every entry from include/akmi.h."""
+    global _LIB, _LOADED, _STANDIN
+    if _LIB is not None and _LIB is not _LOADED:
+        if _STANDIN is None or _STANDIN.target is not _LIB:
+            _STANDIN = _StandIn(_LIB)
+        return _STANDIN
     if _LIB is None:
         if not os.path.exists(LIB_PATH):
             raise AkmiError(
                 "HIP library %s not found: run `python -c 'import __graft_entry__ as g; "
                 "g.build()'` (hipcc --offload-arch=gfx950).  There is no CPU fallback." % LIB_PATH)
         L = C.CDLL(LIB_PATH)
-        L.akmi_last_error.restype = C.c_char_p
-        L.akmi_bvals_cc_segsize.restype = C.c_longlong
-        L.akmi_bvals_fc_segsize.restype = C.c_longlong
-        L.akmi_stage_workspace_bytes.restype = C.c_longlong
-        L.akmi_smr_fc_map.restype = C.c_longlong
-        L.akmi_smr_cc_map.restype = C.c_longlong
-        L.akmi_sim_create.restype = C.c_void_p
-        L.akmi_sim_array.restype = C.c_void_p
-        L.akmi_sim_lloc.restype = C.POINTER(C.c_int)
-        L.akmi_host_exchange_plan.restype = C.c_longlong
-        L.akmi_host_exchange_plan.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                              C.c_longlong]
-        L.akmi_host_device_bytes.restype = C.c_longlong
-        for f in ("akmi_rng_uniform", "akmi_rng_gaussian"):
-            getattr(L, f).restype = C.c_double
-            getattr(L, f).argtypes = [C.POINTER(RngState)]
-        L.akmi_turb_workspace_bytes.restype = C.c_longlong
-        for f in ("akmi_mg_reduce_scratch_doubles", "akmi_mg_workspace_doubles", "akmi_mg_level_offset",
-                  "akmi_mg_launch_count"):
-            getattr(L, f).restype = C.c_longlong
-        L.akmi_turb_history_workspace_bytes.restype = C.c_longlong
-        for f in ("akmi_sim_time", "akmi_sim_dt", "akmi_sim_tlim"):
-            getattr(L, f).restype = C.c_double
-        _LIB = L
+        for name, (restype, argtypes) in signatures().items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        _LIB = _LOADED = L
     return _LIB
 
 

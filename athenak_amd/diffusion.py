@@ -3,8 +3,6 @@ Ohmic resistivity.  Mirror of src/diffusion/{viscosity,conduction,resistivity}.c
 its fluxes (EMFs) inside the Fluxes (EField) task and owns a `dtnew` that Mesh::NewTimeStep folds
 into the time step (src/mesh/mesh.cpp:586-612).  The kernels are csrc/akmi_diffusion.hip.
 """
-import ctypes as C
-
 import torch
 
 from . import capi
@@ -52,8 +50,8 @@ class Viscosity(_Diffusion):
     def AddViscousFluxes(self, w0, flx, face_shaped):
         if self.nu_iso != 0.0:                                   # viscosity.cpp:52-54
             capi.check(self.L.akmi_viscous_fluxes(
-                C.byref(self.phys.pack_c), C.c_double(self.nu_iso), capi._p(w0), capi._p(flx.x1f),
-                capi._p(flx.x2f), capi._p(flx.x3f), face_shaped, capi._stream()), "viscous_fluxes")
+                self.phys.pack_c, self.nu_iso, w0, flx.x1f, flx.x2f, flx.x3f, face_shaped, capi._stream()),
+                "viscous_fluxes")
 
     def NewTimeStep(self):
         self.dtnew = self._const_dt(self.nu_iso) if self.nu_iso != 0.0 else FLT_MAX
@@ -76,16 +74,15 @@ class Conduction(_Diffusion):
     def AddHeatFluxes(self, w0, flx, face_shaped):
         if self.alpha_iso != 0.0:                                # conduction.cpp:89-91
             capi.check(self.L.akmi_heat_fluxes(
-                C.byref(self.phys.pack_c), C.c_double(self.alpha_iso), capi._p(w0), capi._p(flx.x1f),
-                capi._p(flx.x2f), capi._p(flx.x3f), face_shaped, capi._stream()), "heat_fluxes")
+                self.phys.pack_c, self.alpha_iso, w0, flx.x1f, flx.x2f, flx.x3f, face_shaped, capi._stream()),
+                "heat_fluxes")
 
     def NewTimeStep(self, w0):
         if self.alpha_iso == 0.0:
             self.dtnew = FLT_MAX*_fac(self.pmy_pack.pmesh)      # SQR(dx)/0 = inf never wins the min
             return
         capi.check(self.L.akmi_conduction_newdt(
-            C.byref(self.phys.pack_c), C.c_double(self.alpha_iso), capi._p(w0), capi._p(self.dtmin),
-            capi._stream()), "conduction_newdt")
+            self.phys.pack_c, self.alpha_iso, w0, self.dtmin, capi._stream()), "conduction_newdt")
         self.dtnew = float(self.dtmin.item())*_fac(self.pmy_pack.pmesh)
 
 
@@ -101,34 +98,30 @@ class Resistivity(_Diffusion):
     def AddResistiveEMFs(self, b0, efld):
         if self.eta_ohm != 0.0:                                  # resistivity.cpp:49-51
             capi.check(self.L.akmi_resistive_emfs(
-                C.byref(self.phys.pack_c), C.c_double(self.eta_ohm), capi._p(b0.x1f), capi._p(b0.x2f),
-                capi._p(b0.x3f), capi._p(efld.x1e), capi._p(efld.x2e), capi._p(efld.x3e),
-                capi._stream()), "resistive_emfs")
+                self.phys.pack_c, self.eta_ohm, b0.x1f, b0.x2f, b0.x3f, efld.x1e, efld.x2e, efld.x3e, capi._stream()),
+                "resistive_emfs")
         if self.eta_ad != 0.0:                                   # resistivity.cpp:52-54
             capi.check(self.L.akmi_ambipolar_emfs(
-                C.byref(self.phys.pack_c), C.c_double(self.eta_ad), capi._p(self.phys.bcc0),
-                capi._p(b0.x1f), capi._p(b0.x2f), capi._p(b0.x3f), capi._p(efld.x1e), capi._p(efld.x2e),
-                capi._p(efld.x3e), capi._stream()), "ambipolar_emfs")
+                self.phys.pack_c, self.eta_ad, self.phys.bcc0, b0.x1f, b0.x2f, b0.x3f, efld.x1e, efld.x2e, efld.x3e,
+                capi._stream()), "ambipolar_emfs")
 
     def AddResistiveFluxes(self, b0, flx):
         if self.eta_ohm != 0.0:                                  # resistivity.cpp:64-66
             capi.check(self.L.akmi_resistive_fluxes(
-                C.byref(self.phys.pack_c), C.c_double(self.eta_ohm), capi._p(b0.x1f), capi._p(b0.x2f),
-                capi._p(b0.x3f), capi._p(flx.x1f), capi._p(flx.x2f), capi._p(flx.x3f),
-                capi._stream()), "resistive_fluxes")
+                self.phys.pack_c, self.eta_ohm, b0.x1f, b0.x2f, b0.x3f, flx.x1f, flx.x2f, flx.x3f, capi._stream()),
+                "resistive_fluxes")
         if self.eta_ad != 0.0:                                   # resistivity.cpp:67-69
             capi.check(self.L.akmi_ambipolar_fluxes(
-                C.byref(self.phys.pack_c), C.c_double(self.eta_ad), capi._p(self.phys.bcc0),
-                capi._p(b0.x1f), capi._p(b0.x2f), capi._p(b0.x3f), capi._p(flx.x1f), capi._p(flx.x2f),
-                capi._p(flx.x3f), capi._stream()), "ambipolar_fluxes")
+                self.phys.pack_c, self.eta_ad, self.phys.bcc0, b0.x1f, b0.x2f, b0.x3f, flx.x1f, flx.x2f, flx.x3f,
+                capi._stream()), "ambipolar_fluxes")
 
     def NewTimeStep(self):
         if self.eta_ad == 0.0:                                   # resistivity.cpp:298-311
             self.dtnew = self._const_dt(self.eta_ohm) if self.eta_ohm > 0.0 else FLT_MAX
             return
         capi.check(self.L.akmi_resistive_newdt(                  # resistivity.cpp:313-345
-            C.byref(self.phys.pack_c), C.c_double(self.eta_ohm), C.c_double(self.eta_ad),
-            capi._p(self.phys.bcc0), capi._p(self.dtmin), capi._stream()), "resistive_newdt")
+            self.phys.pack_c, self.eta_ohm, self.eta_ad,
+            self.phys.bcc0, self.dtmin, capi._stream()), "resistive_newdt")
         self.dtnew = float(self.dtmin.item())*_fac(self.pmy_pack.pmesh)
 
 

@@ -157,7 +157,7 @@ class MGGravityDriver:
         p.four_pi_G, p.eps, p.vol = self.four_pi_G_, self.eps_, self.vol_
         p.nghbr, p.lloc = self.nghbr_dev.data_ptr(), self.lloc_dev.data_ptr()
         if self.ws is None:
-            n = int(self.L.akmi_mg_workspace_doubles(C.byref(p)))
+            n = int(self.L.akmi_mg_workspace_doubles(p))
             if n < 0:
                 raise capi.AkmiError("mg_workspace_doubles: %s" % self.L.akmi_last_error().decode())
             self.ws = torch.zeros(n, dtype=torch.float64, device=self.device)
@@ -165,7 +165,7 @@ class MGGravityDriver:
 
     def level_array(self, is_root, level, which):
         """a view of array `which` (0 u, 1 src, 2 def, 3 uold) of a level inside the workspace"""
-        off = int(self.L.akmi_mg_level_offset(C.byref(self.plan), int(is_root), level, which))
+        off = int(self.L.akmi_mg_level_offset(self.plan, int(is_root), level, which))
         if off < 0:
             raise capi.AkmiError("mg_level_offset: %s" % self.L.akmi_last_error().decode())
         s = self.nmblevel_ - 1 - level if not is_root else self.nrootlevel_ - 1 - level
@@ -182,8 +182,8 @@ class MGGravityDriver:
         fluid = pk.pmhd if pk.pmhd is not None else pk.phydro
         self._fill_plan(fluid)
         co = C.c_int(self.coffset_)
-        capi.check(self.L.akmi_mg_solve(C.byref(self.plan), capi._p(fluid.u0), capi._p(pk.pgrav.phi), C.byref(co),
-                                        self.norms, C.byref(self.ncycles), capi._stream()), "mg_solve")
+        capi.check(self.L.akmi_mg_solve(self.plan, fluid.u0, pk.pgrav.phi, C.byref(co), self.norms,
+                                        C.byref(self.ncycles), capi._stream()), "mg_solve")
         self.coffset_ = co.value
         nrm = list(self.norms)
         self.last_norms = [v for v in nrm[:41] if v >= 0.0]

@@ -193,7 +193,7 @@ class FluidBase:
 
     def _workspace(self, is_mhd):
         if self.ws is None:
-            nbytes = int(self.L.akmi_stage_workspace_bytes(C.byref(self.pack_c), is_mhd))
+            nbytes = int(self.L.akmi_stage_workspace_bytes(self.pack_c, is_mhd))
             self.ws = torch.empty((nbytes + 7)//8, dtype=torch.float64, device=self.device)
         return self.ws
 
@@ -421,12 +421,10 @@ class Hydro(FluidBase):
         if self._oop_first(pdrive, stage):
             pass                                  # RKUpdate writes the new state into u1 and swaps the registers
         elif stage == 1 and not self.fused:
-            capi.check(self.L.akmi_copy_cons(C.byref(self.pack_c), capi._p(self.u0),
-                                             capi._p(self.u1), capi._stream()), "copy_cons")
+            capi.check(self.L.akmi_copy_cons(self.pack_c, self.u0, self.u1, capi._stream()), "copy_cons")
         elif stage > 1 and pdrive.integrator == "rk4":
             capi.check(self.L.akmi_rk4_copy_cons(
-                C.byref(self.pack_c), C.c_double(pdrive.delta[stage - 1]), capi._p(self.u0),
-                capi._p(self.u1), capi._stream()), "rk4_copy_cons")
+                self.pack_c, pdrive.delta[stage - 1], self.u0, self.u1, capi._stream()), "rk4_copy_cons")
         return TaskStatus.complete
 
     def Fluxes(self, pdrive, stage):
@@ -435,21 +433,17 @@ class Hydro(FluidBase):
             return TaskStatus.complete
         # hydro_fluxes.cpp:92-101: ranges extended by one cell when FOFC is on
         fn = self.L.akmi_hydro_fluxes_fofc if self.use_fofc else self.L.akmi_hydro_fluxes
-        capi.check(fn(C.byref(self.pack_c), self.recon_method, self.rsolver_method, capi._p(self.w0),
-                      capi._p(self.uflx.x1f), capi._p(self.uflx.x2f), capi._p(self.uflx.x3f), 0,
-                      capi._stream()), "hydro_fluxes")
+        capi.check(fn(self.pack_c, self.recon_method, self.rsolver_method, self.w0, self.uflx.x1f, self.uflx.x2f,
+                      self.uflx.x3f, 0, capi._stream()), "hydro_fluxes")
         if self.pcond is not None:                       # hydro_tasks.cpp:184-189
             self.pcond.AddHeatFluxes(self.w0, self.uflx, 0)
         if self.pvisc is not None:
             self.pvisc.AddViscousFluxes(self.w0, self.uflx, 0)
         if self.use_fofc:                                # hydro_tasks.cpp:192-194 -> Hydro::FOFC
             capi.check(self.L.akmi_hydro_fofc(
-                C.byref(self.pack_c), C.c_double(pdrive.gam0[stage - 1]),
-                C.c_double(pdrive.gam1[stage - 1]),
-                C.c_double(pdrive.beta[stage - 1]*self.pmy_pack.pmesh.dt), capi._p(self.w0),
-                capi._p(self.u0), capi._p(self.u1), capi._p(self.uflx.x1f), capi._p(self.uflx.x2f),
-                capi._p(self.uflx.x3f), 0, capi._p(self.fofc), capi._p(self.nfofc),
-                capi._stream()), "hydro_fofc")
+                self.pack_c, pdrive.gam0[stage - 1], pdrive.gam1[stage - 1],
+                pdrive.beta[stage - 1]*self.pmy_pack.pmesh.dt, self.w0, self.u0, self.u1, self.uflx.x1f, self.uflx.x2f,
+                self.uflx.x3f, 0, self.fofc, self.nfofc, capi._stream()), "hydro_fofc")
         return TaskStatus.complete
 
     def RKUpdate(self, pdrive, stage):
@@ -474,15 +468,13 @@ class Hydro(FluidBase):
             self._stage_phase(pdrive, stage, capi.PHASE_ALL)
         elif self._oop_first(pdrive, stage):
             capi.check(self.L.akmi_rk_update_oop(
-                C.byref(self.pack_c), capi.d(gam0), capi.d(gam1), capi.d(beta_dt), capi._p(self.u0),
-                capi._p(self.u1), capi._p(self.uflx.x1f), capi._p(self.uflx.x2f),
-                capi._p(self.uflx.x3f), 0, capi._stream()), "rk_update_oop")
+                self.pack_c, gam0, gam1, beta_dt, self.u0, self.u1, self.uflx.x1f, self.uflx.x2f, self.uflx.x3f, 0,
+                capi._stream()), "rk_update_oop")
             self.u0, self.u1 = self.u1, self.u0
         else:
             capi.check(self.L.akmi_rk_update(
-                C.byref(self.pack_c), capi.d(gam0), capi.d(gam1), capi.d(beta_dt), capi._p(self.u0),
-                capi._p(self.u1), capi._p(self.uflx.x1f), capi._p(self.uflx.x2f),
-                capi._p(self.uflx.x3f), 0, capi._stream()), "rk_update")
+                self.pack_c, gam0, gam1, beta_dt, self.u0, self.u1, self.uflx.x1f, self.uflx.x2f, self.uflx.x3f, 0,
+                capi._stream()), "rk_update")
         return TaskStatus.complete
 
     def _w_eligible(self):
@@ -499,7 +491,7 @@ class Hydro(FluidBase):
         ok = tuple(capi.BC[k] for k in ("block", "periodic", "outflow", "reflect"))
         if any(int(f) not in ok for f in np.asarray(self.pmy_pack.pmb.mb_bcs).ravel()):
             return False
-        return bool(fn(C.byref(self.pack_c), self.recon_method, self.rsolver_method))
+        return bool(fn(self.pack_c, self.recon_method, self.rsolver_method))
 
     def _stage_w(self, pdrive, stage):
         """akmi_hydro_stage_w: the whole stage, ConsToPrim of the active cells inside the update kernel, the new
@@ -511,17 +503,14 @@ class Hydro(FluidBase):
     def _call_stage(self, gam0, gam1, beta_dt, copy, do_dt, phases, write_prims):
         if not write_prims:
             capi.check(self.L.akmi_hydro_stage_phase(
-                C.byref(self.pack_c), self.recon_method, self.rsolver_method, capi.d(gam0),
-                capi.d(gam1), capi.d(beta_dt), copy, capi._p(self.w0),
-                capi._p(self.u0), capi._p(self.u1), do_dt, capi._p(self.counters),
-                capi._p(self.dt3), phases, capi._p(self._workspace(0)), capi._stream()),
+                self.pack_c, self.recon_method, self.rsolver_method, gam0, gam1, beta_dt, copy, self.w0, self.u0,
+                self.u1, do_dt, self.counters, self.dt3, phases, self._workspace(0), capi._stream()),
                 "hydro_stage_phase")
             return 0
         wrote = C.c_int(0)
         capi.check(self.L.akmi_hydro_stage_w(
-            C.byref(self.pack_c), self.recon_method, self.rsolver_method, capi.d(gam0), capi.d(gam1), capi.d(beta_dt),
-            None, copy, capi._p(self.w0), capi._p(self.w1), capi._p(self.u0), capi._p(self.u1), do_dt,
-            capi._p(self.counters), capi._p(self.dt3), capi._p(self._workspace(0)), capi._stream(), C.byref(wrote)),
+            self.pack_c, self.recon_method, self.rsolver_method, gam0, gam1, beta_dt, None, copy, self.w0, self.w1,
+            self.u0, self.u1, do_dt, self.counters, self.dt3, self._workspace(0), capi._stream(), C.byref(wrote)),
             "hydro_stage_w")
         return wrote.value
 
@@ -535,8 +524,8 @@ class Hydro(FluidBase):
             bv, pm = self.pbval_u, self.pmy_pack.pmesh
             hb = np.ascontiguousarray(self.pmy_pack.pmb.mb_bcs, dtype=np.int32)
             capi.check(self.L.akmi_hydro_ghost_uw(
-                C.byref(self.pack_c), capi._p(bv.nghbr), capi._p(bv.bcs), hb.ctypes.data_as(C.c_void_p), capi._p(self.u0),
-                capi._p(self.w0), capi._p(self._workspace(0)), capi._p(self.counters), capi._stream()), "hydro_ghost_uw")
+                self.pack_c, bv.nghbr, bv.bcs, hb.ctypes.data_as(C.c_void_p), self.u0, self.w0, self._workspace(0),
+                self.counters, capi._stream()), "hydro_ghost_uw")
             bv._u_bcs_done = True
             self._shell_done = True
             self._dt3_reset = False
@@ -576,17 +565,15 @@ class Hydro(FluidBase):
             self._interior_done = False
             if not self._shell_done:
                 capi.check(self.L.akmi_hydro_c2p_shell(
-                    C.byref(self.pack_c), capi._p(self.u0), capi._p(self.w0), capi._p(self.counters),
-                    capi._stream()), "hydro_c2p_shell")
+                    self.pack_c, self.u0, self.w0, self.counters, capi._stream()), "hydro_c2p_shell")
             self._shell_done = False
             return TaskStatus.complete
         if self.fused:
             do_dt = 1 if stage == pdrive.nexp_stages else 0
             with self._timed():          # bench.py: the conversion belongs to the stage's launch group
                 capi.check(self.L.akmi_hydro_c2p_newdt(
-                    C.byref(self.pack_c), capi._p(self.u0), capi._p(self.w0),
-                    2 if (do_dt and self._dt3_reset) else do_dt,
-                    capi._p(self.counters), capi._p(self.dt3), capi._stream()), "hydro_c2p_newdt")
+                    self.pack_c, self.u0, self.w0, 2 if (do_dt and self._dt3_reset) else do_dt, self.counters, self.dt3,
+                    capi._stream()), "hydro_c2p_newdt")
             self._dt3_reset = False
             self._dt_ready = bool(do_dt)
             return TaskStatus.complete
@@ -595,12 +582,10 @@ class Hydro(FluidBase):
             # entry without it (see mhd.py)
             do_dt = 1 if stage == pdrive.nexp_stages else 0
             capi.check(self.L.akmi_hydro_c2p_newdt(
-                C.byref(self.pack_c), capi._p(self.u0), capi._p(self.w0), do_dt,
-                capi._p(self.counters), capi._p(self.dt3), capi._stream()), "hydro_c2p_newdt")
+                self.pack_c, self.u0, self.w0, do_dt, self.counters, self.dt3, capi._stream()), "hydro_c2p_newdt")
             self._dt_ready = bool(do_dt)
             return TaskStatus.complete
-        capi.check(self.L.akmi_hydro_c2p(C.byref(self.pack_c), capi._p(self.u0), capi._p(self.w0),
-                                         0, n1 - 1, 0, n2 - 1, 0, n3 - 1, capi._p(self.counters),
+        capi.check(self.L.akmi_hydro_c2p(self.pack_c, self.u0, self.w0, 0, n1 - 1, 0, n2 - 1, 0, n3 - 1, self.counters,
                                          capi._stream()), "hydro_c2p")
         return TaskStatus.complete
 
@@ -609,11 +594,9 @@ class Hydro(FluidBase):
         if stage != pdrive.nexp_stages:
             return TaskStatus.complete
         if self.kinematic:                                       # hydro_newdt.cpp:55-72
-            capi.check(self.L.akmi_kinematic_newdt(C.byref(self.pack_c), capi._p(self.w0),
-                                                   capi._p(self.dt3), capi._stream()), "kinematic_newdt")
+            capi.check(self.L.akmi_kinematic_newdt(self.pack_c, self.w0, self.dt3, capi._stream()), "kinematic_newdt")
         elif not self._dt_ready:
-            capi.check(self.L.akmi_hydro_newdt(C.byref(self.pack_c), capi._p(self.w0),
-                                               capi._p(self.dt3), capi._stream()), "hydro_newdt")
+            capi.check(self.L.akmi_hydro_newdt(self.pack_c, self.w0, self.dt3, capi._stream()), "hydro_newdt")
         self._dt_ready = False
         self._finish_newdt()
         self._diffusion_newdt()

@@ -142,8 +142,7 @@ class IonNeutral:
         assert ru.shape[1] == self.pmy_pack.nmb_thispack, (ru.shape, self.pmy_pack.nmb_thispack)
         adt_c = (C.c_double*max(len(adt), 1))(*adt)
         capi.check(self.L.akmi_ionn_imp_update(
-            self.pmy_pack.nmb_thispack, C.c_longlong(n3*n2*n1), pmhd.nvars, phyd.nvars, pdrive.nimp_stages, istage,
-            1 if do_solve else 0, adt_c, capi.d(g_adt), capi.d(xi_adt), capi.d(al_adt), capi.d(self.drag_coeff),
-            capi.d(self.ionization_coeff), capi.d(self.recombination_coeff), capi._p(pmhd.u0), capi._p(phyd.u0),
-            capi._p(ru), capi._stream()), "ionn_imp_update")
+            self.pmy_pack.nmb_thispack, n3*n2*n1, pmhd.nvars, phyd.nvars, pdrive.nimp_stages, istage,
+            1 if do_solve else 0, adt_c, g_adt, xi_adt, al_adt, self.drag_coeff, self.ionization_coeff,
+            self.recombination_coeff, pmhd.u0, phyd.u0, ru, capi._stream()), "ionn_imp_update")
         return TaskStatus.complete

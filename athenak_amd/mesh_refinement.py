@@ -8,8 +8,6 @@ akmi_amr_regrid_cc / _fc / akmi_amr_repair_fc.  The regrid is out of place, from
 objects rebuilt for the new mesh, so the reference's move-left / move-right ordering of in-place copies (:817-910) has
 no counterpart here.  Everything downstream of a regrid is the path of a statically refined mesh.
 """
-import ctypes as C
-
 import numpy as np
 import torch
 
@@ -152,9 +150,8 @@ class MeshRefinement:
                 flags[torch.from_numpy(self._location_mask(pk, c)).to(flags.device)] = 1
                 continue
             ph, q = self._variable(pk, c.variable)
-            capi.check(ph.L.akmi_amr_check(C.byref(ph.pack_c), capi.AMR_METHOD[c.method], capi._p(q),
-                                           C.c_longlong(q.stride(0)), capi.d(c.value_min), capi.d(c.value_max),
-                                           capi._p(flags), capi._stream()), "amr_check")
+            capi.check(ph.L.akmi_amr_check(ph.pack_c, capi.AMR_METHOD[c.method], q, q.stride(0), c.value_min,
+                                           c.value_max, flags, capi._stream()), "amr_check")
         rf = flags.cpu().numpy()                  # the one device-to-host copy of a check
         for m in range(pk.nmb_thispack):
             lev = pm.lloc_eachmb[m + pk.gids].level
@@ -252,16 +249,16 @@ class MeshRefinement:
         for old, new in ((old_h, pk.phydro), (old_m, pk.pmhd)):
             if old is None:
                 continue
-            capi.check(new.L.akmi_amr_regrid_cc(C.byref(old.pack_c), C.byref(new.pack_c), new.nvars, capi._p(plan_dev),
-                                                capi._p(old.u0), capi._p(new.u0), capi._stream()), "amr_regrid_cc")
+            capi.check(new.L.akmi_amr_regrid_cc(old.pack_c, new.pack_c, new.nvars, plan_dev, old.u0, new.u0,
+                                                capi._stream()), "amr_regrid_cc")
             new.counters.copy_(old.counters)
             if getattr(old, "use_fofc", False):
                 new.nfofc.copy_(old.nfofc)
         if old_m is not None:
             ob, nb = old_m.b0, pk.pmhd.b0
             capi.check(pk.pmhd.L.akmi_amr_regrid_fc(
-                C.byref(old_m.pack_c), C.byref(pk.pmhd.pack_c), capi._p(plan_dev), capi._p(ob.x1f), capi._p(ob.x2f),
-                capi._p(ob.x3f), capi._p(nb.x1f), capi._p(nb.x2f), capi._p(nb.x3f), capi._stream()), "amr_regrid_fc")
+                old_m.pack_c, pk.pmhd.pack_c, plan_dev, ob.x1f, ob.x2f, ob.x3f, nb.x1f, nb.x2f, nb.x3f, capi._stream()),
+                "amr_regrid_fc")
         if dev != "cpu" and torch.cuda.is_available():
             torch.cuda.current_stream().synchronize()          # the old arrays and the plan are released on return
 
@@ -270,8 +267,7 @@ class MeshRefinement:
         boundary exchange has finalized"""
         rep = torch.from_numpy(self.fc_amr_repair).to(pmhd.device)
         b = pmhd.b0
-        capi.check(pmhd.L.akmi_amr_repair_fc(C.byref(pmhd.pack_c), capi._p(rep), capi._p(b.x1f), capi._p(b.x2f),
-                                             capi._p(b.x3f), capi._stream()), "amr_repair_fc")
+        capi.check(pmhd.L.akmi_amr_repair_fc(pmhd.pack_c, rep, b.x1f, b.x2f, b.x3f, capi._stream()), "amr_repair_fc")
         if pmhd.device != "cpu" and torch.cuda.is_available():
             torch.cuda.current_stream().synchronize()
 

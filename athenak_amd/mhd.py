@@ -4,8 +4,6 @@ Mirror of src/mhd/mhd.hpp:93-199 / mhd.cpp:30-382 / mhd_tasks.cpp:38-699: member
 u1, b0, b1, bcc0, uflx, efld, e3x1..e1x3, peos, pbval_u, pbval_b, dtnew; the `stagen` chain
 of AssembleMHDTasks (mhd_tasks.cpp:48-75) with each body one call through include/akmi.h.
 """
-import ctypes as C
-
 import torch
 
 from . import capi
@@ -158,15 +156,14 @@ class MHD(FluidBase):
         return TaskStatus.complete
 
     def _b(self, f):
-        return capi._p(f.x1f), capi._p(f.x2f), capi._p(f.x3f)
+        return f.x1f, f.x2f, f.x3f
 
     def CopyCons(self, pdrive, stage):
         """mhd_tasks.cpp:162-170"""
         if self._oop_first(pdrive, stage):
             return TaskStatus.complete            # RKUpdate / CT write u1 / b1 and swap the registers
         if stage == 1 and not self.fused:
-            capi.check(self.L.akmi_copy_cons(C.byref(self.pack_c), capi._p(self.u0),
-                                             capi._p(self.u1), capi._stream()), "copy_cons")
+            capi.check(self.L.akmi_copy_cons(self.pack_c, self.u0, self.u1, capi._stream()), "copy_cons")
             self.b1.x1f.copy_(self.b0.x1f)
             self.b1.x2f.copy_(self.b0.x2f)
             self.b1.x3f.copy_(self.b0.x3f)
@@ -175,11 +172,10 @@ class MHD(FluidBase):
     def Fluxes(self, pdrive, stage):
         """mhd_tasks.cpp:177-216"""
         if not self.fused:
-            efc = [capi._p(x) for x in (self.e3x1, self.e2x1, self.e1x2, self.e3x2, self.e2x3, self.e1x3)]
+            efc = (self.e3x1, self.e2x1, self.e1x2, self.e3x2, self.e2x3, self.e1x3)
             fn = self.L.akmi_mhd_fluxes_fofc if self.use_fofc else self.L.akmi_mhd_fluxes
-            capi.check(fn(C.byref(self.pack_c), self.recon_method, self.rsolver_method,
-                          capi._p(self.w0), capi._p(self.bcc0), *self._b(self.b0), *self._b(self.uflx),
-                          *efc, capi._stream()), "mhd_fluxes")
+            capi.check(fn(self.pack_c, self.recon_method, self.rsolver_method, self.w0, self.bcc0, *self._b(self.b0),
+                          *self._b(self.uflx), *efc, capi._stream()), "mhd_fluxes")
             if self.pcond is not None:                   # mhd_tasks.cpp:198-206
                 self.pcond.AddHeatFluxes(self.w0, self.uflx, 1)
             if self.pvisc is not None:
@@ -188,12 +184,10 @@ class MHD(FluidBase):
                 self.presist.AddResistiveFluxes(self.b0, self.uflx)
             if self.use_fofc:                    # mhd_tasks.cpp:209-211 -> MHD::FOFC
                 capi.check(self.L.akmi_mhd_fofc(
-                    C.byref(self.pack_c), C.c_double(pdrive.gam0[stage - 1]),
-                    C.c_double(pdrive.gam1[stage - 1]),
-                    C.c_double(pdrive.beta[stage - 1]*self.pmy_pack.pmesh.dt), capi._p(self.w0),
-                    capi._p(self.bcc0), *self._b(self.b0), *self._b(self.b1), capi._p(self.u0),
-                    capi._p(self.u1), *self._b(self.uflx), *efc, capi._p(self.fofc),
-                    capi._p(self.nfofc), capi._stream()), "mhd_fofc")
+                    self.pack_c, pdrive.gam0[stage - 1], pdrive.gam1[stage - 1],
+                    pdrive.beta[stage - 1]*self.pmy_pack.pmesh.dt, self.w0, self.bcc0, *self._b(self.b0),
+                    *self._b(self.b1), self.u0, self.u1, *self._b(self.uflx), *efc, self.fofc, self.nfofc,
+                    capi._stream()), "mhd_fofc")
         return TaskStatus.complete
 
     def RKUpdate(self, pdrive, stage):
@@ -219,22 +213,20 @@ class MHD(FluidBase):
             self._stage_phase(pdrive, stage, capi.PHASE_ALL)
         elif self._oop_first(pdrive, stage):
             capi.check(self.L.akmi_rk_update_oop(
-                C.byref(self.pack_c), capi.d(gam0), capi.d(gam1), capi.d(beta_dt), capi._p(self.u0),
-                capi._p(self.u1), *self._b(self.uflx), 1, capi._stream()), "rk_update_oop")
+                self.pack_c, gam0, gam1, beta_dt, self.u0, self.u1, *self._b(self.uflx), 1, capi._stream()),
+                "rk_update_oop")
             self.u0, self.u1 = self.u1, self.u0
         else:
             capi.check(self.L.akmi_rk_update(
-                C.byref(self.pack_c), capi.d(gam0), capi.d(gam1), capi.d(beta_dt), capi._p(self.u0),
-                capi._p(self.u1), *self._b(self.uflx), 1, capi._stream()), "rk_update")
+                self.pack_c, gam0, gam1, beta_dt, self.u0, self.u1, *self._b(self.uflx), 1, capi._stream()),
+                "rk_update")
         return TaskStatus.complete
 
     def _call_stage(self, gam0, gam1, beta_dt, copy, do_dt, phases, write_prims):
         capi.check(self.L.akmi_mhd_stage_phase(
-            C.byref(self.pack_c), self.recon_method, self.rsolver_method, capi.d(gam0),
-            capi.d(gam1), capi.d(beta_dt), copy, capi._p(self.w0),
-            capi._p(self.bcc0), capi._p(self.u0), capi._p(self.u1), *self._b(self.b0),
-            *self._b(self.b1), do_dt, capi._p(self.counters), capi._p(self.dt3), phases,
-            capi._p(self._workspace(1)), capi._stream()), "mhd_stage_phase")
+            self.pack_c, self.recon_method, self.rsolver_method, gam0, gam1, beta_dt, copy, self.w0, self.bcc0, self.u0,
+            self.u1, *self._b(self.b0), *self._b(self.b1), do_dt, self.counters, self.dt3, phases, self._workspace(1),
+            capi._stream()), "mhd_stage_phase")
         return 0
 
     def _swap_b(self):
@@ -256,10 +248,8 @@ class MHD(FluidBase):
         """MHD::CornerE, mhd_corner_e.cpp:26-417"""
         if not self.fused:
             capi.check(self.L.akmi_mhd_corner_e(
-                C.byref(self.pack_c), capi._p(self.w0), capi._p(self.bcc0), capi._p(self.e3x1),
-                capi._p(self.e2x1), capi._p(self.e1x2), capi._p(self.e3x2), capi._p(self.e2x3),
-                capi._p(self.e1x3), *self._b(self.uflx), capi._p(self.efld.x1e),
-                capi._p(self.efld.x2e), capi._p(self.efld.x3e), capi._stream()), "mhd_corner_e")
+                self.pack_c, self.w0, self.bcc0, self.e3x1, self.e2x1, self.e1x2, self.e3x2, self.e2x3, self.e1x3,
+                *self._b(self.uflx), self.efld.x1e, self.efld.x2e, self.efld.x3e, capi._stream()), "mhd_corner_e")
             if self.presist is not None:                 # mhd_tasks.cpp:381-383
                 self.presist.AddResistiveEMFs(self.b0, self.efld)
         return TaskStatus.complete
@@ -273,15 +263,13 @@ class MHD(FluidBase):
             beta_dt = pdrive.beta[stage - 1]*self.pmy_pack.pmesh.dt
             if self._oop_first(pdrive, stage):
                 capi.check(self.L.akmi_mhd_ct_oop(
-                    C.byref(self.pack_c), capi.d(gam0), capi.d(gam1), capi.d(beta_dt),
-                    capi._p(self.efld.x1e), capi._p(self.efld.x2e), capi._p(self.efld.x3e),
-                    *self._b(self.b0), *self._b(self.b1), capi._stream()), "mhd_ct_oop")
+                    self.pack_c, gam0, gam1, beta_dt, self.efld.x1e, self.efld.x2e, self.efld.x3e, *self._b(self.b0),
+                    *self._b(self.b1), capi._stream()), "mhd_ct_oop")
                 self._swap_b()
                 return TaskStatus.complete
             capi.check(self.L.akmi_mhd_ct(
-                C.byref(self.pack_c), capi.d(gam0), capi.d(gam1), capi.d(beta_dt),
-                capi._p(self.efld.x1e), capi._p(self.efld.x2e), capi._p(self.efld.x3e),
-                *self._b(self.b0), *self._b(self.b1), capi._stream()), "mhd_ct")
+                self.pack_c, gam0, gam1, beta_dt, self.efld.x1e, self.efld.x2e, self.efld.x3e, *self._b(self.b0),
+                *self._b(self.b1), capi._stream()), "mhd_ct")
         return TaskStatus.complete
 
     def SendB(self, pdrive, stage):
@@ -316,15 +304,14 @@ class MHD(FluidBase):
         if self.fused and self._interior_done:
             self._interior_done = False
             capi.check(self.L.akmi_mhd_c2p_shell(
-                C.byref(self.pack_c), capi._p(self.u0), *self._b(self.b0), capi._p(self.w0),
-                capi._p(self.bcc0), capi._p(self.counters), capi._stream()), "mhd_c2p_shell")
+                self.pack_c, self.u0, *self._b(self.b0), self.w0, self.bcc0, self.counters, capi._stream()),
+                "mhd_c2p_shell")
             return TaskStatus.complete
         if self.fused:
             do_dt = 1 if stage == pdrive.nexp_stages else 0
             with self._timed():          # bench.py: the conversion belongs to the stage's launch group
                 capi.check(self.L.akmi_mhd_c2p_newdt(
-                    C.byref(self.pack_c), capi._p(self.u0), *self._b(self.b0), capi._p(self.w0),
-                    capi._p(self.bcc0), do_dt, capi._p(self.counters), capi._p(self.dt3),
+                    self.pack_c, self.u0, *self._b(self.b0), self.w0, self.bcc0, do_dt, self.counters, self.dt3,
                     capi._stream()), "mhd_c2p_newdt")
             self._dt_ready = bool(do_dt)
             return TaskStatus.complete
@@ -335,14 +322,12 @@ class MHD(FluidBase):
             # (960 blocks of 32^3: 1 380 against 1 480 us for akmi_mhd_c2p)
             do_dt = 1 if stage == pdrive.nexp_stages else 0
             capi.check(self.L.akmi_mhd_c2p_newdt(
-                C.byref(self.pack_c), capi._p(self.u0), *self._b(self.b0), capi._p(self.w0),
-                capi._p(self.bcc0), do_dt, capi._p(self.counters), capi._p(self.dt3),
+                self.pack_c, self.u0, *self._b(self.b0), self.w0, self.bcc0, do_dt, self.counters, self.dt3,
                 capi._stream()), "mhd_c2p_newdt")
             self._dt_ready = bool(do_dt)
             return TaskStatus.complete
         capi.check(self.L.akmi_mhd_c2p(
-            C.byref(self.pack_c), capi._p(self.u0), *self._b(self.b0), capi._p(self.w0),
-            capi._p(self.bcc0), 0, n1 - 1, 0, n2 - 1, 0, n3 - 1, capi._p(self.counters),
+            self.pack_c, self.u0, *self._b(self.b0), self.w0, self.bcc0, 0, n1 - 1, 0, n2 - 1, 0, n3 - 1, self.counters,
             capi._stream()), "mhd_c2p")
         return TaskStatus.complete
 
@@ -351,12 +336,9 @@ class MHD(FluidBase):
         if stage != pdrive.nexp_stages:
             return TaskStatus.complete
         if self.kinematic:                                       # mhd_newdt.cpp:56-73
-            capi.check(self.L.akmi_kinematic_newdt(C.byref(self.pack_c), capi._p(self.w0),
-                                                   capi._p(self.dt3), capi._stream()), "kinematic_newdt")
+            capi.check(self.L.akmi_kinematic_newdt(self.pack_c, self.w0, self.dt3, capi._stream()), "kinematic_newdt")
         elif not self._dt_ready:
-            capi.check(self.L.akmi_mhd_newdt(C.byref(self.pack_c), capi._p(self.w0),
-                                             capi._p(self.bcc0), capi._p(self.dt3), capi._stream()),
-                       "mhd_newdt")
+            capi.check(self.L.akmi_mhd_newdt(self.pack_c, self.w0, self.bcc0, self.dt3, capi._stream()), "mhd_newdt")
         self._dt_ready = False
         self._finish_newdt()
         self._diffusion_newdt()

@@ -113,8 +113,7 @@ class NativeSimulation:
 
     def Initialize(self):
         torch.cuda.synchronize()
-        capi.check(self.L.akmi_sim_initialize(self.h, C.c_double(self.pin.GetReal("time", "tlim"))),
-                   "sim_initialize")
+        capi.check(self.L.akmi_sim_initialize(self.h, self.pin.GetReal("time", "tlim")), "sim_initialize")
 
     def Execute(self, max_cycles=None):
         n = capi.check(self.L.akmi_sim_execute(self.h, -1 if max_cycles is None else int(max_cycles)), "sim_execute")
@@ -137,7 +136,7 @@ class NativeSimulation:
         _, nmb, _, n3, n2, n1 = self._shape
         out = torch.empty((nmb, ncomp, n3, n2, n1), dtype=torch.float64, device="cuda")
         torch.cuda.synchronize()
-        capi.check(self.L.akmi_sim_derived(self.h, which, capi._p(out)), "sim_derived")
+        capi.check(self.L.akmi_sim_derived(self.h, which, out), "sim_derived")
         return out
 
     def coarsen(self, variable, factor, moments=False, ghost_zones=False, staged=None):
@@ -169,9 +168,8 @@ class NativeSimulation:
         weights = torch.zeros(shape, dtype=torch.float64, device="cuda")
         nan = torch.zeros(1, dtype=torch.int64, device="cuda")
         torch.cuda.synchronize()
-        capi.check(self.L.akmi_sim_pdf(self.h, C.byref(cax[0]), C.byref(cax[1]) if len(cax) == 2 else None,
-                                       1 if mass_weighted else 0, capi._p(counts), capi._p(weights), capi._p(nan),
-                                       1 if force_global else 0), "sim_pdf")
+        capi.check(self.L.akmi_sim_pdf(self.h, cax[0], cax[1] if len(cax) == 2 else None, 1 if mass_weighted else 0,
+                                       counts, weights, nan, 1 if force_global else 0), "sim_pdf")
         return PdfResult(axes, *pdf_reduce_ranks(self.pmesh, counts, weights, nan))
 
     def turb_history(self):

@@ -132,10 +132,9 @@ def derived_array(phys, which):
     if not hasattr(L, "akmi_derived_var"):
         _fatal("derived output variables need akmi_derived_var of libakmi.so (a GPU): this backend has none")
     b0 = getattr(phys, "b0", None)
-    b = (capi._p(b0.x1f), capi._p(b0.x2f), capi._p(b0.x3f)) if b0 is not None else (None, None, None)
-    capi.check(L.akmi_derived_var(C.byref(phys.pack_c), which, capi._p(phys.w0), capi._p(phys.u0),
-                                  capi._p(getattr(phys, "bcc0", None)), *b, capi._p(out), 1, capi._stream()),
-               "derived_var")
+    b = (b0.x1f, b0.x2f, b0.x3f) if b0 is not None else (None, None, None)
+    capi.check(L.akmi_derived_var(phys.pack_c, which, phys.w0, phys.u0, getattr(phys, "bcc0", None), *b, out, 1,
+                                  capi._stream()), "derived_var")
     return out
 
 
@@ -401,17 +400,16 @@ class HistoryOutput(BaseTypeOutput):
         out = torch.zeros(len(self.labels), dtype=torch.float64, device=phys.u0.device)
         L = capi.lib()
         if self.is_mhd:
-            b = (capi._p(phys.b0.x1f), capi._p(phys.b0.x2f), capi._p(phys.b0.x3f))
+            b = (phys.b0.x1f, phys.b0.x2f, phys.b0.x3f)
         else:
             b = (None, None, None)
-        capi.check(L.akmi_history_sums(C.byref(phys.pack_c), 1 if self.is_mhd else 0, capi._p(phys.u0),
-                                       *b, capi._p(out), capi._stream()), "history_sums")
+        capi.check(L.akmi_history_sums(phys.pack_c, 1 if self.is_mhd else 0, phys.u0, *b, out, capi._stream()),
+                   "history_sums")
         self.hdata = out
         if self.neutral is not None:
             ph = pk.phydro
             nout = torch.zeros(len(self.neutral["labels"]), dtype=torch.float64, device=ph.u0.device)
-            capi.check(L.akmi_history_sums(C.byref(ph.pack_c), 0, capi._p(ph.u0), None, None, None, capi._p(nout),
-                                           capi._stream()), "history_sums")
+            capi.check(L.akmi_history_sums(ph.pack_c, 0, ph.u0, None, None, None, nout, capi._stream()), "history_sums")
             self.neutral["hdata"] = nout
 
     def WriteOutputFile(self, pm, pin):
@@ -486,11 +484,10 @@ def turb_history_sums(phys, pack):
         _fatal("the turbulence history columns need an MHD run")
     nmb = phys.w0.shape[0]
     partial = torch.zeros((nmb, capi.TURB_NHIST), dtype=torch.float64, device=phys.w0.device)
-    nbytes = int(L.akmi_turb_history_workspace_bytes(C.byref(phys.pack_c)))
+    nbytes = int(L.akmi_turb_history_workspace_bytes(phys.pack_c))
     work = torch.empty(nbytes//8 + 1, dtype=torch.float64, device=phys.w0.device)
-    capi.check(L.akmi_turb_history(C.byref(phys.pack_c), capi._p(phys.w0), capi._p(phys.bcc0), capi._p(phys.b0.x1f),
-                                   capi._p(phys.b0.x2f), capi._p(phys.b0.x3f), capi._p(partial), capi._p(work),
-                                   capi._stream()), "turb_history")
+    capi.check(L.akmi_turb_history(phys.pack_c, phys.w0, phys.bcc0, phys.b0.x1f, phys.b0.x2f, phys.b0.x3f, partial,
+                                   work, capi._stream()), "turb_history")
     return gid_ordered_sums(partial.cpu().numpy(), pack)
 
 
@@ -575,9 +572,8 @@ def pdf_histogram(pack, axes, mass_weighted, force_global=False):
     counts = torch.zeros(shape, dtype=torch.int64, device=dev)        # the entry counts in uint64; the bits are the same
     weights = torch.zeros(shape, dtype=torch.float64, device=dev)
     nan = torch.zeros(1, dtype=torch.int64, device=dev)
-    capi.check(L.akmi_pdf(C.byref(phys.pack_c), C.byref(cax[0]), C.byref(cax[1]) if len(cax) == 2 else None,
-                          capi._p(phys.u0) if mass_weighted else None, capi._p(counts), capi._p(weights), capi._p(nan),
-                          1 if force_global else 0, capi._stream()), "pdf")
+    capi.check(L.akmi_pdf(phys.pack_c, cax[0], cax[1] if len(cax) == 2 else None, phys.u0 if mass_weighted else None,
+                          counts, weights, nan, 1 if force_global else 0, capi._stream()), "pdf")
     return pdf_reduce_ranks(pack.pmesh, counts, weights, nan)
 
 
@@ -768,11 +764,11 @@ def coarsen_pack(pack, outvars, factor, moments, lo, nc, staged=None):
     st = -1 if staged is None else int(bool(staged))
     if native is not None:
         torch.cuda.synchronize()
-        capi.check(L.akmi_sim_coarsen(native.h, tab, len(outvars), factor, 1 if moments else 0, clo, cnc, capi._p(out), st),
+        capi.check(L.akmi_sim_coarsen(native.h, tab, len(outvars), factor, 1 if moments else 0, clo, cnc, out, st),
                    "sim_coarsen")
     else:
-        capi.check(L.akmi_coarsen(C.byref(phys.pack_c), tab, len(outvars), factor, 1 if moments else 0, clo, cnc,
-                                  capi._p(out), st, capi._stream()), "coarsen")
+        capi.check(L.akmi_coarsen(phys.pack_c, tab, len(outvars), factor, 1 if moments else 0, clo, cnc, out, st,
+                                  capi._stream()), "coarsen")
     return out
 
 

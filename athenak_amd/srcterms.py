@@ -7,8 +7,6 @@ the task `srctrms` between the RK update and the send of the conserved variables
 akmi_srcterms_newdt.  self_gravity (akmi_mg_selfgravity, csrc/akmi_mg.hip) comes after them and needs the <gravity>
 block (gravity.py); rel_cooling and rad_beam stop with a message, and so does self_gravity without <gravity>.
 """
-import ctypes as C
-
 import torch
 
 from . import capi
@@ -92,8 +90,8 @@ class SourceTerms:
         """srcterms.cpp:93-101: bdt = beta*dt, formed in the kernel; SelfGravity last"""
         f = self.pmy_fluid
         if self.const_accel or self.ism_cooling:
-            capi.check(f.L.akmi_srcterms_apply(C.byref(f.pack_c), C.byref(self.c), capi.d(bdt_beta), capi.d(dt), None,
-                                               capi._p(w0), capi._p(u0), capi._stream()), "srcterms_apply")
+            capi.check(f.L.akmi_srcterms_apply(f.pack_c, self.c, bdt_beta, dt, None, w0, u0, capi._stream()),
+                       "srcterms_apply")
         if self.self_gravity:
             self.SelfGravity(w0, bdt_beta*dt, u0)
 
@@ -107,8 +105,7 @@ class SourceTerms:
         if fl is None:
             raise RuntimeError("### FATAL ERROR self_gravity needs the flux arrays of the task-granular path")
         face = 1 if fl.x1f.shape[-1] == u0.shape[-1] + 1 else 0
-        capi.check(f.L.akmi_mg_selfgravity(C.byref(f.pack_c), face, capi.d(bdt), capi._p(w0), capi._p(pgrav.phi),
-                                           capi._p(fl.x1f), capi._p(fl.x2f), capi._p(fl.x3f), capi._p(u0),
+        capi.check(f.L.akmi_mg_selfgravity(f.pack_c, face, bdt, w0, pgrav.phi, fl.x1f, fl.x2f, fl.x3f, u0,
                                            capi._stream()), "mg_selfgravity")
 
     def NewTimeStep(self, w0):
@@ -119,6 +116,5 @@ class SourceTerms:
             return
         if self.dt_dev is None:
             self.dt_dev = torch.zeros(1, dtype=torch.float64, device=f.device)
-        capi.check(f.L.akmi_srcterms_newdt(C.byref(f.pack_c), C.byref(self.c), capi._p(w0), capi._p(self.dt_dev),
-                                           capi._stream()), "srcterms_newdt")
+        capi.check(f.L.akmi_srcterms_newdt(f.pack_c, self.c, w0, self.dt_dev, capi._stream()), "srcterms_newdt")
         self.dtnew = float(self.dt_dev.cpu()[0])

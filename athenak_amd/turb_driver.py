@@ -135,9 +135,8 @@ class TurbulenceDriver:
     # ---- pieces -------------------------------------------------------------------------
     def _amplitudes(self, amp, kvec=None):
         n = self.L.akmi_turb_amplitudes(
-            self.nlow, self.nhigh, self.driving_type, capi.d(self.expo), capi.d(self.exp_prp), capi.d(self.exp_prl),
-            capi.d(self.lens[0]), capi.d(self.lens[1]), capi.d(self.lens[2]), C.byref(self.rstate),
-            None if kvec is None else kvec.ctypes.data_as(C.c_void_p),
+            self.nlow, self.nhigh, self.driving_type, self.expo, self.exp_prp, self.exp_prl, self.lens[0], self.lens[1],
+            self.lens[2], C.byref(self.rstate), None if kvec is None else kvec.ctypes.data_as(C.c_void_p),
             None if amp is None else amp.ctypes.data_as(C.c_void_p))
         return capi.check(n, "turb_amplitudes")
 
@@ -147,7 +146,7 @@ class TurbulenceDriver:
 
     def _work(self, pack_c):
         if self.work is None:
-            nbytes = int(self.L.akmi_turb_workspace_bytes(C.byref(pack_c)))
+            nbytes = int(self.L.akmi_turb_workspace_bytes(pack_c))
             self.work = torch.empty((nbytes + 7)//8, dtype=torch.float64, device=self.device)
         return self.work
 
@@ -172,13 +171,11 @@ class TurbulenceDriver:
         amp_dev = torch.from_numpy(amp).to(self.device)
         xs, xc, ys, yc, zs, zc = self.tables
         capi.check(self.L.akmi_turb_synthesize(
-            C.byref(f.pack_c), self.nmode, capi._p(amp_dev), capi._p(xs), capi._p(xc), capi._p(ys), capi._p(yc),
-            capi._p(zs), capi._p(zc), capi._p(f.u0), capi._p(self.force_tmp), capi._p(self.partial),
-            capi._p(self._work(f.pack_c)), capi._stream()), "turb_synthesize")
+            f.pack_c, self.nmode, amp_dev, xs, xc, ys, yc, zs, zc, f.u0, self.force_tmp, self.partial,
+            self._work(f.pack_c), capi._stream()), "turb_synthesize")
         t0, t1, t2, t3 = self._sums(4)
         capi.check(self.L.akmi_turb_moments(
-            C.byref(f.pack_c), capi.d(t0), capi.d(t1), capi.d(t2), capi.d(t3), capi._p(f.u0),
-            capi._p(self.force_tmp), capi._p(self.partial), capi._p(self._work(f.pack_c)), capi._stream()),
+            f.pack_c, t0, t1, t2, t3, f.u0, self.force_tmp, self.partial, self._work(f.pack_c), capi._stream()),
             "turb_moments")
         m0, m1 = self._sums(2)
         self.s = scale_factor(m0, m1, self.dedt, self.pmy_pack.pmesh.dt, self.gnx)
@@ -190,13 +187,11 @@ class TurbulenceDriver:
         dt = self.pmy_pack.pmesh.dt
         fcorr, gcorr = ou_factors(dt, self.tcorr)
         capi.check(self.L.akmi_turb_add_forcing(
-            C.byref(f.pack_c), capi.d(fcorr), capi.d(gcorr), capi.d(self.s), capi.d(dt), capi._p(self.force_tmp),
-            capi._p(self.force), capi._p(f.u0), capi._p(self.partial), capi._p(self._work(f.pack_c)),
+            f.pack_c, fcorr, gcorr, self.s, dt, self.force_tmp, self.force, f.u0, self.partial, self._work(f.pack_c),
             capi._stream()), "turb_add_forcing")
         t0, t1, t2, t3 = self._sums(4)
         capi.check(self.L.akmi_turb_remove_net_mom(
-            C.byref(f.pack_c), capi.d(t0), capi.d(t1), capi.d(t2), capi.d(t3), capi._p(f.u0), capi._stream()),
-            "turb_remove_net_mom")
+            f.pack_c, t0, t1, t2, t3, f.u0, capi._stream()), "turb_remove_net_mom")
         return TaskStatus.complete
 
 

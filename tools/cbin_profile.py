@@ -40,7 +40,7 @@ def coarsen_call(pack, outvars, f, moments, staged, n):
     lo, cnc = (C.c_int*3)(ind.is_, ind.js, ind.ks), (C.c_int*3)(nc, nc, nc)
 
     def call():
-        capi.check(L.akmi_coarsen(C.byref(ph.pack_c), tab, len(outvars), f, int(moments), lo, cnc, capi._p(out), int(staged),
+        capi.check(L.akmi_coarsen(ph.pack_c, tab, len(outvars), f, int(moments), lo, cnc, out, int(staged),
                                   capi._stream()), "coarsen")
     call.keep = (tab, out, lo, cnc)
     return call

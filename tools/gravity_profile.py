@@ -94,10 +94,10 @@ def run_smooth(n, nb, rounds):
             a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             a.record()
             if what == "smooth":
-                capi.check(L.akmi_mg_smooth(nmb, nb, nb, nb, capi.d(1.0/n), capi.d(1.15), r & 1, 0, capi._p(u),
-                                            capi._p(src), capi._stream()), "mg_smooth")
+                capi.check(L.akmi_mg_smooth(nmb, nb, nb, nb, 1.0/n, 1.15, r & 1, 0, u, src, capi._stream()),
+                           "mg_smooth")
             else:
-                capi.check(L.akmi_calib_copy(capi._p(src), capi._p(u), C_ll(cells), capi._stream()), "calib_copy")
+                capi.check(L.akmi_calib_copy(src, u, cells, capi._stream()), "calib_copy")
             b.record()
             if r >= WARM:
                 ev[what].append((a, b))
@@ -106,11 +106,6 @@ def run_smooth(n, nb, rounds):
         med, lo, hi = _median([1e3*a.elapsed_time(b) for a, b in ev[what]])
         print("%-6s %4d^3, blocks %2d^3: median %8.1f us  min %8.1f  max %8.1f   counted %7.1f MB  %6.0f GB/s" % (
             what, n, nb, med, lo, hi, by/1e6, by/med/1e3), flush=True)
-
-
-def C_ll(v):
-    import ctypes
-    return ctypes.c_longlong(v)
 
 
 if __name__ == "__main__":

@@ -55,10 +55,9 @@ def run_kernel(n, rounds):
             adt_c = (C.c_double*max(len(adt), 1))(*adt)
             a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             a.record()
-            capi.check(L.akmi_ionn_imp_update(1, C.c_longlong(cells), 4, 4, 4, istage, 1 if SOLVES[istage] else 0, adt_c,
-                                              capi.d(drag*d.a_impl*dt), capi.d(0.0), capi.d(0.0), capi.d(drag),
-                                              capi.d(0.0), capi.d(0.0), capi._p(ui), capi._p(un), capi._p(ru),
-                                              capi._stream()), "ionn_imp_update")
+            capi.check(L.akmi_ionn_imp_update(1, cells, 4, 4, 4, istage, 1 if SOLVES[istage] else 0, adt_c,
+                                              drag*d.a_impl*dt, 0.0, 0.0, drag, 0.0, 0.0, ui, un, ru, capi._stream()),
+                       "ionn_imp_update")
             b.record()
             if r >= WARM:
                 ev[istage].append((a, b))

@@ -1,6 +1,5 @@
 """workload for tools/pmc.sh: calibration copies of known size + 2 RK2 cycles of the bench
 configuration (3-D Orszag-Tang 256^3 MHD, fused stage path)."""
-import ctypes as C
 import os
 import sys
 
@@ -17,7 +16,7 @@ n = 64*1024*1024            # 512 MiB read + 512 MiB written: far beyond the 256
 a = torch.randn(n, dtype=torch.float64, device="cuda")
 b = torch.empty_like(a)
 for _ in range(3):
-    capi.check(L.akmi_calib_copy(capi._p(b), capi._p(a), C.c_longlong(n), capi._stream()), "calib")
+    capi.check(L.akmi_calib_copy(b, a, n, capi._stream()), "calib")
 torch.cuda.synchronize()
 nx = int(os.environ.get("AKMI_PMC_NX", "256"))
 ov = ["time/cfl_number=0.3", "time/nlim=-1", "time/tlim=1.0e9"]

@@ -8,7 +8,6 @@ constant field (every cell in one bin) through both paths -- each next to a copy
 The lines are printed and written to the output file (default profiles/stats_outputs.txt).  Run it under
 `rocprofv3 --kernel-trace --stats -- python tools/stats_profile.py` for the kernel rows the events bracket (the event
 times of akmi_pdf include its three memsets, those of akmi_turb_history its second kernel)."""
-import ctypes as C
 import os
 import sys
 
@@ -46,11 +45,11 @@ def pdf_call(ph, axes, mass, force_global):
     counts = torch.zeros(shape, dtype=torch.int64, device="cuda")
     weights = torch.zeros(shape, dtype=torch.float64, device="cuda")
     nan = torch.zeros(1, dtype=torch.int64, device="cuda")
-    y = C.byref(cax[1]) if len(cax) == 2 else None
+    y = cax[1] if len(cax) == 2 else None
 
     def call():
-        capi.check(L.akmi_pdf(C.byref(ph.pack_c), C.byref(cax[0]), y, capi._p(ph.u0) if mass else None, capi._p(counts),
-                              capi._p(weights), capi._p(nan), int(force_global), capi._stream()), "pdf")
+        capi.check(L.akmi_pdf(ph.pack_c, cax[0], y, ph.u0 if mass else None, counts, weights, nan, int(force_global),
+                              capi._stream()), "pdf")
     call.keep = (cax, counts, weights, nan)
     return call
 
@@ -67,11 +66,10 @@ if __name__ == "__main__":
     L = capi.lib()
     say("# tools/stats_profile.py %d %d: entries timed by HIP events, each against a device-to-device copy" % (n, repeats))
     partial = torch.zeros((1, capi.TURB_NHIST), dtype=torch.float64, device="cuda")
-    work = torch.empty(int(L.akmi_turb_history_workspace_bytes(C.byref(ph.pack_c)))//8 + 1, dtype=torch.float64, device="cuda")
+    work = torch.empty(int(L.akmi_turb_history_workspace_bytes(ph.pack_c))//8 + 1, dtype=torch.float64, device="cuda")
 
     def hist():
-        capi.check(L.akmi_turb_history(C.byref(ph.pack_c), capi._p(ph.w0), capi._p(ph.bcc0), capi._p(ph.b0.x1f),
-                                       capi._p(ph.b0.x2f), capi._p(ph.b0.x3f), capi._p(partial), capi._p(work),
+        capi.check(L.akmi_turb_history(ph.pack_c, ph.w0, ph.bcc0, ph.b0.x1f, ph.b0.x2f, ph.b0.x3f, partial, work,
                                        capi._stream()), "turb_history")
     # history: bcc0 (3), velocities (3), three face arrays
     row(n, "akmi_turb_history", timed(hist, repeats), 9*cells, repeats)
