@@ -83,7 +83,7 @@ struct GhostSet {
 struct GhostBC {
   const int *bcs;        // [nmb][6] AKMI_BC_*
   const double *in;      // inflow constants: u_in[nvar][6] (cell-centred set) / b_in[3][6] (face-centred set), may be null
-  double *dt3;           // when non-null: the three CFL minima are reset here (saves the k_init_dt3 launch of the last stage)
+  double *dt3;           // when non-null: the three CFL minima are reset here (saves the fill_fltmax launch of the last stage)
 };
 __host__ __device__ inline bool bc_is_physical(int f) {
   return f == AKMI_BC_REFLECT || f == AKMI_BC_OUTFLOW || f == AKMI_BC_INFLOW || f == AKMI_BC_DIODE || f == AKMI_BC_VACUUM;

@@ -7,6 +7,7 @@
 // One thread per face (edge), the arithmetic of each expression kept in the reference's order.
 // All of them are streaming kernels: a face reads its two (to eighteen) neighbouring cells.
 #include "akmi_common.hpp"
+#include "akmi_c2p.hpp"
 #include <cfloat>
 
 namespace akmi {
@@ -112,7 +113,7 @@ k_heat_flux(Geo g, double alpha_iso, double gm1, const double *__restrict__ w0,
 // Conduction::NewTimeStep, conduction.cpp:314-377: min over the active cells of
 // SQR(dx)/alpha*d/gm1 per direction.  Every factor is positive, so the expression is a monotone
 // function of d for a given block and the minimum over a block is the value at its minimum
-// density: reduce min(d) per wave, evaluate once per workgroup, one atomicMin if it can win.
+// density: reduce min(d) over the workgroup, evaluate once, one atomic minimum if it can win (akmi_c2p.hpp).
 __global__ void __launch_bounds__(DX*DY)
 k_cond_newdt(Geo g, double alpha_iso, double gm1, const double *__restrict__ w0,
              double *__restrict__ dtmin, int nk) {
@@ -120,25 +121,18 @@ k_cond_newdt(Geo g, double alpha_iso, double gm1, const double *__restrict__ w0,
   const int j = g.js + blockIdx.y*DY + threadIdx.y;
   const int m = blockIdx.z/nk;
   const int k = g.ks + (blockIdx.z - m*nk);
+  __shared__ double sm[DY];
   double d = DBL_MAX;
   if (i <= g.ie && j <= g.je) d = w0[ix5(g.nvar, g.N3, g.N2, g.N1, m, 0, k, j, i)];
-  for (int off = 32; off > 0; off >>= 1) d = fmin(d, __shfl_xor(d, off, 64));
-  __shared__ double sm[DY];
-  if ((threadIdx.x & 63) == 0) sm[threadIdx.y] = d;
-  __syncthreads();
+  d = wg_reduce<false>(d, sm, threadIdx.y*DX + threadIdx.x, DY);
   if (threadIdx.x == 0 && threadIdx.y == 0) {
-    for (int q = 1; q < DY; ++q) d = fmin(d, sm[q]);
     if (d == DBL_MAX) return;
     double v = sqr(g.dx[3*m])/alpha_iso*d/gm1;
     if (g.multi_d) v = fmin(v, sqr(g.dx[3*m + 1])/alpha_iso*d/gm1);
     if (g.three_d) v = fmin(v, sqr(g.dx[3*m + 2])/alpha_iso*d/gm1);
-    if (v < __hip_atomic_load(dtmin, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-      atomicMin(reinterpret_cast<unsigned long long *>(dtmin),
-                (unsigned long long)__double_as_longlong(v));
+    atomic_min_positive(dtmin, v);
   }
 }
-
-__global__ void k_set_fltmax(double *x) { if (threadIdx.x == 0) *x = (double)FLT_MAX; }
 
 struct Bf {                      // face-field access of MeshBlock m
   const double *b1, *b2, *b3;
@@ -487,27 +481,22 @@ k_resist_newdt(Geo g, double eta_o, double eta_a, const double *__restrict__ bcc
   const int j = g.js + blockIdx.y*DY + threadIdx.y;
   const int m = blockIdx.z/nk;
   const int k = g.ks + (blockIdx.z - m*nk);
+  __shared__ double sm[DY];
   double b2 = -1.0;
   if (i <= g.ie && j <= g.je) {
     const size_t cs = (size_t)g.N3*g.N2*g.N1;
     const size_t c = ix5(3, g.N3, g.N2, g.N1, m, 0, k, j, i);
     b2 = sqr(bcc0[c]) + sqr(bcc0[c + cs]) + sqr(bcc0[c + 2*cs]);
   }
-  for (int off = 32; off > 0; off >>= 1) b2 = fmax(b2, __shfl_xor(b2, off, 64));
-  __shared__ double sm[DY];
-  if ((threadIdx.x & 63) == 0) sm[threadIdx.y] = b2;
-  __syncthreads();
+  b2 = wg_reduce<true>(b2, sm, threadIdx.y*DX + threadIdx.x, DY);
   if (threadIdx.x == 0 && threadIdx.y == 0) {
-    for (int q = 1; q < DY; ++q) b2 = fmax(b2, sm[q]);
     if (b2 < 0.0) return;
     const double eta = eta_o + eta_a*b2;
     if (!(eta > 0.0)) return;
     double v = sqr(g.dx[3*m])/eta;
     if (g.multi_d) v = fmin(v, sqr(g.dx[3*m + 1])/eta);
     if (g.three_d) v = fmin(v, sqr(g.dx[3*m + 2])/eta);
-    if (v < __hip_atomic_load(dtmin, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-      atomicMin(reinterpret_cast<unsigned long long *>(dtmin),
-                (unsigned long long)__double_as_longlong(v));
+    atomic_min_positive(dtmin, v);
   }
 }
 
@@ -572,7 +561,7 @@ int akmi_conduction_newdt(const akmi_pack *p, double alpha_iso, const double *w0
                           void *stream) {
   Geo g = make_geo(p);
   hipStream_t st = (hipStream_t)stream;
-  k_set_fltmax<<<1, 64, 0, st>>>(dtmin);
+  fill_fltmax(dtmin, 1, st);
   const int nk = g.ke - g.ks + 1;
   dim3 grid(cdiv(g.nx1, DX), cdiv(g.je - g.js + 1, DY), nk*g.nmb), block(DX, DY);
   k_cond_newdt<<<grid, block, 0, st>>>(g, alpha_iso, p->gamma - 1.0, w0, dtmin, nk);
@@ -652,7 +641,7 @@ int akmi_resistive_newdt(const akmi_pack *p, double eta_ohm, double eta_ad, cons
                          double *dtmin, void *stream) {
   Geo g = make_geo(p);
   hipStream_t st = (hipStream_t)stream;
-  k_set_fltmax<<<1, 64, 0, st>>>(dtmin);
+  fill_fltmax(dtmin, 1, st);
   const int nk = g.ke - g.ks + 1;
   dim3 grid(cdiv(g.nx1, DX), cdiv(g.je - g.js + 1, DY), nk*g.nmb), block(DX, DY);
   k_resist_newdt<<<grid, block, 0, st>>>(g, eta_ohm, eta_ad, bcc0, dtmin, nk);

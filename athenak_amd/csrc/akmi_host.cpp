@@ -906,7 +906,7 @@ __global__ void k_mesh_newdt(Real *__restrict__ dt3, Real *__restrict__ st, Real
   if ((time < tlim) && ((time + dt) > tlim)) dt = tlim - time;
   st[0] = dt; st[1] = time;
   slot[0] = dt; slot[1] = time; slot[2] = dtnew;
-  dt3[0] = dt3[1] = dt3[2] = static_cast<Real>(FLT_MAX);    // the next cycle's scan starts from here (no k_init_dt3 launch)
+  dt3[0] = dt3[1] = dt3[2] = static_cast<Real>(FLT_MAX);    // the next cycle's scan starts from here (no fill_fltmax launch)
 }
 void Driver::EnqueueMeshNewDt(FluidBase *f) {
   Mesh *pm = f->pmy_pack->pmesh;

@@ -370,10 +370,10 @@ k_hydro_stage3d2(Geo g, FaceEos eos, const double *__restrict__ w0, UpdArgs u, i
         if (tfl) atomicAdd(&cp.counters[2], 1);
         cp.flags[(size_t)m*cs + (oc >> 3)] = (unsigned char)((dfl ? 1 : 0) | (efl ? 2 : 0) | (tfl ? 4 : 0));
         stu(wom, oc, wd); stu(wom + cs, oc, wvx); stu(wom + 2*cs, oc, wvy); stu(wom + 3*cs, oc, wvz); stu(wom + 4*cs, oc, we);
-        if (cp.do_newdt) {                             // hydro_newdt.cpp:97-118
-          const double pr = (cp.eos.gamma - 1.0)*we;
-          const double cs_ = sqrt(cp.eos.gamma*pr/wd);
-          mv1 = fmax(mv1, fabs(wvx) + cs_); mv2 = fmax(mv2, fabs(wvy) + cs_); mv3 = fmax(mv3, fabs(wvz) + cs_);
+        if (cp.do_newdt) {
+          double a1, a2, a3;
+          max_speeds_ideal<false>(cp.eos.gamma, wd, wvx, wvy, wvz, we, 0.0, 0.0, 0.0, a1, a2, a3);
+          mv1 = fmax(mv1, a1); mv2 = fmax(mv2, a2); mv3 = fmax(mv3, a3);
         }
       }
 #pragma unroll
@@ -391,21 +391,9 @@ k_hydro_stage3d2(Geo g, FaceEos eos, const double *__restrict__ w0, UpdArgs u, i
     oc += (unsigned)ps*8u; oh += (unsigned)ps*8u;
   }
   if constexpr (C2P) {
-    if (cp.do_newdt) {         // uniform across the grid: wave maxima, workgroup maxima through LDS, one division + filtered
-      __syncthreads();         // atomicMin per direction (min over cells of fl(dx/a) == fl(dx/max a): division is monotone)
-      mv1 = wave_max(mv1); mv2 = wave_max(mv2); mv3 = wave_max(mv3);
-      const int wv = tid >> 6, nwv = (int)(blockDim.x >> 6);
-      if ((tid & 63) == 0) { hs_lds[wv] = mv1; hs_lds[8 + wv] = mv2; hs_lds[16 + wv] = mv3; }
-      __syncthreads();
-      if (tid < 3) {
-        double v = hs_lds[8*tid];
-        for (int q = 1; q < nwv; ++q) v = fmax(v, hs_lds[8*tid + q]);
-        if (v > 0.0) {
-          const double d = g.dx[3*m + tid]/v;
-          if (d < __hip_atomic_load(&cp.dt3[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-            atomicMin(reinterpret_cast<unsigned long long *>(&cp.dt3[tid]), (unsigned long long)__double_as_longlong(d));
-        }
-      }
+    if (cp.do_newdt) {         // uniform across the grid
+      __syncthreads();         // the last plane's fluxes have been read: hs_lds is free
+      cfl_from_max(mv1, mv2, mv3, g.dx + 3*m, cp.dt3, hs_lds, tid, (int)(blockDim.x >> 6));
     }
   }
 #undef ISOSKIP

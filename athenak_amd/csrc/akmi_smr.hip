@@ -14,6 +14,7 @@
 // the other), a workgroup owns (block, component) and walks the slots with a barrier in between.
 #include <vector>
 #include "akmi_common.hpp"
+#include "akmi_c2p.hpp"
 
 namespace akmi {
 
@@ -351,13 +352,15 @@ k_smr_c2p_coarse(SGeo s, Tab t, Eos eos, int nvar, int mhd, double *__restrict__
     double wd, wx, wy, wz, we;
     bool f1 = false, f2 = false, f3 = false;
     if (mhd) {
-      const double bx = 0.5*(cb.b[0][f4(s, 1, 0, m, k, j, i)] + cb.b[0][f4(s, 1, 0, m, k, j, i + 1)]);
-      const double by = 0.5*(cb.b[1][f4(s, 1, 1, m, k, j, i)] + cb.b[1][f4(s, 1, 1, m, k, j + 1, i)]);
-      const double bz = 0.5*(cb.b[2][f4(s, 1, 2, m, k, j, i)] + cb.b[2][f4(s, 1, 2, m, k + 1, j, i)]);
-      c2p_mhd(eos, ud, umx, umy, umz, ue, bx, by, bz, wd, wx, wy, wz, we, f1, f2, f3);
+      double bx, by, bz;
+      cell_bcc(cb.b[0][f4(s, 1, 0, m, k, j, i)], cb.b[0][f4(s, 1, 0, m, k, j, i + 1)], cb.b[1][f4(s, 1, 1, m, k, j, i)],
+               cb.b[1][f4(s, 1, 1, m, k, j + 1, i)], cb.b[2][f4(s, 1, 2, m, k, j, i)], cb.b[2][f4(s, 1, 2, m, k + 1, j, i)],
+               bx, by, bz);
+      c2p_convert<true>(eos, ud, umx, umy, umz, ue, bx, by, bz, wd, wx, wy, wz, we, f1, f2, f3);
     } else {
-      c2p_hyd(eos, ud, umx, umy, umz, ue, wd, wx, wy, wz, we, f1, f2, f3);
+      c2p_convert<false>(eos, ud, umx, umy, umz, ue, 0.0, 0.0, 0.0, wd, wx, wy, wz, we, f1, f2, f3);
     }
+    // own stores, not c2p_commit: the floors are neither written back to cu nor counted (see above)
     cw[c5(s, 1, nvar, m, 0, k, j, i)] = wd; cw[c5(s, 1, nvar, m, 1, k, j, i)] = wx;
     cw[c5(s, 1, nvar, m, 2, k, j, i)] = wy; cw[c5(s, 1, nvar, m, 3, k, j, i)] = wz;
     cw[c5(s, 1, nvar, m, 4, k, j, i)] = we;
@@ -393,9 +396,10 @@ k_smr_p2c_fine(SGeo s, Tab t, int nvar, int mhd, const double *__restrict__ w, C
     u[c5(s, 0, nvar, m, 2, k, j, i)] = d*vy;
     u[c5(s, 0, nvar, m, 3, k, j, i)] = d*vz;
     if (mhd) {
-      const double bx = 0.5*(fb.b[0][f4(s, 0, 0, m, k, j, i)] + fb.b[0][f4(s, 0, 0, m, k, j, i + 1)]);
-      const double by = 0.5*(fb.b[1][f4(s, 0, 1, m, k, j, i)] + fb.b[1][f4(s, 0, 1, m, k, j + 1, i)]);
-      const double bz = 0.5*(fb.b[2][f4(s, 0, 2, m, k, j, i)] + fb.b[2][f4(s, 0, 2, m, k + 1, j, i)]);
+      double bx, by, bz;
+      cell_bcc(fb.b[0][f4(s, 0, 0, m, k, j, i)], fb.b[0][f4(s, 0, 0, m, k, j, i + 1)], fb.b[1][f4(s, 0, 1, m, k, j, i)],
+               fb.b[1][f4(s, 0, 1, m, k, j + 1, i)], fb.b[2][f4(s, 0, 2, m, k, j, i)], fb.b[2][f4(s, 0, 2, m, k + 1, j, i)],
+               bx, by, bz);
       u[c5(s, 0, nvar, m, 4, k, j, i)] = ei + 0.5*(d*(sqr(vx) + sqr(vy) + sqr(vz)) + (sqr(bx) + sqr(by) + sqr(bz)));
     } else {
       u[c5(s, 0, nvar, m, 4, k, j, i)] = ei + 0.5*d*(sqr(vx) + sqr(vy) + sqr(vz));

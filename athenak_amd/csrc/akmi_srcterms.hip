@@ -9,6 +9,7 @@
 // are not glibc's: that term agrees with a CPU evaluation to a few 1e-13 relative, not bit for bit.
 #include <cfloat>
 #include "akmi_common.hpp"
+#include "akmi_c2p.hpp"
 
 namespace akmi {
 namespace {
@@ -102,10 +103,11 @@ k_srcterms(Geo g, int is_ideal, int dir, double gacc, Cool c, double beta, doubl
 }
 
 // SourceTerms::NewTimeStep, srcterms_newdt.cpp:25-72 (ism_cooling): min over the active cells of
-// eint/(FLT_MIN + |rho*(rho*lambda - gamma_heating)|).  Wave reduction, LDS across the four waves, one filtered
-// 64-bit atomicMin per workgroup (positive doubles order like their bit patterns); a minimum does not depend on the order.
+// eint/(FLT_MIN + |rho*(rho*lambda - gamma_heating)|).  The minimum over the workgroup, then one filtered atomic minimum
+// (akmi_c2p.hpp); a minimum does not depend on the order.
 __global__ void __launch_bounds__(SX*SY)
 k_srcterms_newdt(Geo g, Cool c, const double *__restrict__ w0, double *__restrict__ dtmin, int fm) {
+  __shared__ double sm[SY];
   const Lane l = lane_of(g, fm);
   const size_t cs = (size_t)g.N3*g.N2*g.N1;
   const double *wm = w0 + l.mb;
@@ -114,18 +116,9 @@ k_srcterms_newdt(Geo g, Cool c, const double *__restrict__ w0, double *__restric
   cool_rates(c, rho, eint, lam, gh);
   const double cooling_heating = (double)FLT_MIN + fabs(rho*(rho*lam - gh));
   double v = l.in ? eint/cooling_heating : (double)FLT_MAX;
-  for (int off = 32; off > 0; off >>= 1) v = fmin(v, __shfl_xor(v, off, 64));
-  __shared__ double sm[SY];
-  if ((threadIdx.x & 63) == 0) sm[threadIdx.y] = v;
-  __syncthreads();
-  if (threadIdx.x == 0 && threadIdx.y == 0) {
-    for (int q = 1; q < SY; ++q) v = fmin(v, sm[q]);
-    if (v < __hip_atomic_load(dtmin, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-      atomicMin(reinterpret_cast<unsigned long long *>(dtmin), (unsigned long long)__double_as_longlong(v));
-  }
+  v = wg_reduce<false>(v, sm, threadIdx.y*SX + threadIdx.x, SY);
+  if (threadIdx.x == 0 && threadIdx.y == 0) atomic_min_positive(dtmin, v);
 }
-
-__global__ void k_srcterms_dt_init(double *x) { if (threadIdx.x == 0) *x = (double)FLT_MAX; }
 
 int check_args(const akmi_pack *p, const akmi_srcterms *s, const char *who) {
   if (!p || !s) { set_error("%s: null pack or parameter struct", who); return AKMI_FAIL; }
@@ -187,7 +180,7 @@ int akmi_srcterms_apply(const akmi_pack *p, const akmi_srcterms *s, double beta,
 int akmi_srcterms_newdt(const akmi_pack *p, const akmi_srcterms *s, const double *w0, double *dtmin, void *stream) {
   if (check_args(p, s, "srcterms_newdt") != AKMI_COMPLETE) return AKMI_FAIL;
   hipStream_t st = (hipStream_t)stream;
-  k_srcterms_dt_init<<<1, 64, 0, st>>>(dtmin);
+  fill_fltmax(dtmin, 1, st);
   if (s->ism_cooling) {
     const Geo g = make_geo(p);
     const int fm = lane_mode(g);

@@ -257,7 +257,7 @@ static int stage_update(const StageCall &c) {
     if (g.three_d) { a2.kl = g.ks - 1; a2.ku = g.ke + 1; }
     a3.il = g.is - 1; a3.iu = g.ie + 1; a3.jl = g.js - 1; a3.ju = g.je + 1;
   }
-  if (do_c2p && c.do_newdt == 1) launch_init_dt3(c.dt3, st);       // 2: the caller has reset the minima
+  if (do_c2p && c.do_newdt == 1) fill_fltmax(c.dt3, 3, st);       // 2: the caller has reset the minima
   bool c2p_done = false;              // ConsToPrim of the active cells happened inside the sweeps' kernel
   // the bytes of the mass-flux signs: k_sweep12s writes no x1 flux, so they take its place; the generic x1 sweep fills flx1
   // with the five fluxes the x2 march reads, and its bytes go behind those of x2 in the region of flx2, of which only

@@ -6,6 +6,8 @@
 //   akmi_stage_mhd.hip       k_sweep12s, k_corner_ct, k_ct_copy
 //   akmi_stage_hydro.hip     k_hydro_stage3d2 (akmi_hydro_stage3d2.hpp)
 //   akmi_stage_c2p.hip       ConsToPrim + CFL scan, with the entry points that need nothing else
+//   akmi_c2p.hpp             the conversion of one cell, the signal speeds and the reductions of a CFL scan, for these two
+//                            units and the task-granular ones (akmi_tasks, akmi_diffusion, akmi_srcterms, akmi_smr)
 //   akmi_stage.hip           the plan of a stage, stage_update and the remaining entry points: no kernel
 // The launchers are templates declared at the end of this file; each is instantiated explicitly in the unit that
 // defines it, for exactly the combinations the callers use -- a missed one is a link error.
@@ -15,6 +17,7 @@
 #define AKMI_STAGE_HPP_
 #include <cstdlib>
 #include "akmi_common.hpp"
+#include "akmi_c2p.hpp"
 
 namespace akmi {
 
@@ -131,12 +134,6 @@ inline int march_len(long col_blocks, int ncells, int nmb, int lmax, int wgs_per
   return (int)ml;
 }
 
-// maximum over the wave (the CFL scans of ConsToPrim and of the hydro stage kernel that converts its cells)
-__device__ __forceinline__ double wave_max(double v) {
-  for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
-  return v;
-}
-
 // ---------------------------------------------------------------------------------------
 // face flux from the cell stencil (registers only).  Returns flux in sweep-aligned order.
 template <int DIR, int RECON, bool MHD, int RS>
@@ -214,8 +211,7 @@ int launch_ct_copy(const Geo &g, const double *const *e, const CtArgs &c, hipStr
 // akmi_stage_march_x2.hip: the passive scalars of the planes [k0, k0 + nk)
 int launch_scalars(const Geo &g, const Scheme &sc, const double *w0, const double *m1, const double *m2,
                    const double *m3, const UpdArgs &u, int k0, int nk, hipStream_t st);
-// akmi_stage_c2p.hip
-void launch_init_dt3(double *dt3, hipStream_t st);
+// akmi_stage_c2p.hip (and fill_fltmax, declared in akmi_c2p.hpp)
 template <bool MHD, int DROP = 0>
 int launch_c2p(const Geo &g, const Eos &eos, double *u0, const double *bx1f, const double *bx2f, const double *bx3f,
                double *w0, double *bcc0, int do_newdt, int *counters, double *dt3, int il, int iu, int jl, int ju,

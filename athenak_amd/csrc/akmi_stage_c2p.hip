@@ -1,6 +1,8 @@
 // akmi_stage_c2p.hip -- pass B of a stage: ConsToPrim over a box of cells (+ the CFL scan on the last stage) in one
 // kernel, the conversion of the ghost shell, the fill of what a lean conversion dropped, and the entry points that need
-// nothing else (akmi_*_c2p_newdt[_lean], akmi_mhd_c2p_takes_pairs, akmi_mhd_prims_fill, akmi_*_c2p_shell).
+// nothing else (akmi_*_c2p, akmi_*_c2p_newdt[_lean], akmi_mhd_c2p_takes_pairs, akmi_mhd_prims_fill, akmi_*_c2p_shell).
+// The conversion of a cell, the signal speeds and the reduction of the scan: akmi_c2p.hpp.
+#include <cfloat>
 #include "akmi_stage.hpp"
 
 namespace akmi {
@@ -12,23 +14,8 @@ namespace akmi {
 #define AKMI_C2P_PAIRS_MIN 4000000l
 #endif
 
-// SingleC2P_IsothermalHyd / _IsothermalMHD (isothermal_hyd.cpp:30-45, isothermal_mhd.cpp:32-47; density
-// floor fmax(dfloor, b^2/sigma_max) :104-106): no energy variable, scalars from variable 4 without a floor
-template <bool MHD>
-__device__ __forceinline__ void c2p_iso_cell(const Geo &g, const Eos &eos, double *__restrict__ u0,
-                                             double *__restrict__ w0, size_t c, size_t cs, double ubx,
-                                             double uby, double ubz, int *__restrict__ counters, double &wd,
-                                             double &wvx, double &wvy, double &wvz) {
-  double ud = u0[c];
-  double dfloor_ = eos.dfloor;
-  if constexpr (MHD) dfloor_ = fmax(eos.dfloor, (sqr(ubx) + sqr(uby) + sqr(ubz))/eos.sigma_max);
-  if (ud < dfloor_) { ud = dfloor_; u0[c] = ud; atomicAdd(&counters[0], 1); }
-  const double di = 1.0/ud;
-  wd = ud; wvx = di*u0[c + cs]; wvy = di*u0[c + 2*cs]; wvz = di*u0[c + 3*cs];
-  w0[c] = wd; w0[c + cs] = wvx; w0[c + 2*cs] = wvy; w0[c + 3*cs] = wvz;
-  for (int n = 4; n < g.nvar; ++n) w0[c + n*cs] = u0[c + n*cs]/ud;
-}
-
+// cells [il,iu] x [jl,ju] x [k0,k0+nk-1]; lanes over the flattened rows [jl,ju] x N1 of one plane (flat_cells, akmi_common.hpp;
+// with the planes flattened too this kernel is slower on small MeshBlocks: 49 -> 60 us on 120 blocks of 16^3).
 // DROP (mask of AKMI_DROP_*, ideal gas only): the lean conversion -- w0[0..3] and / or bcc0 are computed as always but not
 // stored; a caller whose next sweeps take them from u0 and the faces (AKMI_COPY_X12_U0 / AKMI_COPY_BCC_FACES) asks for it
 template <bool MHD, int DROP = 0>
@@ -38,89 +25,29 @@ k_c2p_newdt(Geo g, Eos eos, double *__restrict__ u0, const double *__restrict__ 
             double *__restrict__ w0, double *__restrict__ bcc0, int do_newdt,
             int *__restrict__ counters, double *__restrict__ dt3, int il, int iu, int jl, int ju,
             int k0, int nk) {
-  // cells [il,iu] x [jl,ju] x [k0,k0+nk-1]; lanes over the flattened rows [jl,ju] x N1 of one plane (flat_cells, akmi_common.hpp;
-  // with the planes flattened too this kernel is slower on small MeshBlocks: 49 -> 60 us on 120 blocks of 16^3)
-  __shared__ double sm[3][SY];
+  __shared__ double sm[3*SY];
   const Cell3 q = flat_cells(0, g.N1, il, iu, jl, ju - jl + 1, k0, nk);
   const int i = q.i, j = q.j, k = q.k, m = q.m;
   double mv1 = 0.0, mv2 = 0.0, mv3 = 0.0;
   if (q.in) {
     const size_t cs = (size_t)g.N3*g.N2*g.N1;
     const size_t c = ix5(g.nvar, g.N3, g.N2, g.N1, m, 0, k, j, i);
-    double wd, wvx, wvy, wvz, we = 0.0, ubx = 0, uby = 0, ubz = 0;
+    double ud, ue, wd, wvx, wvy, wvz, we, ubx = 0.0, uby = 0.0, ubz = 0.0;
+    bool dfl = false, efl = false, tfl = false;
     if constexpr (MHD) {
-      ubx = bcc_from_faces(bx1f[ix4(g.N3, g.N2, g.N1 + 1, m, k, j, i)],
-                           bx1f[ix4(g.N3, g.N2, g.N1 + 1, m, k, j, i + 1)]);
-      uby = bcc_from_faces(bx2f[ix4(g.N3, g.N2 + 1, g.N1, m, k, j, i)],
-                           bx2f[ix4(g.N3, g.N2 + 1, g.N1, m, k, j + 1, i)]);
-      ubz = bcc_from_faces(bx3f[ix4(g.N3 + 1, g.N2, g.N1, m, k, j, i)],
-                           bx3f[ix4(g.N3 + 1, g.N2, g.N1, m, k + 1, j, i)]);
+      cell_bcc(g, bx1f, bx2f, bx3f, m, k, j, i, ubx, uby, ubz);
       if constexpr (!(DROP & AKMI_DROP_BCC)) {
         const size_t b = ix5(3, g.N3, g.N2, g.N1, m, 0, k, j, i);
         bcc0[b] = ubx; bcc0[b + cs] = uby; bcc0[b + 2*cs] = ubz;
       }
     }
-    const bool scan = do_newdt && i >= g.is && i <= g.ie && j >= g.js && j <= g.je && k >= g.ks && k <= g.ke;
-    if (!eos.is_ideal) {
-      c2p_iso_cell<MHD>(g, eos, u0, w0, c, cs, ubx, uby, ubz, counters, wd, wvx, wvy, wvz);
-      if (scan) {                             // hydro_newdt.cpp:109-111, mhd_newdt.cpp:137-144
-        if constexpr (MHD) {
-          mv1 = fabs(wvx) + fast_speed_iso(eos.iso_cs, wd, ubx, uby, ubz);
-          mv2 = fabs(wvy) + fast_speed_iso(eos.iso_cs, wd, uby, ubz, ubx);
-          mv3 = fabs(wvz) + fast_speed_iso(eos.iso_cs, wd, ubz, ubx, uby);
-        } else {
-          mv1 = fabs(wvx) + eos.iso_cs; mv2 = fabs(wvy) + eos.iso_cs; mv3 = fabs(wvz) + eos.iso_cs;
-        }
-      }
-    } else {
-    double ud = u0[c], umx = u0[c + cs], umy = u0[c + 2*cs], umz = u0[c + 3*cs], ue = u0[c + 4*cs];
-    bool dfl = false, efl = false, tfl = false;
-    if constexpr (MHD) {
-      c2p_mhd(eos, ud, umx, umy, umz, ue, ubx, uby, ubz, wd, wvx, wvy, wvz, we, dfl, efl, tfl);
-    } else {
-      c2p_hyd(eos, ud, umx, umy, umz, ue, wd, wvx, wvy, wvz, we, dfl, efl, tfl);
-    }
-    if (dfl) { u0[c] = ud; atomicAdd(&counters[0], 1); }
-    if (efl) { u0[c + 4*cs] = ue; atomicAdd(&counters[1], 1); }
-    if (tfl) { u0[c + 4*cs] = ue; atomicAdd(&counters[2], 1); }
-    if constexpr (!(DROP & AKMI_DROP_W03)) { w0[c] = wd; w0[c + cs] = wvx; w0[c + 2*cs] = wvy; w0[c + 3*cs] = wvz; }
-    w0[c + 4*cs] = we;
-    for (int n = 5; n < g.nvar; ++n) {        // scalars with their floor, ideal_hyd.cpp:94-101
-      double us = u0[c + n*cs];
-      if (us < 0.0) { us = 0.0; u0[c + n*cs] = 0.0; }
-      w0[c + n*cs] = us/ud;
-    }
-    if (scan) {
-      // hydro_newdt.cpp:97-118 / mhd_newdt.cpp:123-136
-      const double pr = (eos.gamma - 1.0)*we;
-      if constexpr (MHD) {
-        mv1 = fabs(wvx) + fast_speed(eos.gamma, wd, pr, ubx, uby, ubz);
-        mv2 = fabs(wvy) + fast_speed(eos.gamma, wd, pr, uby, ubz, ubx);
-        mv3 = fabs(wvz) + fast_speed(eos.gamma, wd, pr, ubz, ubx, uby);
-      } else {
-        const double cs_ = sqrt(eos.gamma*pr/wd);
-        mv1 = fabs(wvx) + cs_; mv2 = fabs(wvy) + cs_; mv3 = fabs(wvz) + cs_;
-      }
-    }
-    }
+    c2p_convert_at<MHD>(eos, u0, c, cs, ud, ue, ubx, uby, ubz, wd, wvx, wvy, wvz, we, dfl, efl, tfl);
+    c2p_commit<DROP>(g, eos, u0, w0, counters, c, cs, ud, ue, wd, wvx, wvy, wvz, we, dfl, efl, tfl);
+    if (do_newdt && i >= g.is && i <= g.ie && j >= g.js && j <= g.je && k >= g.ks && k <= g.ke)
+      max_speeds<MHD>(eos, wd, wvx, wvy, wvz, we, ubx, uby, ubz, mv1, mv2, mv3);
   }
   if (!do_newdt) return;        // uniform across the grid
-  mv1 = wave_max(mv1); mv2 = wave_max(mv2); mv3 = wave_max(mv3);
-  if ((threadIdx.x & 63) == 0) { sm[0][threadIdx.y] = mv1; sm[1][threadIdx.y] = mv2; sm[2][threadIdx.y] = mv3; }
-  __syncthreads();
-  if (threadIdx.y == 0 && threadIdx.x < 3) {
-    double v = sm[threadIdx.x][0];
-    for (int q = 1; q < SY; ++q) v = fmax(v, sm[threadIdx.x][q]);
-    if (v > 0.0) {
-      // min over cells of fl(dx/a) == fl(dx/max a): correctly rounded division is monotone
-      const double d = g.dx[3*m + threadIdx.x]/v;
-      // one word saturates at ~88 atomics/us on this chip: only workgroups that can lower the
-      // running minimum issue the atomic (the plain read is a filter, the atomic decides)
-      if (d < __hip_atomic_load(&dt3[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-        atomicMin(reinterpret_cast<unsigned long long *>(&dt3[threadIdx.x]),
-                  (unsigned long long)__double_as_longlong(d));
-    }
-  }
+  cfl_from_max(mv1, mv2, mv3, g.dx + 3*m, dt3, sm, threadIdx.y*SX + threadIdx.x, SY);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -137,7 +64,7 @@ __device__ __forceinline__ void st2nt(double *p, double a, double b) {
   __builtin_nontemporal_store(v, reinterpret_cast<d2_t *>(p));
 }
 
-// (MHD: 86 VGPRs, five waves per SIMD; held to 80 / 64 registers it spills and runs at 383 / 605 us against 364-389,
+// (MHD: 88 VGPRs, 94 without the stores of w0[0..3] -- at most 96, five waves per SIMD; held to 80 / 64 registers it spills and runs at 383 / 605 us against 364-389,
 //  profiles/r05_c2p_pairs.txt)
 template <bool MHD, int DROP = 0>
 __global__ void __launch_bounds__(SX*SY)
@@ -147,7 +74,7 @@ k_c2p_newdt2(Geo g, Eos eos, double *__restrict__ u0, const double *__restrict__
              int *__restrict__ counters, double *__restrict__ dt3, int il, int iu, int jl, int ju,
              int k0, int nk) {
   // cells [il,iu] x [jl,ju] x [k0,k0+nk-1], il even and iu odd; lanes run over the cell PAIRS of the flattened rows
-  __shared__ double sm[3][SY];
+  __shared__ double sm[3*SY];
   const int hw = g.N1 >> 1;
   const long p = ((long)blockIdx.x*SY + threadIdx.y)*SX + threadIdx.x;
   const int jj = (int)(p/hw);
@@ -182,26 +109,15 @@ k_c2p_newdt2(Geo g, Eos eos, double *__restrict__ u0, const double *__restrict__
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
       bool dfl = false, efl = false, tfl = false;
-      if constexpr (MHD) {
-        c2p_mhd(eos, ud[q], umx[q], umy[q], umz[q], ue[q], ubx[q], uby[q], ubz[q], wd[q], wvx[q], wvy[q], wvz[q], we[q],
-                dfl, efl, tfl);
-      } else {
-        c2p_hyd(eos, ud[q], umx[q], umy[q], umz[q], ue[q], wd[q], wvx[q], wvy[q], wvz[q], we[q], dfl, efl, tfl);
-      }
+      c2p_ideal<MHD>(eos, ud[q], umx[q], umy[q], umz[q], ue[q], ubx[q], uby[q], ubz[q], wd[q], wvx[q], wvy[q], wvz[q],
+                     we[q], dfl, efl, tfl);
       if (dfl) { u0[c + q] = ud[q]; atomicAdd(&counters[0], 1); }
       if (efl) { u0[c + q + 4*cs] = ue[q]; atomicAdd(&counters[1], 1); }
       if (tfl) { u0[c + q + 4*cs] = ue[q]; atomicAdd(&counters[2], 1); }
       if (act && i + q >= g.is && i + q <= g.ie) {
-        // hydro_newdt.cpp:97-118 / mhd_newdt.cpp:123-136
-        const double pr = (eos.gamma - 1.0)*we[q];
-        if constexpr (MHD) {
-          mv1 = fmax(mv1, fabs(wvx[q]) + fast_speed(eos.gamma, wd[q], pr, ubx[q], uby[q], ubz[q]));
-          mv2 = fmax(mv2, fabs(wvy[q]) + fast_speed(eos.gamma, wd[q], pr, uby[q], ubz[q], ubx[q]));
-          mv3 = fmax(mv3, fabs(wvz[q]) + fast_speed(eos.gamma, wd[q], pr, ubz[q], ubx[q], uby[q]));
-        } else {
-          const double cs_ = sqrt(eos.gamma*pr/wd[q]);
-          mv1 = fmax(mv1, fabs(wvx[q]) + cs_); mv2 = fmax(mv2, fabs(wvy[q]) + cs_); mv3 = fmax(mv3, fabs(wvz[q]) + cs_);
-        }
+        double a1, a2, a3;
+        max_speeds_ideal<MHD>(eos.gamma, wd[q], wvx[q], wvy[q], wvz[q], we[q], ubx[q], uby[q], ubz[q], a1, a2, a3);
+        mv1 = fmax(mv1, a1); mv2 = fmax(mv2, a2); mv3 = fmax(mv3, a3);
       }
     }
     if constexpr (!(DROP & AKMI_DROP_W03)) {
@@ -211,25 +127,13 @@ k_c2p_newdt2(Geo g, Eos eos, double *__restrict__ u0, const double *__restrict__
     st2nt(w0 + c + 4*cs, we[0], we[1]);
   }
   if (!do_newdt) return;        // uniform across the grid
-  mv1 = wave_max(mv1); mv2 = wave_max(mv2); mv3 = wave_max(mv3);
-  if ((threadIdx.x & 63) == 0) { sm[0][threadIdx.y] = mv1; sm[1][threadIdx.y] = mv2; sm[2][threadIdx.y] = mv3; }
-  __syncthreads();
-  if (threadIdx.y == 0 && threadIdx.x < 3) {
-    double v = sm[threadIdx.x][0];
-    for (int q = 1; q < SY; ++q) v = fmax(v, sm[threadIdx.x][q]);
-    if (v > 0.0) {
-      const double d = g.dx[3*m + threadIdx.x]/v;
-      if (d < __hip_atomic_load(&dt3[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-        atomicMin(reinterpret_cast<unsigned long long *>(&dt3[threadIdx.x]),
-                  (unsigned long long)__double_as_longlong(d));
-    }
-  }
+  cfl_from_max(mv1, mv2, mv3, g.dx + 3*m, dt3, sm, threadIdx.y*SX + threadIdx.x, SY);
 }
 
-__global__ void k_init_dt3(double *dt3) {
-  if (threadIdx.x < 3) dt3[threadIdx.x] = (double)FLT_MAX;
+__global__ void k_fill_fltmax(double *x, int n) {
+  if ((int)threadIdx.x < n) x[threadIdx.x] = (double)FLT_MAX;
 }
-void launch_init_dt3(double *dt3, hipStream_t st) { k_init_dt3<<<1, 64, 0, st>>>(dt3); }
+void fill_fltmax(double *x, int n, hipStream_t st) { k_fill_fltmax<<<1, 64, 0, st>>>(x, n); }
 
 // ---------------------------------------------------------------------------------------
 // c2p on the ghost SHELL only (after the halo exchange): the interior was converted inside
@@ -262,35 +166,15 @@ k_c2p_shell(Geo g, Eos eos, double *__restrict__ u0, const double *__restrict__ 
   else { i = ii < g.ng ? ii : g.ie + 1 + (ii - g.ng); j = g.js + jj; k = g.ks + kk; }
   const size_t cs = (size_t)g.N3*g.N2*g.N1;
   const size_t c = ix5(g.nvar, g.N3, g.N2, g.N1, m, 0, k, j, i);
-  double wd, wvx, wvy, wvz, we;
-  double ubx = 0.0, uby = 0.0, ubz = 0.0;
+  double ud, ue, wd, wvx, wvy, wvz, we, ubx = 0.0, uby = 0.0, ubz = 0.0;
+  bool dfl = false, efl = false, tfl = false;
   if constexpr (MHD) {
-    ubx = bcc_from_faces(bx1f[ix4(g.N3, g.N2, g.N1 + 1, m, k, j, i)], bx1f[ix4(g.N3, g.N2, g.N1 + 1, m, k, j, i + 1)]);
-    uby = bcc_from_faces(bx2f[ix4(g.N3, g.N2 + 1, g.N1, m, k, j, i)], bx2f[ix4(g.N3, g.N2 + 1, g.N1, m, k, j + 1, i)]);
-    ubz = bcc_from_faces(bx3f[ix4(g.N3 + 1, g.N2, g.N1, m, k, j, i)], bx3f[ix4(g.N3 + 1, g.N2, g.N1, m, k + 1, j, i)]);
+    cell_bcc(g, bx1f, bx2f, bx3f, m, k, j, i, ubx, uby, ubz);
     const size_t b = ix5(3, g.N3, g.N2, g.N1, m, 0, k, j, i);
     bcc0[b] = ubx; bcc0[b + cs] = uby; bcc0[b + 2*cs] = ubz;
   }
-  if (!eos.is_ideal) {
-    c2p_iso_cell<MHD>(g, eos, u0, w0, c, cs, ubx, uby, ubz, counters, wd, wvx, wvy, wvz);
-    return;
-  }
-  double ud = u0[c], umx = u0[c + cs], umy = u0[c + 2*cs], umz = u0[c + 3*cs], ue = u0[c + 4*cs];
-  bool dfl = false, efl = false, tfl = false;
-  if constexpr (MHD) {
-    c2p_mhd(eos, ud, umx, umy, umz, ue, ubx, uby, ubz, wd, wvx, wvy, wvz, we, dfl, efl, tfl);
-  } else {
-    c2p_hyd(eos, ud, umx, umy, umz, ue, wd, wvx, wvy, wvz, we, dfl, efl, tfl);
-  }
-  if (dfl) { u0[c] = ud; atomicAdd(&counters[0], 1); }
-  if (efl) { u0[c + 4*cs] = ue; atomicAdd(&counters[1], 1); }
-  if (tfl) { u0[c + 4*cs] = ue; atomicAdd(&counters[2], 1); }
-  w0[c] = wd; w0[c + cs] = wvx; w0[c + 2*cs] = wvy; w0[c + 3*cs] = wvz; w0[c + 4*cs] = we;
-  for (int n = 5; n < g.nvar; ++n) {
-    double us = u0[c + n*cs];
-    if (us < 0.0) { us = 0.0; u0[c + n*cs] = 0.0; }
-    w0[c + n*cs] = us/ud;
-  }
+  c2p_convert_at<MHD>(eos, u0, c, cs, ud, ue, ubx, uby, ubz, wd, wvx, wvy, wvz, we, dfl, efl, tfl);
+  c2p_commit(g, eos, u0, w0, counters, c, cs, ud, ue, wd, wvx, wvy, wvz, we, dfl, efl, tfl);
 }
 
 template <bool MHD>
@@ -320,9 +204,9 @@ k_prims_fill(Geo g, const double *__restrict__ u0, const double *__restrict__ bx
   const size_t cs = (size_t)g.N3*g.N2*g.N1;
   if constexpr ((DROP & AKMI_DROP_BCC) != 0) {
     const size_t b = ix5(3, g.N3, g.N2, g.N1, m, 0, k, j, i);
-    bcc0[b] = bcc_from_faces(bx1f[ix4(g.N3, g.N2, g.N1 + 1, m, k, j, i)], bx1f[ix4(g.N3, g.N2, g.N1 + 1, m, k, j, i + 1)]);
-    bcc0[b + cs] = bcc_from_faces(bx2f[ix4(g.N3, g.N2 + 1, g.N1, m, k, j, i)], bx2f[ix4(g.N3, g.N2 + 1, g.N1, m, k, j + 1, i)]);
-    bcc0[b + 2*cs] = bcc_from_faces(bx3f[ix4(g.N3 + 1, g.N2, g.N1, m, k, j, i)], bx3f[ix4(g.N3 + 1, g.N2, g.N1, m, k + 1, j, i)]);
+    double ubx, uby, ubz;
+    cell_bcc(g, bx1f, bx2f, bx3f, m, k, j, i, ubx, uby, ubz);
+    bcc0[b] = ubx; bcc0[b + cs] = uby; bcc0[b + 2*cs] = ubz;
   }
   if constexpr ((DROP & AKMI_DROP_W03) != 0) {
     const size_t c = ix5(g.nvar, g.N3, g.N2, g.N1, m, 0, k, j, i);
@@ -381,11 +265,26 @@ using namespace akmi;
 
 extern "C" {
 
+// ConsToPrim of a box (the task-granular entry points; ideal_hyd.cpp:45-103, ideal_mhd.cpp:47-122): the conversion of
+// pass B without its scan
+int akmi_hydro_c2p(const akmi_pack *p, double *u0, double *w0, int il, int iu, int jl, int ju,
+                   int kl, int ku, int *counters, void *stream) {
+  return launch_c2p<false>(make_geo(p), make_eos(p), u0, nullptr, nullptr, nullptr, w0, nullptr, 0, counters, nullptr,
+                           il, iu, jl, ju, kl, ku - kl + 1, (hipStream_t)stream);
+}
+
+int akmi_mhd_c2p(const akmi_pack *p, double *u0, const double *bx1f, const double *bx2f,
+                 const double *bx3f, double *w0, double *bcc0, int il, int iu, int jl, int ju,
+                 int kl, int ku, int *counters, void *stream) {
+  return launch_c2p<true>(make_geo(p), make_eos(p), u0, bx1f, bx2f, bx3f, w0, bcc0, 0, counters, nullptr,
+                          il, iu, jl, ju, kl, ku - kl + 1, (hipStream_t)stream);
+}
+
 int akmi_hydro_c2p_newdt(const akmi_pack *p, double *u0, double *w0, int do_newdt, int *counters,
                          double *dt3, void *stream) {
   Geo g = make_geo(p);
   hipStream_t st = (hipStream_t)stream;
-  if (do_newdt == 1) launch_init_dt3(dt3, st);
+  if (do_newdt == 1) fill_fltmax(dt3, 3, st);
   return launch_c2p<false>(g, make_eos(p), u0, nullptr, nullptr, nullptr, w0, nullptr, do_newdt,
                            counters, dt3, 0, g.N1 - 1, 0, g.N2 - 1, 0, g.N3, st);
 }
@@ -395,7 +294,7 @@ int akmi_mhd_c2p_newdt(const akmi_pack *p, double *u0, const double *bx1f, const
                        double *dt3, void *stream) {
   Geo g = make_geo(p);
   hipStream_t st = (hipStream_t)stream;
-  if (do_newdt == 1) launch_init_dt3(dt3, st);
+  if (do_newdt == 1) fill_fltmax(dt3, 3, st);
   return launch_c2p<true>(g, make_eos(p), u0, bx1f, bx2f, bx3f, w0, bcc0, do_newdt, counters, dt3,
                           0, g.N1 - 1, 0, g.N2 - 1, 0, g.N3, st);
 }
@@ -410,7 +309,7 @@ int akmi_mhd_c2p_newdt_lean(const akmi_pack *p, double *u0, const double *bx1f, 
   }
   Geo g = make_geo(p);
   hipStream_t st = (hipStream_t)stream;
-  if (do_newdt == 1) launch_init_dt3(dt3, st);
+  if (do_newdt == 1) fill_fltmax(dt3, 3, st);
   auto go = [&](auto D) {
     return launch_c2p<true, decltype(D)::value>(g, make_eos(p), u0, bx1f, bx2f, bx3f, w0, bcc0, do_newdt, counters, dt3,
                                                 0, g.N1 - 1, 0, g.N2 - 1, 0, g.N3, st);

@@ -8,6 +8,7 @@
 // row segment; blockDim = (64,4): one wave64 per j-row, 4 rows per workgroup.
 #include <cstdarg>
 #include "akmi_common.hpp"
+#include "akmi_c2p.hpp"
 
 namespace akmi {
 
@@ -96,6 +97,40 @@ static int launch_hydro_flux(const Geo &g, const Scheme &sc, const double *w0,
 
 // ---------------------------------------------------------------------------------------
 // RKUpdate: hydro_update.cpp:50-81
+// cell sizes that are powers of two (every level of a refined mesh on a 2^n root grid): x/dx as one v_ldexp_f64,
+// bit for bit the quotient (akmi_common.hpp pow2_shift; tests/test_gpu_fastmath.py)
+struct DxDiv {
+  double dx1, dx2, dx3;
+  bool p2;
+  int n1, n2, n3;
+  __device__ DxDiv(const Geo &g, int m) : dx1(g.dx[3*m]), dx2(g.dx[3*m + 1]), dx3(g.dx[3*m + 2]) {
+    p2 = is_pow2(dx1) && is_pow2(dx2) && is_pow2(dx3);
+    n1 = pow2_shift(dx1); n2 = pow2_shift(dx2); n3 = pow2_shift(dx3);
+  }
+  AKMI_DEV double by1(double x) const { return p2 ? ldexp(x, n1) : x/dx1; }
+  AKMI_DEV double by2(double x) const { return p2 ? ldexp(x, n2) : x/dx2; }
+  AKMI_DEV double by3(double x) const { return p2 ? ldexp(x, n3) : x/dx3; }
+};
+
+// the flux divergence of variable n in cell (m, k, j, i)
+AKMI_DEV double flux_div(const Geo &g, const double *__restrict__ flx1, const double *__restrict__ flx2,
+                         const double *__restrict__ flx3, int fsh, int m, int n, int k, int j, int i, const DxDiv &d) {
+  const double d1 = flx1[ix5(g.nvar, g.N3, g.N2, g.N1 + fsh, m, n, k, j, i + 1)] -
+                    flx1[ix5(g.nvar, g.N3, g.N2, g.N1 + fsh, m, n, k, j, i)];
+  double divf = d.by1(d1);
+  if (g.multi_d) {
+    const double d2 = flx2[ix5(g.nvar, g.N3, g.N2 + fsh, g.N1, m, n, k, j + 1, i)] -
+                      flx2[ix5(g.nvar, g.N3, g.N2 + fsh, g.N1, m, n, k, j, i)];
+    divf += d.by2(d2);
+  }
+  if (g.three_d) {
+    const double d3 = flx3[ix5(g.nvar, g.N3 + fsh, g.N2, g.N1, m, n, k + 1, j, i)] -
+                      flx3[ix5(g.nvar, g.N3 + fsh, g.N2, g.N1, m, n, k, j, i)];
+    divf += d.by3(d3);
+  }
+  return divf;
+}
+
 __global__ void __launch_bounds__(BX*BY)
 k_rk_update(Geo g, double gam0, double gam1, double beta_dt, double *__restrict__ u0,
             const double *__restrict__ u1, const double *__restrict__ flx1,
@@ -103,25 +138,9 @@ k_rk_update(Geo g, double gam0, double gam1, double beta_dt, double *__restrict_
   const Cell3 q = flat_cells(fm, g.N1, g.is, g.ie, g.js, g.nx2, g.ks, g.nx3);
   const int i = q.i, j = q.j, k = q.k, m = q.m;
   if (!q.in) return;
-  const double dx1 = g.dx[3*m], dx2 = g.dx[3*m + 1], dx3 = g.dx[3*m + 2];
-  // cell sizes that are powers of two (every level of a refined mesh on a 2^n root grid): x/dx as one v_ldexp_f64,
-  // bit for bit the quotient (akmi_common.hpp pow2_shift; tests/test_gpu_fastmath.py)
-  const bool p2 = is_pow2(dx1) && is_pow2(dx2) && is_pow2(dx3);
-  const int n1 = pow2_shift(dx1), n2 = pow2_shift(dx2), n3 = pow2_shift(dx3);
+  const DxDiv d(g, m);
   for (int n = 0; n < g.nvar; ++n) {
-    const double d1 = flx1[ix5(g.nvar, g.N3, g.N2, g.N1 + fsh, m, n, k, j, i + 1)] -
-                      flx1[ix5(g.nvar, g.N3, g.N2, g.N1 + fsh, m, n, k, j, i)];
-    double divf = p2 ? ldexp(d1, n1) : d1/dx1;
-    if (g.multi_d) {
-      const double d2 = flx2[ix5(g.nvar, g.N3, g.N2 + fsh, g.N1, m, n, k, j + 1, i)] -
-                        flx2[ix5(g.nvar, g.N3, g.N2 + fsh, g.N1, m, n, k, j, i)];
-      divf += p2 ? ldexp(d2, n2) : d2/dx2;
-    }
-    if (g.three_d) {
-      const double d3 = flx3[ix5(g.nvar, g.N3 + fsh, g.N2, g.N1, m, n, k + 1, j, i)] -
-                        flx3[ix5(g.nvar, g.N3 + fsh, g.N2, g.N1, m, n, k, j, i)];
-      divf += p2 ? ldexp(d3, n3) : d3/dx3;
-    }
+    const double divf = flux_div(g, flx1, flx2, flx3, fsh, m, n, k, j, i, d);
     size_t c = ix5(g.nvar, g.N3, g.N2, g.N1, m, n, k, j, i);
     u0[c] = gam0*u0[c] + gam1*u1[c] - beta_dt*divf;
   }
@@ -140,160 +159,40 @@ k_rk_update_oop(Geo g, double gam0, double gam1, double beta_dt, const double *_
   const int i = q.i, j = q.j, k = q.k, m = q.m;
   if (!q.in) return;
   const bool act = i >= g.is && i <= g.ie && j >= g.js && j <= g.je && k >= g.ks && k <= g.ke;
-  const double dx1 = g.dx[3*m], dx2 = g.dx[3*m + 1], dx3 = g.dx[3*m + 2];
-  const bool p2 = is_pow2(dx1) && is_pow2(dx2) && is_pow2(dx3);
-  const int n1 = pow2_shift(dx1), n2 = pow2_shift(dx2), n3 = pow2_shift(dx3);
+  const DxDiv d(g, m);
   for (int n = 0; n < g.nvar; ++n) {
     const size_t c = ix5(g.nvar, g.N3, g.N2, g.N1, m, n, k, j, i);
     const double old = src[c];
     if (!act) { dst[c] = old; continue; }
-    const double d1 = flx1[ix5(g.nvar, g.N3, g.N2, g.N1 + fsh, m, n, k, j, i + 1)] -
-                      flx1[ix5(g.nvar, g.N3, g.N2, g.N1 + fsh, m, n, k, j, i)];
-    double divf = p2 ? ldexp(d1, n1) : d1/dx1;
-    if (g.multi_d) {
-      const double d2 = flx2[ix5(g.nvar, g.N3, g.N2 + fsh, g.N1, m, n, k, j + 1, i)] -
-                        flx2[ix5(g.nvar, g.N3, g.N2 + fsh, g.N1, m, n, k, j, i)];
-      divf += p2 ? ldexp(d2, n2) : d2/dx2;
-    }
-    if (g.three_d) {
-      const double d3 = flx3[ix5(g.nvar, g.N3 + fsh, g.N2, g.N1, m, n, k + 1, j, i)] -
-                        flx3[ix5(g.nvar, g.N3 + fsh, g.N2, g.N1, m, n, k, j, i)];
-      divf += p2 ? ldexp(d3, n3) : d3/dx3;
-    }
-    dst[c] = gam0*old + gam1*old - beta_dt*divf;
+    dst[c] = gam0*old + gam1*old - beta_dt*flux_div(g, flx1, flx2, flx3, fsh, m, n, k, j, i, d);
   }
 }
+
+// (ConsToPrim, ideal_hyd.cpp:45-103 / ideal_mhd.cpp:47-122: akmi_*_c2p are the conversion of pass B, akmi_stage_c2p.hip)
 
 // ---------------------------------------------------------------------------------------
-// ConsToPrim: ideal_hyd.cpp:45-103, ideal_mhd.cpp:47-122.  Floor counters: one wave-level
-// ballot + one atomicAdd per wave that actually hit a floor (never on the hot path).
-template <bool MHD>
-__global__ void __launch_bounds__(BX*BY)
-k_c2p(Geo g, Eos eos, double *__restrict__ u0, const double *__restrict__ bx1f,
-      const double *__restrict__ bx2f, const double *__restrict__ bx3f,
-      double *__restrict__ w0, double *__restrict__ bcc0, int il, int iu, int jl, int ju,
-      int kl, int nk, int *__restrict__ counters) {
-  const Cell3 q = flat_cells(0, g.N1, il, iu, jl, ju - jl + 1, kl, nk);
-  const int i = q.i, j = q.j, k = q.k, m = q.m;
-  if (!q.in) return;
-  const size_t cs = (size_t)g.N3*g.N2*g.N1;
-  const size_t c = ix5(g.nvar, g.N3, g.N2, g.N1, m, 0, k, j, i);
-  double ubx = 0.0, uby = 0.0, ubz = 0.0;
-  if constexpr (MHD) {
-    ubx = 0.5*(bx1f[ix4(g.N3, g.N2, g.N1 + 1, m, k, j, i)] +
-               bx1f[ix4(g.N3, g.N2, g.N1 + 1, m, k, j, i + 1)]);
-    uby = 0.5*(bx2f[ix4(g.N3, g.N2 + 1, g.N1, m, k, j, i)] +
-               bx2f[ix4(g.N3, g.N2 + 1, g.N1, m, k, j + 1, i)]);
-    ubz = 0.5*(bx3f[ix4(g.N3 + 1, g.N2, g.N1, m, k, j, i)] +
-               bx3f[ix4(g.N3 + 1, g.N2, g.N1, m, k + 1, j, i)]);
-    const size_t b = ix5(3, g.N3, g.N2, g.N1, m, 0, k, j, i);
-    bcc0[b] = ubx; bcc0[b + cs] = uby; bcc0[b + 2*cs] = ubz;
-  }
-  if (!eos.is_ideal) {
-    // SingleC2P_IsothermalHyd / _IsothermalMHD (isothermal_hyd.cpp:30-45, isothermal_mhd.cpp:32-47,
-    // density floor fmax(dfloor, b^2/sigma_max) :104-106): no energy variable (g.nvar == 4)
-    double ud = u0[c];
-    double dfloor_ = eos.dfloor;
-    if constexpr (MHD) dfloor_ = fmax(eos.dfloor, (sqr(ubx) + sqr(uby) + sqr(ubz))/eos.sigma_max);
-    if (ud < dfloor_) { ud = dfloor_; u0[c] = ud; atomicAdd(&counters[0], 1); }
-    const double di = 1.0/ud;
-    w0[c] = ud; w0[c + cs] = di*u0[c + cs]; w0[c + 2*cs] = di*u0[c + 2*cs];
-    w0[c + 3*cs] = di*u0[c + 3*cs];
-    for (int n = 4; n < g.nvar; ++n) w0[c + n*cs] = u0[c + n*cs]/ud;   // isothermal_*.cpp: no floor
-    return;
-  }
-  double ud = u0[c], umx = u0[c + cs], umy = u0[c + 2*cs], umz = u0[c + 3*cs], ue = u0[c + 4*cs];
-  double wd, wvx, wvy, wvz, we;
-  bool dfl = false, efl = false, tfl = false;
-  if constexpr (MHD) {
-    c2p_mhd(eos, ud, umx, umy, umz, ue, ubx, uby, ubz, wd, wvx, wvy, wvz, we, dfl, efl, tfl);
-  } else {
-    c2p_hyd(eos, ud, umx, umy, umz, ue, wd, wvx, wvy, wvz, we, dfl, efl, tfl);
-  }
-  if (dfl) { u0[c] = ud; atomicAdd(&counters[0], 1); }
-  if (efl) { u0[c + 4*cs] = ue; atomicAdd(&counters[1], 1); }
-  if (tfl) { u0[c + 4*cs] = ue; atomicAdd(&counters[2], 1); }
-  w0[c] = wd; w0[c + cs] = wvx; w0[c + 2*cs] = wvy; w0[c + 3*cs] = wvz; w0[c + 4*cs] = we;
-  for (int n = 5; n < g.nvar; ++n) {        // scalars with their floor, ideal_hyd.cpp:94-101
-    double us = u0[c + n*cs];
-    if (us < 0.0) { us = 0.0; u0[c + n*cs] = 0.0; }
-    w0[c + n*cs] = us/ud;
-  }
-}
-
-// ---------------------------------------------------------------------------------------
-// NewTimeStep: hydro_newdt.cpp:73-119, mhd_newdt.cpp:76-150.  Three minima; positive
-// doubles order like their bit patterns, so the cross-workgroup reduction is one
-// 64-bit atomicMin per workgroup per direction after a wave-level DPP/shuffle min.
-__device__ __forceinline__ double wave_min(double v) {
-  for (int off = 32; off > 0; off >>= 1) v = fmin(v, __shfl_xor(v, off, 64));
-  return v;
-}
-__device__ __forceinline__ void block_min3_atomic(double a, double b, double c,
-                                                  double *__restrict__ dt3) {
-  __shared__ double sm[3][BY];
-  a = wave_min(a); b = wave_min(b); c = wave_min(c);
-  const int lane = threadIdx.x & 63, w = threadIdx.y;
-  if (lane == 0) { sm[0][w] = a; sm[1][w] = b; sm[2][w] = c; }
-  __syncthreads();
-  if (threadIdx.y == 0 && threadIdx.x < 3) {
-    double v = sm[threadIdx.x][0];
-    for (int q = 1; q < BY; ++q) v = fmin(v, sm[threadIdx.x][q]);
-    if (v < __hip_atomic_load(&dt3[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-      atomicMin(reinterpret_cast<unsigned long long *>(&dt3[threadIdx.x]),
-                (unsigned long long)__double_as_longlong(v));
-  }
-}
-
-template <bool MHD>
-__device__ __forceinline__ void cell_dt(const Geo &g, const Eos &eos, const double *__restrict__ w0,
-                                        const double *__restrict__ bcc0, int m, int k, int j,
-                                        int i, double &d1, double &d2, double &d3) {
-  const double gamma = eos.gamma;
-  const size_t cs = (size_t)g.N3*g.N2*g.N1;
-  const size_t c = ix5(g.nvar, g.N3, g.N2, g.N1, m, 0, k, j, i);
-  double wd = w0[c], vx = w0[c + cs], vy = w0[c + 2*cs], vz = w0[c + 3*cs];
-  double mv1, mv2, mv3;
-  if (!eos.is_ideal) {                     // hydro_newdt.cpp:109-111, mhd_newdt.cpp:137-144
-    if constexpr (MHD) {
-      const size_t b = ix5(3, g.N3, g.N2, g.N1, m, 0, k, j, i);
-      double bx = bcc0[b], by = bcc0[b + cs], bz = bcc0[b + 2*cs];
-      mv1 = fabs(vx) + fast_speed_iso(eos.iso_cs, wd, bx, by, bz);
-      mv2 = fabs(vy) + fast_speed_iso(eos.iso_cs, wd, by, bz, bx);
-      mv3 = fabs(vz) + fast_speed_iso(eos.iso_cs, wd, bz, bx, by);
-    } else {
-      mv1 = fabs(vx) + eos.iso_cs; mv2 = fabs(vy) + eos.iso_cs; mv3 = fabs(vz) + eos.iso_cs;
-    }
-    d1 = g.dx[3*m]/mv1; d2 = g.dx[3*m + 1]/mv2; d3 = g.dx[3*m + 2]/mv3;
-    return;
-  }
-  double pr = (gamma - 1.0)*w0[c + 4*cs];
-  if constexpr (MHD) {
-    const size_t b = ix5(3, g.N3, g.N2, g.N1, m, 0, k, j, i);
-    double bx = bcc0[b], by = bcc0[b + cs], bz = bcc0[b + 2*cs];
-    mv1 = fabs(vx) + fast_speed(gamma, wd, pr, bx, by, bz);
-    mv2 = fabs(vy) + fast_speed(gamma, wd, pr, by, bz, bx);
-    mv3 = fabs(vz) + fast_speed(gamma, wd, pr, bz, bx, by);
-  } else {
-    double cs_ = sqrt(gamma*pr/wd);
-    mv1 = fabs(vx) + cs_; mv2 = fabs(vy) + cs_; mv3 = fabs(vz) + cs_;
-  }
-  d1 = g.dx[3*m]/mv1; d2 = g.dx[3*m + 1]/mv2; d3 = g.dx[3*m + 2]/mv3;
-}
-
+// NewTimeStep: hydro_newdt.cpp:73-119, mhd_newdt.cpp:76-150.  The largest signal speed per direction over the wave and
+// the workgroup, then one division and one filtered atomicMin per workgroup and direction (cfl_from_max, akmi_c2p.hpp).
 template <bool MHD>
 __global__ void __launch_bounds__(BX*BY)
 k_newdt(Geo g, Eos eos, const double *__restrict__ w0, const double *__restrict__ bcc0,
         double *__restrict__ dt3) {
+  __shared__ double sm[3*BY];
   const Cell3 q = flat_cells(0, g.N1, g.is, g.ie, g.js, g.nx2, g.ks, g.nx3);
   const int i = q.i, j = q.j, k = q.k, m = q.m;
-  double d1 = (double)FLT_MAX, d2 = (double)FLT_MAX, d3 = (double)FLT_MAX;
-  if (q.in) cell_dt<MHD>(g, eos, w0, bcc0, m, k, j, i, d1, d2, d3);
-  block_min3_atomic(d1, d2, d3, dt3);
-}
-
-__global__ void k_init_dt(double *dt3) {
-  if (threadIdx.x < 3) dt3[threadIdx.x] = (double)FLT_MAX;
+  double mv1 = 0.0, mv2 = 0.0, mv3 = 0.0;
+  if (q.in) {
+    const size_t cs = (size_t)g.N3*g.N2*g.N1;
+    const size_t c = ix5(g.nvar, g.N3, g.N2, g.N1, m, 0, k, j, i);
+    double bx = 0.0, by = 0.0, bz = 0.0;
+    if constexpr (MHD) {
+      const size_t b = ix5(3, g.N3, g.N2, g.N1, m, 0, k, j, i);
+      bx = bcc0[b]; by = bcc0[b + cs]; bz = bcc0[b + 2*cs];
+    }
+    max_speeds<MHD>(eos, w0[c], w0[c + cs], w0[c + 2*cs], w0[c + 3*cs], eos.is_ideal ? w0[c + 4*cs] : 0.0, bx, by, bz,
+                    mv1, mv2, mv3);
+  }
+  cfl_from_max(mv1, mv2, mv3, g.dx + 3*m, dt3, sm, threadIdx.y*BX + threadIdx.x, BY);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -302,11 +201,6 @@ __global__ void k_init_dt(double *dt3) {
 // energies.  One cell per thread, wave reduction by shuffles, workgroup reduction through LDS,
 // one fp64 atomicAdd per workgroup and quantity (the reference's Kokkos reduction is not
 // order-deterministic either; values agree to round-off).
-AKMI_DEV double wave_sum(double v) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 template <bool MHD>
 __global__ void __launch_bounds__(BX*BY)
 k_history(Geo g, int ideal, const double *__restrict__ u0, const double *__restrict__ bx1f,
@@ -693,7 +587,27 @@ k_corner_e_3d(Geo g, EccAccess cc, const double *__restrict__ e3x1,
 }
 
 // ---------------------------------------------------------------------------------------
-// CT, mhd_ct.cpp:23-80: all three face components in one launch.
+// CT, mhd_ct.cpp:23-80: all three face components in one launch.  ct_x1f / _x2f / _x3f: the face value after the update,
+// from b = its weighted sum over the registers and the corner EMFs around the face (mhd_ct.cpp:45-77).
+AKMI_DEV double ct_x1f(const Geo &g, const DxDiv &d, double beta_dt, const double *__restrict__ e2,
+                       const double *__restrict__ e3, int m, int k, int j, int i, double b) {
+  b -= d.by2(beta_dt*(e3[ix4(g.N3, g.N2 + 1, g.N1 + 1, m, k, j + 1, i)] - e3[ix4(g.N3, g.N2 + 1, g.N1 + 1, m, k, j, i)]));
+  if (g.three_d) b += d.by3(beta_dt*(e2[ix4(g.N3 + 1, g.N2, g.N1 + 1, m, k + 1, j, i)] - e2[ix4(g.N3 + 1, g.N2, g.N1 + 1, m, k, j, i)]));
+  return b;
+}
+AKMI_DEV double ct_x2f(const Geo &g, const DxDiv &d, double beta_dt, const double *__restrict__ e1,
+                       const double *__restrict__ e3, int m, int k, int j, int i, double b) {
+  b += d.by1(beta_dt*(e3[ix4(g.N3, g.N2 + 1, g.N1 + 1, m, k, j, i + 1)] - e3[ix4(g.N3, g.N2 + 1, g.N1 + 1, m, k, j, i)]));
+  if (g.three_d) b -= d.by3(beta_dt*(e1[ix4(g.N3 + 1, g.N2 + 1, g.N1, m, k + 1, j, i)] - e1[ix4(g.N3 + 1, g.N2 + 1, g.N1, m, k, j, i)]));
+  return b;
+}
+AKMI_DEV double ct_x3f(const Geo &g, const DxDiv &d, double beta_dt, const double *__restrict__ e1,
+                       const double *__restrict__ e2, int m, int k, int j, int i, double b) {
+  b -= d.by1(beta_dt*(e2[ix4(g.N3 + 1, g.N2, g.N1 + 1, m, k, j, i + 1)] - e2[ix4(g.N3 + 1, g.N2, g.N1 + 1, m, k, j, i)]));
+  if (g.multi_d) b += d.by2(beta_dt*(e1[ix4(g.N3 + 1, g.N2 + 1, g.N1, m, k, j + 1, i)] - e1[ix4(g.N3 + 1, g.N2 + 1, g.N1, m, k, j, i)]));
+  return b;
+}
+
 __global__ void __launch_bounds__(BX*BY)
 k_ct(Geo g, double gam0, double gam1, double beta_dt, const double *__restrict__ e1,
      const double *__restrict__ e2, const double *__restrict__ e3, double *__restrict__ b0x1f,
@@ -702,38 +616,19 @@ k_ct(Geo g, double gam0, double gam1, double beta_dt, const double *__restrict__
   const Cell3 q = flat_cells(FLAT_K, g.N1 + 1, g.is, g.ie + 1, g.js, g.je - g.js + 2, g.ks, g.ke - g.ks + 2);
   const int i = q.i, j = q.j, k = q.k, m = q.m;
   if (!q.in) return;
-  const double dx1 = g.dx[3*m], dx2 = g.dx[3*m + 1], dx3 = g.dx[3*m + 2];
-#define E1(k, j, i) e1[ix4(g.N3 + 1, g.N2 + 1, g.N1, m, k, j, i)]
-#define E2(k, j, i) e2[ix4(g.N3 + 1, g.N2, g.N1 + 1, m, k, j, i)]
-#define E3(k, j, i) e3[ix4(g.N3, g.N2 + 1, g.N1 + 1, m, k, j, i)]
-  const bool p2 = is_pow2(dx1) && is_pow2(dx2) && is_pow2(dx3);      // x/dx as v_ldexp_f64, see k_rk_update
-  const int n1 = pow2_shift(dx1), n2 = pow2_shift(dx2), n3 = pow2_shift(dx3);
-#define DIVX(x, q) (p2 ? ldexp((x), n##q) : (x)/dx##q)
+  const DxDiv d(g, m);                                               // x/dx as v_ldexp_f64, see k_rk_update
   if (g.multi_d && j <= g.je && k <= g.ke) {
     size_t c = ix4(g.N3, g.N2, g.N1 + 1, m, k, j, i);
-    double b = gam0*b0x1f[c] + gam1*b1x1f[c];
-    b -= DIVX(beta_dt*(E3(k, j + 1, i) - E3(k, j, i)), 2);
-    if (g.three_d) b += DIVX(beta_dt*(E2(k + 1, j, i) - E2(k, j, i)), 3);
-    b0x1f[c] = b;
+    b0x1f[c] = ct_x1f(g, d, beta_dt, e2, e3, m, k, j, i, gam0*b0x1f[c] + gam1*b1x1f[c]);
   }
   if (i <= g.ie && k <= g.ke) {
     size_t c = ix4(g.N3, g.N2 + 1, g.N1, m, k, j, i);
-    double b = gam0*b0x2f[c] + gam1*b1x2f[c];
-    b += DIVX(beta_dt*(E3(k, j, i + 1) - E3(k, j, i)), 1);
-    if (g.three_d) b -= DIVX(beta_dt*(E1(k + 1, j, i) - E1(k, j, i)), 3);
-    b0x2f[c] = b;
+    b0x2f[c] = ct_x2f(g, d, beta_dt, e1, e3, m, k, j, i, gam0*b0x2f[c] + gam1*b1x2f[c]);
   }
   if (i <= g.ie && j <= g.je) {
     size_t c = ix4(g.N3 + 1, g.N2, g.N1, m, k, j, i);
-    double b = gam0*b0x3f[c] + gam1*b1x3f[c];
-    b -= DIVX(beta_dt*(E2(k, j, i + 1) - E2(k, j, i)), 1);
-    if (g.multi_d) b += DIVX(beta_dt*(E1(k, j + 1, i) - E1(k, j, i)), 2);
-    b0x3f[c] = b;
+    b0x3f[c] = ct_x3f(g, d, beta_dt, e1, e2, m, k, j, i, gam0*b0x3f[c] + gam1*b1x3f[c]);
   }
-#undef DIVX
-#undef E1
-#undef E2
-#undef E3
 }
 
 // CT of the first stage out of place (see k_rk_update_oop): every face of the three arrays is written to the second
@@ -746,49 +641,27 @@ k_ct_oop(Geo g, double gam0, double gam1, double beta_dt, const double *__restri
   const Cell3 q = flat_cells(FLAT_K, g.N1 + 1, 0, g.N1, 0, g.N2 + 1, 0, g.N3 + 1);      // every face index of the three arrays
   const int i = q.i, j = q.j, k = q.k, m = q.m;
   if (!q.in) return;
-  const double dx1 = g.dx[3*m], dx2 = g.dx[3*m + 1], dx3 = g.dx[3*m + 2];
-#define E1(k, j, i) e1[ix4(g.N3 + 1, g.N2 + 1, g.N1, m, k, j, i)]
-#define E2(k, j, i) e2[ix4(g.N3 + 1, g.N2, g.N1 + 1, m, k, j, i)]
-#define E3(k, j, i) e3[ix4(g.N3, g.N2 + 1, g.N1 + 1, m, k, j, i)]
-  const bool p2 = is_pow2(dx1) && is_pow2(dx2) && is_pow2(dx3);
-  const int n1 = pow2_shift(dx1), n2 = pow2_shift(dx2), n3 = pow2_shift(dx3);
-#define DIVX(x, q) (p2 ? ldexp((x), n##q) : (x)/dx##q)
+  const DxDiv d(g, m);
   // the ranges of k_ct: i in [is, ie+1], j in [js, je+1], k in [ks, ke+1], then per component
   const bool in = i >= g.is && i <= g.ie + 1 && j >= g.js && j <= g.je + 1 && k >= g.ks && k <= g.ke + 1;
   if (k < g.N3 && j < g.N2) {                                        // x1f (N3, N2, N1+1)
     const size_t c = ix4(g.N3, g.N2, g.N1 + 1, m, k, j, i);
     double b = sx1f[c];
-    if (in && g.multi_d && j <= g.je && k <= g.ke) {
-      b = gam0*b + gam1*b;
-      b -= DIVX(beta_dt*(E3(k, j + 1, i) - E3(k, j, i)), 2);
-      if (g.three_d) b += DIVX(beta_dt*(E2(k + 1, j, i) - E2(k, j, i)), 3);
-    }
+    if (in && g.multi_d && j <= g.je && k <= g.ke) b = ct_x1f(g, d, beta_dt, e2, e3, m, k, j, i, gam0*b + gam1*b);
     dx1f[c] = b;
   }
   if (k < g.N3 && i < g.N1) {                                        // x2f (N3, N2+1, N1)
     const size_t c = ix4(g.N3, g.N2 + 1, g.N1, m, k, j, i);
     double b = sx2f[c];
-    if (in && i <= g.ie && k <= g.ke) {
-      b = gam0*b + gam1*b;
-      b += DIVX(beta_dt*(E3(k, j, i + 1) - E3(k, j, i)), 1);
-      if (g.three_d) b -= DIVX(beta_dt*(E1(k + 1, j, i) - E1(k, j, i)), 3);
-    }
+    if (in && i <= g.ie && k <= g.ke) b = ct_x2f(g, d, beta_dt, e1, e3, m, k, j, i, gam0*b + gam1*b);
     dx2f[c] = b;
   }
   if (j < g.N2 && i < g.N1) {                                        // x3f (N3+1, N2, N1)
     const size_t c = ix4(g.N3 + 1, g.N2, g.N1, m, k, j, i);
     double b = sx3f[c];
-    if (in && i <= g.ie && j <= g.je) {
-      b = gam0*b + gam1*b;
-      b -= DIVX(beta_dt*(E2(k, j, i + 1) - E2(k, j, i)), 1);
-      if (g.multi_d) b += DIVX(beta_dt*(E1(k, j + 1, i) - E1(k, j, i)), 2);
-    }
+    if (in && i <= g.ie && j <= g.je) b = ct_x3f(g, d, beta_dt, e1, e2, m, k, j, i, gam0*b + gam1*b);
     dx3f[c] = b;
   }
-#undef DIVX
-#undef E1
-#undef E2
-#undef E3
 }
 
 // Hydro::FOFC part 1 (hydro_fofc.cpp:46-85): trial update + floor test of one cell
@@ -904,9 +777,8 @@ k_fofc_flag_mhd(Geo g, Eos eos, double gam0, double gam1, double beta_dt, FofcMh
     ut[n] = gam0*a.u0[c] + gam1*a.u1[c] - divf;
   }
   // trial cell-centred field, mhd_fofc.cpp:88-107
-  const double b1old = 0.5*(a.b1[0][ix4(N3, N2, N1 + 1, m, k, j, i)] + a.b1[0][ix4(N3, N2, N1 + 1, m, k, j, i + 1)]);
-  const double b2old = 0.5*(a.b1[1][ix4(N3, N2 + 1, N1, m, k, j, i)] + a.b1[1][ix4(N3, N2 + 1, N1, m, k, j + 1, i)]);
-  const double b3old = 0.5*(a.b1[2][ix4(N3 + 1, N2, N1, m, k, j, i)] + a.b1[2][ix4(N3 + 1, N2, N1, m, k + 1, j, i)]);
+  double b1old, b2old, b3old;
+  cell_bcc(g, a.b1[0], a.b1[1], a.b1[2], m, k, j, i, b1old, b2old, b3old);
   const size_t cs = (size_t)N3*N2*N1;
   const size_t bc = ix5(3, N3, N2, N1, m, 0, k, j, i);
   double bx = gam0*a.bcc0[bc] + gam1*b1old;
@@ -969,8 +841,8 @@ k_fofc_fix_mhd(Geo g, Eos eos, FofcMhd a, int il, int iu, int jl, int ju, int kl
 }
 
 // NewTimeStep of kinematic runs (hydro_newdt.cpp:55-72): dx/|v| per direction.  |v| may be 0: dx/0 =
-// inf never wins the min.  Reduced like k_newdt: the division is monotone, so min dx/|v| =
-// dx/max|v| ... only for positive max; keep the per-cell form, it is a cold path.
+// inf never wins the min.  The division is monotone, so min dx/|v| = dx/max|v| as in k_newdt ... only for a
+// positive max; keep the per-cell form, it is a cold path.
 __global__ void __launch_bounds__(BX*BY)
 k_kinematic_newdt(Geo g, const double *__restrict__ w0, double *__restrict__ dt3) {
   const int i = g.is + blockIdx.x*BX + threadIdx.x;
@@ -978,6 +850,7 @@ k_kinematic_newdt(Geo g, const double *__restrict__ w0, double *__restrict__ dt3
   const int nk = g.ke - g.ks + 1;
   const int m = blockIdx.z/nk;
   const int k = g.ks + (blockIdx.z - m*nk);
+  __shared__ double sm[3*BY];
   double d1 = DBL_MAX, d2 = DBL_MAX, d3 = DBL_MAX;
   if (i <= g.ie && j <= g.je) {
     const size_t cs = (size_t)g.N3*g.N2*g.N1;
@@ -986,7 +859,9 @@ k_kinematic_newdt(Geo g, const double *__restrict__ w0, double *__restrict__ dt3
     d2 = g.dx[3*m + 1]/fabs(w0[c + 2*cs]);
     d3 = g.dx[3*m + 2]/fabs(w0[c + 3*cs]);
   }
-  block_min3_atomic(d1, d2, d3, dt3);
+  const int tid = threadIdx.y*BX + threadIdx.x;
+  const double v = wg_reduce3<false>(d1, d2, d3, sm, tid, BY);
+  if (tid < 3) atomic_min_positive(&dt3[tid], v);
 }
 
 // Hydro::CopyCons for rk4 (hydro_tasks.cpp:134-148): u1 += delta*u0, active cells
@@ -1119,33 +994,10 @@ int akmi_rk_update_oop(const akmi_pack *p, double gam0, double gam1, double beta
   return AKMI_COMPLETE;
 }
 
-int akmi_hydro_c2p(const akmi_pack *p, double *u0, double *w0, int il, int iu, int jl, int ju,
-                   int kl, int ku, int *counters, void *stream) {
-  Geo g = make_geo(p);
-  int nk = ku - kl + 1;
-  dim3 grid = flat_cells_grid(0, g.N1, il, iu, ju - jl + 1, nk, g.nmb), block(BX, BY);
-  k_c2p<false><<<grid, block, 0, (hipStream_t)stream>>>(g, make_eos(p), u0, nullptr, nullptr,
-      nullptr, w0, nullptr, il, iu, jl, ju, kl, nk, counters);
-  AKMI_CHECK_LAUNCH("hydro_c2p");
-  return AKMI_COMPLETE;
-}
-
-int akmi_mhd_c2p(const akmi_pack *p, double *u0, const double *bx1f, const double *bx2f,
-                 const double *bx3f, double *w0, double *bcc0, int il, int iu, int jl, int ju,
-                 int kl, int ku, int *counters, void *stream) {
-  Geo g = make_geo(p);
-  int nk = ku - kl + 1;
-  dim3 grid = flat_cells_grid(0, g.N1, il, iu, ju - jl + 1, nk, g.nmb), block(BX, BY);
-  k_c2p<true><<<grid, block, 0, (hipStream_t)stream>>>(g, make_eos(p), u0, bx1f, bx2f, bx3f, w0,
-      bcc0, il, iu, jl, ju, kl, nk, counters);
-  AKMI_CHECK_LAUNCH("mhd_c2p");
-  return AKMI_COMPLETE;
-}
-
 int akmi_hydro_newdt(const akmi_pack *p, const double *w0, double *dt3, void *stream) {
   Geo g = make_geo(p);
   hipStream_t st = (hipStream_t)stream;
-  k_init_dt<<<1, 64, 0, st>>>(dt3);
+  fill_fltmax(dt3, 3, st);
   dim3 grid = flat_cells_grid(0, g.N1, g.is, g.ie, g.nx2, g.nx3, g.nmb), block(BX, BY);
   k_newdt<false><<<grid, block, 0, st>>>(g, make_eos(p), w0, nullptr, dt3);
   AKMI_CHECK_LAUNCH("hydro_newdt");
@@ -1155,7 +1007,7 @@ int akmi_hydro_newdt(const akmi_pack *p, const double *w0, double *dt3, void *st
 int akmi_kinematic_newdt(const akmi_pack *p, const double *w0, double *dt3, void *stream) {
   Geo g = make_geo(p);
   hipStream_t st = (hipStream_t)stream;
-  k_init_dt<<<1, 64, 0, st>>>(dt3);
+  fill_fltmax(dt3, 3, st);
   dim3 grid(cdiv(g.nx1, BX), cdiv(g.je - g.js + 1, BY), (g.ke - g.ks + 1)*g.nmb), block(BX, BY);
   k_kinematic_newdt<<<grid, block, 0, st>>>(g, w0, dt3);
   AKMI_CHECK_LAUNCH("kinematic_newdt");
@@ -1166,7 +1018,7 @@ int akmi_mhd_newdt(const akmi_pack *p, const double *w0, const double *bcc0, dou
                    void *stream) {
   Geo g = make_geo(p);
   hipStream_t st = (hipStream_t)stream;
-  k_init_dt<<<1, 64, 0, st>>>(dt3);
+  fill_fltmax(dt3, 3, st);
   dim3 grid = flat_cells_grid(0, g.N1, g.is, g.ie, g.nx2, g.nx3, g.nmb), block(BX, BY);
   k_newdt<true><<<grid, block, 0, st>>>(g, make_eos(p), w0, bcc0, dt3);
   AKMI_CHECK_LAUNCH("mhd_newdt");
