@@ -120,6 +120,8 @@ class Driver:
             ph.ClearSend(self, -1)
             ph.ClearRecv(self, -1)
             ph.RecvU(self, 0)
+            ph.SendU_Shr(self, 0)              # driver.cpp:597-600: the shear-periodic x1 faces at the start time
+            ph.RecvU_Shr(self, 0)
             ph.Prolongate(self, 0)
             ph.ApplyPhysicalBCs(self, 0)
             ph.ConToPrim(self, 0)

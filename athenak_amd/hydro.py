@@ -326,6 +326,12 @@ class Hydro(FluidBase):
                                "problems (llf, hlle, hllc, roe on this path)" % rs)
         self.rsolver_method = capi.RSOLVER[rs]
         self.nhydro = self.nfluid
+        # <shearing_box>, hydro.cpp:135-142: both objects exist iff the block does.  The fused stage kernel cannot place
+        # the source term and the orbital remap between the update and the exchange: the task-granular chain
+        self.psbox_u = self.porb_u = None
+        has_sbox = pin.DoesBlockExist("shearing_box")
+        if has_sbox:
+            self.fused = False
         n3, n2, n1 = ppack.pmesh.mb_indcs.ncells
         sh = (self.nmb, self.nvars, n3, n2, n1)
         z = lambda: torch.zeros(sh, dtype=torch.float64, device=device)
@@ -334,6 +340,14 @@ class Hydro(FluidBase):
         self.uflx = None if self.fused else FaceFld(self.nmb, self.nvars, n3, n2, n1, device, face_shaped=False)
         self.pbval_u = MeshBoundaryValues(ppack, bvals_kernels, device)
         self.pbval_u.set_pack(self.pack_c, self.nvars)
+        if has_sbox:
+            from .shearing_box import OrbitalAdvectionCC, ShearingBoxCC
+            self.psbox_u = ShearingBoxCC(ppack, pin, self.nvars, self)
+            self.porb_u = OrbitalAdvectionCC(ppack, pin, self.nvars, self)
+            if ppack.pmesh.shear_periodic:
+                # the shear remap of the x1 ghost slabs sits between the exchange and the boundary functions, as in
+                # the reference's list: the gather must not apply the boundary functions of the other faces itself
+                self.pbval_u.fold_bcs = False
         self.psmr = None
         if self.multilevel:
             from .bvals_smr import MeshBoundaryValuesSMR
@@ -374,12 +388,55 @@ class Hydro(FluidBase):
     def _noop(self, pdrive, stage):
         return TaskStatus.complete
 
-    InitRecv = SendU_OA = RecvU_OA = _noop
-    SendU_Shr = RecvU_Shr = ClearSend = ClearRecv = _noop
+    ClearSend = ClearRecv = _noop
+
+    def _sbox_3d(self):
+        """the shear tasks run `if (three_d || shearing_box_r_phi)`, and r-phi is never set (hydro_tasks.cpp:101-113)"""
+        return self.psbox_u is not None and self.pmy_pack.pmesh.three_d
+
+    def InitRecv(self, pdrive, stage):
+        """hydro_tasks.cpp:109-120: the distance the x1 boundaries have sheared at the time this stage ends; the call of
+        the driver's initialisation has stage = -1, hence the plain time"""
+        if self._sbox_3d():
+            pm = self.pmy_pack.pmesh
+            time = pm.time
+            if stage == pdrive.nexp_stages:
+                time += pm.dt
+            self.psbox_u.InitRecv(time)
+        return TaskStatus.complete
 
     def HydroSrcTerms(self, pdrive, stage):
-        """hydro_tasks.cpp:237-241: if (psrc != nullptr) psrc->ApplySrcTerms(w0, peos->eos_data, beta_dt, u0)"""
-        return self._srcterms(pdrive, stage)
+        """hydro_tasks.cpp:237-244: psrc->ApplySrcTerms(w0, eos_data, beta_dt, u0), then
+        psbox_u->SourceTermsCC(w0, eos_data, beta_dt, u0)"""
+        st = self._srcterms(pdrive, stage)
+        if self.psbox_u is not None:
+            self.psbox_u.SourceTermsCC(self.w0, pdrive.beta[stage - 1]*self.pmy_pack.pmesh.dt, self.u0)
+        return st
+
+    def SendU_OA(self, pdrive, stage):
+        """hydro_tasks.cpp:263-273: nothing to pack on one rank (the remap reads the neighbours' cells itself)"""
+        return TaskStatus.complete
+
+    def RecvU_OA(self, pdrive, stage):
+        """hydro_tasks.cpp:280-290: last stage, 3-D.  Out of place into u1: the second register is dead between the
+        last RKUpdate of a cycle and the CopyCons / out-of-place update of the next first stage, which write all of its
+        active cells; its ghost cells are filled by SendU / the boundary functions right after this task"""
+        if self._sbox_3d() and stage == pdrive.nexp_stages:
+            self.porb_u.RecvAndUnpackCC(self.u0, self.u1, self.recon_method)
+            self.u0, self.u1 = self.u1, self.u0
+        return TaskStatus.complete
+
+    def SendU_Shr(self, pdrive, stage):
+        """hydro_tasks.cpp:326-335"""
+        if self._sbox_3d():
+            self.psbox_u.PackAndSendCC(self.u0, self.recon_method)
+        return TaskStatus.complete
+
+    def RecvU_Shr(self, pdrive, stage):
+        """hydro_tasks.cpp:342-351"""
+        if self._sbox_3d():
+            self.psbox_u.RecvAndUnpackCC(self.u0)
+        return TaskStatus.complete
 
     def SendFlux(self, pdrive, stage):
         """hydro_tasks.cpp:206-215: restricted fluxes at fine/coarse boundaries (SMR only)"""

@@ -22,6 +22,9 @@ class Simulation:
         if restart is not None and pin.DoesBlockExist("gravity"):
             raise RuntimeError("### FATAL ERROR -r of a deck with <gravity>: restarting a self-gravitating run is not on "
                                "this path yet")
+        if restart is not None:
+            from .shearing_box import shearing_box_deck_checks
+            shearing_box_deck_checks(pin, nranks, restart=True)
         self.pmesh = Mesh(pin, my_rank, nranks)
         if restart is not None and self.pmesh.adaptive:
             raise RuntimeError("### FATAL ERROR -r of a deck with <mesh_refinement>/refinement = adaptive: the restart "
@@ -77,6 +80,16 @@ class Simulation:
         if pg is None:
             raise RuntimeError("### FATAL ERROR the gravitational potential needs a <gravity> block")
         return pg.phi
+
+    @property
+    def psbox_u(self):
+        """the ShearingBoxCC of the hydro fluid (qshear, omega0, yshear); None without a <shearing_box> block"""
+        return getattr(self.pmesh.pmb_pack.phydro, "psbox_u", None)
+
+    @property
+    def porb_u(self):
+        """the OrbitalAdvectionCC of the hydro fluid (maxjshift); None without a <shearing_box> block"""
+        return getattr(self.pmesh.pmb_pack.phydro, "porb_u", None)
 
     @property
     def omega_measured(self):

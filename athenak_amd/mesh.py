@@ -16,6 +16,12 @@ FLT_MAX = float(np.finfo(np.float32).max)
 FLT_MIN = float(np.finfo(np.float32).tiny)
 
 _BCNAMES = {k: capi.BC[k] for k in ("periodic", "outflow", "reflect", "user", "inflow", "diode", "vacuum")}
+# BoundaryFlag::shear_periodic (x1 faces of a shearing box).  A host-side flag: the ghost exchange treats such a face as
+# periodic (the neighbour tables wrap), no boundary function of the library knows the value, so ApplyPhysicalBCs leaves
+# the face alone (bvals/physics/hydro_bcs.cpp:79-81); shearing_box.py remaps the slab afterwards.
+SHEAR_PERIODIC = 7
+_BCNAMES["shear_periodic"] = SHEAR_PERIODIC
+_WRAPS = (capi.BC["periodic"], SHEAR_PERIODIC)
 
 
 def LeftEdgeX(ith, n, xmin, xmax):
@@ -173,12 +179,12 @@ class MeshBlock:
                 for q in range(3):
                     l[q] = lloc[q] + o[q]
                     if l[q] < 0:
-                        if pm.mesh_bcs[2*q] == capi.BC["periodic"]:
+                        if pm.mesh_bcs[2*q] in _WRAPS:
                             l[q] += nb[q]
                         else:
                             ok = False
                     elif l[q] >= nb[q]:
-                        if pm.mesh_bcs[2*q + 1] == capi.BC["periodic"]:
+                        if pm.mesh_bcs[2*q + 1] in _WRAPS:
                             l[q] -= nb[q]
                         else:
                             ok = False
@@ -281,6 +287,10 @@ class Mesh:
     def __init__(self, pin, my_rank=0, nranks=1):
         self.my_rank, self.nranks = my_rank, nranks
         self.pin = pin
+        # what a deck with <shearing_box> may not ask for is whole blocks (<mhd>, <mesh_refinement>, ...): said before
+        # the tree is built and before those blocks' own checks speak of their parameters
+        from .shearing_box import shearing_box_deck_checks
+        shearing_box_deck_checks(pin, nranks)
         g = pin.GetReal
         self.mesh_size = RegionSize(g("mesh", "x1min"), g("mesh", "x1max"), g("mesh", "x2min"),
                                     g("mesh", "x2max"), g("mesh", "x3min"), g("mesh", "x3max"))
@@ -302,9 +312,24 @@ class Mesh:
             v = pin.GetOrAddString("mesh", name, "periodic")
             if v not in _BCNAMES:
                 raise RuntimeError("### FATAL ERROR boundary flag '%s' not supported on this "
-                                   "path (periodic/outflow/reflect/inflow/diode/vacuum/user)" % v)
+                                   "path (periodic/outflow/reflect/inflow/diode/vacuum/user/shear_periodic)" % v)
             bcs.append(_BCNAMES[v])
         self.mesh_bcs = bcs
+        # mesh.cpp:95-117, :133-139, :160-166: shear-periodic faces come in pairs, on x1 only, with a <shearing_box>
+        shr = [b == SHEAR_PERIODIC for b in bcs]
+        if shr[0] and shr[1]:
+            if self.one_d:
+                raise RuntimeError("### FATAL ERROR Shear Periodic Boundaries require 2D or 3D")
+            if not pin.DoesBlockExist("shearing_box"):
+                raise RuntimeError("### FATAL ERROR Shear Periodic Boundaries set but no <shearing_box> block in "
+                                   "input file")
+        elif shr[0] or shr[1]:
+            raise RuntimeError("### FATAL ERROR In shearing box, both x1 bcs must be shear_periodic")
+        if self.multi_d and (shr[2] or shr[3]):
+            raise RuntimeError("### FATAL ERROR Shear Periodic Boundaries cannot be applied in x2")
+        if self.three_d and (shr[4] or shr[5]):
+            raise RuntimeError("### FATAL ERROR Shear Periodic Boundaries cannot be applied in x3")
+        self.shear_periodic = shr[0] and shr[1]
         per = capi.BC["periodic"]
         self.strictly_periodic = (bcs[0] == per and bcs[1] == per and
                                   (not self.multi_d or (bcs[2] == per and bcs[3] == per)) and

@@ -48,6 +48,8 @@ class NativeSimulation:
         if pin.DoesBlockExist("gravity"):
             raise RuntimeError("### FATAL ERROR <gravity> runs on the Python host only (--host python): the C++ host "
                                "(--host native) has no multigrid driver")
+        from .shearing_box import shearing_box_native_refusal
+        shearing_box_native_refusal(pin)
         self.L = capi.lib()
         stream = capi._stream()
         h = self.L.akmi_sim_create(pin.Dump().encode(), stream)

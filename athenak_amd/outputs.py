@@ -393,7 +393,11 @@ class HistoryOutput(BaseTypeOutput):
         import torch
         pk = pm.pmb_pack
         if self.user_hist:
-            self.udata = turb_history_sums(pk.pmhd, pk)
+            enrolled = getattr(pm.pgen, "user_hist_func", None)      # ShwaveHistory (pgen_name = shwave, ipert = 3)
+            if enrolled is not None:
+                self.ulabels, self.udata = enrolled(pm)
+            else:
+                self.ulabels, self.udata = capi.TURB_HIST_LABELS, turb_history_sums(pk.pmhd, pk)
         if not self.physics_hist:
             return
         phys = pk.pmhd if self.is_mhd else pk.phydro
@@ -432,7 +436,7 @@ class HistoryOutput(BaseTypeOutput):
                                                         nt["hdata"].cpu().numpy(), nt["header_written"])
         if self.user_hist and pm.my_rank == 0:
             # the sums are already those of the whole mesh on every rank (turb_history_sums)
-            self.user_header_written = self._append("%s.user.hst" % op.file_basename, pm, capi.TURB_HIST_LABELS,
+            self.user_header_written = self._append("%s.user.hst" % op.file_basename, pm, self.ulabels,
                                                     self.udata, self.user_header_written)
         self._advance(pm, pin, numbered=False)
 
@@ -457,10 +461,16 @@ class HistoryOutput(BaseTypeOutput):
 
 def user_hist_of(pin):
     """<problem>/user_hist (pgen.cpp:49; default false, read without adding it to the deck) and what this path enrols for it:
-    TurbulentHistory of pgen_name = turb on an MHD run (turb.cpp:42)"""
+    TurbulentHistory of pgen_name = turb on an MHD run (turb.cpp:42), ShwaveHistory of pgen_name = shwave with ipert = 3"""
     if not (pin.DoesParameterExist("problem", "user_hist") and pin.GetBoolean("problem", "user_hist")):
         return False
     name = pin.GetString("problem", "pgen_name") if pin.DoesParameterExist("problem", "pgen_name") else "none"
+    if name == "shwave":
+        # shwave.cpp:144: ShwaveHistory is enrolled for the compressible hydro wave only
+        if pin.DoesBlockExist("hydro") and pin.GetInteger("problem", "ipert") == 3:
+            return True
+        _fatal("<problem>/user_hist = true with pgen_name = shwave: the user history function (dVyc) is enrolled for "
+               "ipert = 3 of a hydro run only")
     if name != "turb":
         # pgen.cpp:86-92 exits with "user history function not enrolled"; the other generators' functions are not on this path
         _fatal("<problem>/user_hist = true, but the user history function of pgen_name = '%s' is not enrolled on this "

@@ -199,7 +199,8 @@ class ProblemGenerator:
         table = {"linear_wave": self.LinearWave, "shock_tube": self.ShockTube,
                  "orszag_tang": self.OrszagTang, "blast": self.UserProblem, "diffusion": self.Diffusion,
                  "cpaw": self.AlfvenWave, "turb": self.Turb, "rt": self.RayleighTaylor, "cshock": self.CShock,
-                 "gravity": self.SelfGravity}
+                 "gravity": self.SelfGravity, "shwave": self.Shwave}
+        self.user_hist_func = None       # (labels, sums) of the user history file; enrolled by the problem function
         # user-defined boundary conditions (pgen.cpp:57-62): enrolled by the problem function
         self.user_bcs = any(b == capi.BC["user"] for b in pmesh.mesh_bcs)
         self.user_bcs_func = None
@@ -1325,3 +1326,72 @@ class ProblemGenerator:
                 bf[0][m][ks, js, is_.start:is_.stop + 1] = np.broadcast_to(b1, (nk, nj, ni + 1))
                 bf[1][m][ks, js.start:js.stop + 1, is_] = -(0.0)/sz.dx1
         self._store(w, bf)
+
+    # ---- shearing waves, src/pgen/tests/shwave.cpp:59-168 (hydro), :346-428 ---------------
+    def Shwave(self, pin, restart):
+        """pgen_name = shwave: ipert = 1 epicyclic oscillation, 2 incompressible and 3 compressible shearing wave of
+        Johnson & Gammie (2005).  The MHD perturbations (ipert = 4) belong to the face-centred half of the shearing box,
+        which is not on this path."""
+        if restart:
+            return
+        pm = self.pmy_mesh_
+        pk = pm.pmb_pack
+        d0 = pin.GetReal("problem", "d0")
+        p0 = pin.GetOrAddReal("problem", "p0", 1.0)
+        amp = pin.GetReal("problem", "amp")
+        ipert = pin.GetInteger("problem", "ipert")
+        ms = pm.mesh_size
+        Lx, Ly, Lz = ms.x1max - ms.x1min, ms.x2max - ms.x2min, ms.x3max - ms.x3min
+        kx = (2.0*math.pi/Lx)*float(pin.GetInteger("problem", "nwx"))
+        ky = (2.0*math.pi/Ly)*float(pin.GetInteger("problem", "nwy"))
+        kz = (2.0*math.pi/Lz)*float(pin.GetInteger("problem", "nwz"))
+        if pk.phydro is None or getattr(pk.phydro, "psbox_u", None) is None:
+            raise RuntimeError("### FATAL ERROR shwave problem generator only works in shearing box.\nLikely missing "
+                               "<shearing_box> block in input file")
+        if ipert < 1 or ipert > 3:
+            raise RuntimeError("### FATAL ERROR ipert must be 1,2, or 3 for hydro shwaves")
+        phys = pk.phydro
+        self._shw = dict(kx=kx, ky=ky, kz=kz, qshear=phys.psbox_u.qshear, omega0=phys.psbox_u.omega0)
+        if ipert == 3:
+            self.user_hist_func = self.ShwaveHistory       # shwave.cpp:144
+        ideal = phys.peos.eos_data.is_ideal
+        gm1 = phys.peos.eos_data.gamma - 1.0
+        w, _ = self._alloc_host()
+        ks, js, is_ = self._active()
+        for m in range(pk.nmb_thispack):
+            x1v, x2v, x3v = self._coords(m)[:3]
+            X3, X2, X1 = np.meshgrid(x3v, x2v, x1v, indexing="ij")
+            if ipert == 1:
+                rvx, rvy = np.full_like(X1, amp), np.zeros_like(X1)
+            elif ipert == 2:
+                rvx = amp*np.sin(kx*X1 + ky*X2)
+                rvy = -amp*(kx/ky)*np.sin(kx*X1 + ky*X2)
+            else:
+                rvx = -(amp*np.cos(kx*X1 + ky*X2))
+                rvy = -(amp*(ky/kx)*np.cos(kx*X1 + ky*X2))
+            # the reference sets u0 = (d0, d0*rvx, d0*rvy, 0, p0/gm1 + 0.5*d0*(rvx^2 + rvy^2)): the same products
+            # and sums as the conversion of these primitives in _store
+            w[m, IDN][ks, js, is_] = d0
+            w[m, 1][ks, js, is_] = rvx
+            w[m, 2][ks, js, is_] = rvy
+            if ideal:
+                w[m, IEN][ks, js, is_] = p0/gm1
+        self._store(w, None)
+
+    def ShwaveHistory(self, pm):
+        """shwave.cpp:346-428: (labels, sums) of the user history file of the compressible shearing wave,
+        dVyc = sum of vol*2*vy*cos(kx(t) x + ky y) with kx(t) = kx + qshear*omega0*t*ky.  A diagnostic written at the
+        cadence of the history file: summed on the host from the primitive velocity."""
+        sv = self._shw
+        pk = pm.pmb_pack
+        kx = sv["kx"] + sv["qshear"]*sv["omega0"]*pm.time*sv["ky"]
+        ks, js, is_ = self._active()
+        vy = pk.phydro.w0[:, 2].cpu().numpy()
+        total = 0.0
+        for m in range(pk.nmb_thispack):
+            x1v, x2v, _ = self._coords(m)[:3]
+            sz = pk.pmb.mb_size[m]
+            vol = sz.dx1*sz.dx2*sz.dx3
+            X2, X1 = np.meshgrid(x2v, x1v, indexing="ij")
+            total += float(np.sum(vol*2.0*vy[m][ks, js, is_]*np.cos(kx*X1 + sv["ky"]*X2)))
+        return ["dVyc"], np.array([total])

@@ -1087,6 +1087,38 @@ int akmi_mg_solve(const akmi_mg_plan *plan, const double *u0, double *phi, int *
 /* kernel launches this unit has enqueued since the last reset */
 long long akmi_mg_launch_count(int reset);
 
+/* ---- shearing box, cell-centred half (src/shearing_box/) ------------------------------------------------- *
+ * csrc/akmi_sbox.hip.  Hydro only; every entry reproduces the reference's roundings in the written order.
+ * xlim = device double[nmb][6]: x1min, x1max, x2min, x2max, x3min, x3max of every MeshBlock (mb_size).
+ *
+ * ShearingBoxCC::SourceTermsCC (shearing_box_srcterms.cpp:27-84) on the active cells: the 3-D branch when nx3 > 1, the
+ * 2-D r-z branch otherwise; old primitives w0 in, u0 read-modify-written.  The host forms
+ *   coef1 = 2.0*bdt*omega0,  coef2 = (2.0-qshear)*bdt*omega0,  coef3 = bdt*SQR(omega0),  qo = qshear*omega0
+ * as the reference writes them.  stratified (3-D only) reads the x3 bounds of xlim (may be NULL otherwise). */
+int akmi_sbox_srcterms(const akmi_pack *p, double coef1, double coef2, double coef3, double bdt, double qo, int stratified,
+                       const double *xlim, const double *w0, double *u0, void *stream);
+/* The shear-periodic x1 boundary of cell-centred variables, ShearingBoxCC::PackAndSendCC / RecvAndUnpackCC
+ * (shearing_box_cc.cpp:48-266, :281-391) on one rank, both faces per launch.
+ * tab = device int[2][nslot][tab_stride], tab_stride = 2 + nmbx2, per face (0 inner, 1 outer) and boundary MeshBlock:
+ *   {local index of the MeshBlock, its lx2, slot of the MeshBlock at lx2 = 0, 1, .., nmbx2-1 on this face and this lx3};
+ * nb_in / nb_out of the nslot slots of a face are used.  buf = device double[2][nslot][nvar][N3][nx2][ng].
+ * remap_x1: buf(j) = a(j) - (flx(j+1) - flx(j)) for j in [js, je], all k (ghost planes included), of the x1 ghost slab,
+ * eps = fmod(yshear, dx2)/dx2, negated on the outer face; the remap flux by recon: dc, plm, anything else PPMX.
+ * shift_x1: every x1 ghost cell, all rows j of the MeshBlock, takes buf at global row g - joffset (inner face) /
+ * g + joffset (outer face) modulo nmbx2*nx2, g = lx2*nx2 + (j - js); joffset = int(yshear/dx2) >= 0. */
+int akmi_sbox_remap_x1(const akmi_pack *p, int recon, int nb_in, int nb_out, int nslot, const int *tab, int tab_stride,
+                       double yshear, const double *u0, double *buf, void *stream);
+int akmi_sbox_shift_x1(const akmi_pack *p, int nb_in, int nb_out, int nslot, const int *tab, int tab_stride, int nmbx2,
+                       int joffset, const double *buf, double *u0, void *stream);
+/* OrbitalAdvectionCC::RecvAndUnpackCC (orbital_advection_cc.cpp:215-288) on one rank: the active cells of `out` are u0
+ * remapped along x2 by yshear = -qo*x1v*dt of their column (integer shift + conservative remap of the rest); u0 is
+ * only read, the ghost cells of `out` are not written.  Rows beyond an x2 edge are the active rows of the x2 neighbour
+ * of nghbr (device int[nmb][27], local indices; a MeshBlock may be its own neighbour).  The caller guarantees
+ * nghost + maxjshift <= nx2 (checked) and |int(yshear/dx2)| <= maxjshift for every column (indices are clamped into
+ * the arrays if it does not hold; the result is then wrong). */
+int akmi_sbox_orbital_cc(const akmi_pack *p, int recon, int maxjshift, double qo, double dt, const int *nghbr,
+                         const double *xlim, const double *u0, double *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
