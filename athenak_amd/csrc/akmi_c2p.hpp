@@ -185,6 +185,20 @@ AKMI_DEV void c2p_commit(const Geo &g, const Eos &eos, double *__restrict__ u0, 
   }
 }
 
+// The other way for the cell at c: SingleP2C_IdealHyd / _IdealMHD (src/eos/ideal_c2p_hyd.hpp:76-83,
+// ideal_c2p_mhd.hpp:75-84; mhd: (bx, by, bz) is the cell-centred field) and, without an energy variable, their
+// isothermal forms with the passive scalars from variable 4.
+AKMI_DEV void p2c_at(int nvar, bool is_ideal, bool mhd, const double *__restrict__ w, double *__restrict__ u, size_t c,
+                     size_t cs, double bx, double by, double bz) {
+  const double d = w[c], vx = w[c + cs], vy = w[c + 2*cs], vz = w[c + 3*cs];
+  u[c] = d; u[c + cs] = d*vx; u[c + 2*cs] = d*vy; u[c + 3*cs] = d*vz;
+  if (is_ideal) {
+    if (mhd) u[c + 4*cs] = w[c + 4*cs] + 0.5*(d*(sqr(vx) + sqr(vy) + sqr(vz)) + (sqr(bx) + sqr(by) + sqr(bz)));
+    else u[c + 4*cs] = w[c + 4*cs] + 0.5*d*(sqr(vx) + sqr(vy) + sqr(vz));
+  }
+  for (int n = is_ideal ? 5 : 4; n < nvar; ++n) u[c + n*cs] = d*w[c + n*cs];
+}
+
 // x[0..n) = FLT_MAX, n <= 64: where a running minimum starts (akmi_stage_c2p.hip)
 void fill_fltmax(double *x, int n, hipStream_t st);
 

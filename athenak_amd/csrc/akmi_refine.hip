@@ -1,11 +1,12 @@
 // akmi_refine.hip -- the operators between a MeshBlock and its coarse buffer that SMR/AMR boundary
 // exchange is made of: restriction of cell- and face-centred data, slope-limited
 // prolongation of cell-centred data, and the divergence-preserving prolongation of the face field
-// (shared faces first, then the Toth & Roe interior).  The mesh tree, the level-aware neighbour
-// tables and the flux/EMF correction that call them in the reference are not built yet; the
+// (shared faces first, then the Toth & Roe interior).  The level-aware boundary exchange and the flux/EMF
+// correction of a refined mesh are akmi_smr.hip, the regrid of an adaptive one akmi_amr.hip; here the
 // operators are exposed through the C ABI over caller-given index boxes, which is how
 // src/bvals/prolongation.cpp drives them (iprol boxes of the receive buffers).
 #include "akmi_common.hpp"
+#include "akmi_c2p.hpp"
 #include "akmi_refine_ops.hpp"
 
 namespace akmi {
@@ -138,24 +139,13 @@ __global__ void k_restrict_flux_cc(Geo g, CGeo c, Box bx, int nvar, const double
   if (!box_index(bx, nvar, m, v, k, j, i)) return;
   const int ni = bx.iu - bx.il + 1, nj = bx.ju - bx.jl + 1, nk = bx.ku - bx.kl + 1;
   const int f3 = g.N3 + (DIR == 2), f2 = g.N2 + (DIR == 1), f1 = g.N1 + (DIR == 0);
-  const int fi = 2*i - c.cis, fj = 2*j - c.cjs, fk = 2*k - c.cks;
-#define FX(k, j, i) flx[ix5(nvar, f3, f2, f1, m, v, k, j, i)]
-  double r;
+  const int fi = 2*i - c.cis, fj = g.multi_d ? 2*j - c.cjs : 0, fk = g.three_d ? 2*k - c.cks : 0;
+  auto FX = [&](int kk, int jj, int ii) { return flx[ix5(nvar, f3, f2, f1, m, v, kk, jj, ii)]; };
+  const double r = restrict_fc_face<DIR>(g.multi_d, g.three_d, FX, fk, fj, fi);
   size_t o;
-  if constexpr (DIR == 0) {
-    if (!g.multi_d) r = FX(0, 0, fi);
-    else if (!g.three_d) r = 0.5*(FX(0, fj, fi) + FX(0, fj + 1, fi));
-    else r = 0.25*(FX(fk, fj, fi) + FX(fk, fj + 1, fi) + FX(fk + 1, fj, fi) + FX(fk + 1, fj + 1, fi));
-    o = (size_t)(j - bx.jl) + (size_t)nj*((k - bx.kl) + (size_t)nk*v);
-  } else if constexpr (DIR == 1) {
-    if (!g.three_d) r = 0.5*(FX(0, fj, fi) + FX(0, fj, fi + 1));
-    else r = 0.25*(FX(fk, fj, fi) + FX(fk, fj, fi + 1) + FX(fk + 1, fj, fi) + FX(fk + 1, fj, fi + 1));
-    o = (size_t)(i - bx.il) + (size_t)ni*((k - bx.kl) + (size_t)nk*v);
-  } else {
-    r = 0.25*(FX(fk, fj, fi) + FX(fk, fj, fi + 1) + FX(fk, fj + 1, fi) + FX(fk, fj + 1, fi + 1));
-    o = (size_t)(i - bx.il) + (size_t)ni*((j - bx.jl) + (size_t)nj*v);
-  }
-#undef FX
+  if constexpr (DIR == 0) o = (size_t)(j - bx.jl) + (size_t)nj*((k - bx.kl) + (size_t)nk*v);
+  else if constexpr (DIR == 1) o = (size_t)(i - bx.il) + (size_t)ni*((k - bx.kl) + (size_t)nk*v);
+  else o = (size_t)(i - bx.il) + (size_t)ni*((j - bx.jl) + (size_t)nj*v);
   out[(size_t)m*nvar*ni*nj*nk + o] = r;
 }
 
@@ -169,12 +159,8 @@ __global__ void k_restrict_emf(Geo g, CGeo c, Box bx, const double *__restrict__
   const int ni = bx.iu - bx.il + 1, nj = bx.ju - bx.jl + 1, nk = bx.ku - bx.kl + 1;
   const int e3 = g.N3 + (COMP != 2), e2 = g.N2 + (COMP != 1), e1 = g.N1 + (COMP != 0);
   const int fi = 2*i - c.cis, fj = g.multi_d ? 2*j - c.cjs : 0, fk = g.three_d ? 2*k - c.cks : 0;
-#define EE(k, j, i) e[ix4(e3, e2, e1, m, k, j, i)]
-  double r;
-  if constexpr (COMP == 0) r = g.multi_d ? 0.5*(EE(fk, fj, fi) + EE(fk, fj, fi + 1)) : EE(fk, fj, fi);
-  else if constexpr (COMP == 1) r = g.multi_d ? 0.5*(EE(fk, fj, fi) + EE(fk, fj + 1, fi)) : EE(fk, fj, fi);
-  else r = g.three_d ? 0.5*(EE(fk, fj, fi) + EE(fk + 1, fj, fi)) : EE(fk, fj, fi);
-#undef EE
+  auto EE = [&](int kk, int jj, int ii) { return e[ix4(e3, e2, e1, m, kk, jj, ii)]; };
+  const double r = restrict_edge<COMP>(g.multi_d, g.three_d, EE, fk, fj, fi);
   out[(size_t)m*ni*nj*nk + (size_t)(i - bx.il) + (size_t)ni*((j - bx.jl) + (size_t)nj*(k - bx.kl))] = r;
 }
 
@@ -197,18 +183,12 @@ __global__ void k_prim2cons(Geo g, Box bx, int is_ideal, const double *__restric
   if (!box_index(bx, 1, m, v, k, j, i)) return;
   const size_t cs = (size_t)g.N3*g.N2*g.N1;
   const size_t c = ix5(g.nvar, g.N3, g.N2, g.N1, m, 0, k, j, i);
-  const double d = w[c], vx = w[c + cs], vy = w[c + 2*cs], vz = w[c + 3*cs];
-  u[c] = d; u[c + cs] = d*vx; u[c + 2*cs] = d*vy; u[c + 3*cs] = d*vz;
-  if (is_ideal) {
-    if (bcc) {
-      const size_t b = ix5(3, g.N3, g.N2, g.N1, m, 0, k, j, i);
-      const double bx_ = bcc[b], by = bcc[b + cs], bz = bcc[b + 2*cs];
-      u[c + 4*cs] = w[c + 4*cs] + 0.5*(d*(vx*vx + vy*vy + vz*vz) + (bx_*bx_ + by*by + bz*bz));
-    } else {
-      u[c + 4*cs] = w[c + 4*cs] + 0.5*d*(vx*vx + vy*vy + vz*vz);
-    }
+  double bx_ = 0.0, by = 0.0, bz = 0.0;
+  if (is_ideal && bcc) {
+    const size_t b = ix5(3, g.N3, g.N2, g.N1, m, 0, k, j, i);
+    bx_ = bcc[b]; by = bcc[b + cs]; bz = bcc[b + 2*cs];
   }
-  for (int n = is_ideal ? 5 : 4; n < g.nvar; ++n) u[c + n*cs] = d*w[c + n*cs];
+  p2c_at(g.nvar, is_ideal, bcc != nullptr, w, u, c, cs, bx_, by, bz);
 }
 
 extern "C" {

@@ -1,7 +1,8 @@
 // akmi_refine_ops.hpp -- the per-cell restriction and prolongation operators, written once over accessors so
 // that the boundary exchange of a refined mesh (akmi_refine.hip, akmi_smr.hip: a block and its own coarse buffer)
 // and the regrid of an adaptive mesh (akmi_amr.hip: a new block and the old blocks it comes from) apply the same
-// arithmetic in the same order.  An accessor is a callable (k, j, i) -> value (or reference, where written).
+// arithmetic in the same order.  An accessor is a callable (k, j, i) -> value (or, where written, a reference or an
+// object assignable from a double that converts to one: akmi_smr.hip's owned faces).
 #ifndef AKMI_REFINE_OPS_HPP_
 #define AKMI_REFINE_OPS_HPP_
 #include "akmi_common.hpp"
@@ -69,6 +70,17 @@ __device__ __forceinline__ double restrict_fc_face(int multi_d, int three_d, B &
   }
 }
 
+// A restricted face flux of direction DIR (PackAndSendFluxCC, src/bvals/flux_correct_cc.cpp:78-148) is
+// restrict_fc_face<DIR> of the flux array.  The restricted edge EMF of component COMP (PackAndSendFluxFC,
+// src/bvals/flux_correct_fc.cpp:84-360): the mean of the two fine edges along the edge's own direction, (fk, fj, fi)
+// the lower of them; a single edge where that direction is collapsed
+template <int COMP, class E>
+__device__ __forceinline__ double restrict_edge(int multi_d, int three_d, E &&e, int fk, int fj, int fi) {
+  if constexpr (COMP == 0) return multi_d ? 0.5*(e(fk, fj, fi) + e(fk, fj, fi + 1)) : e(fk, fj, fi);
+  else if constexpr (COMP == 1) return multi_d ? 0.5*(e(fk, fj, fi) + e(fk, fj + 1, fi)) : e(fk, fj, fi);
+  else return three_d ? 0.5*(e(fk, fj, fi) + e(fk + 1, fj, fi)) : e(fk, fj, fi);
+}
+
 // ProlongCC, src/mesh/prolongation.hpp:19-63: coarse cell (k, j, i) of ca into its fine cells of a
 template <class CA, class A>
 __device__ __forceinline__ void prolong_cc_cell(int multi_d, int three_d, CA &&ca, A &&a, int k, int j, int i,
@@ -131,7 +143,8 @@ __device__ __forceinline__ void prolong_fc_shared_face(int multi_d, int three_d,
 }
 
 // ProlongFCInternal, src/mesh/prolongation.hpp:166-230 (Toth & Roe 2002); 1-D: the mean of the two shared faces
-// (src/bvals/prolongation.cpp:765-770, src/mesh/mesh_refinement.cpp:1171-1174).  B1/B2/B3 return references.
+// (src/bvals/prolongation.cpp:765-770, src/mesh/mesh_refinement.cpp:1171-1174).  B1/B2/B3 return what can be
+// read and assigned.  Every inner face is assigned from shared faces only, none from another inner face.
 template <class F1, class F2, class F3>
 __device__ __forceinline__ void prolong_fc_internal_cell(int multi_d, int three_d, F1 &&B1, F2 &&B2, F3 &&B3,
                                                          int fk, int fj, int fi) {

@@ -15,38 +15,33 @@
 #include <vector>
 #include "akmi_common.hpp"
 #include "akmi_c2p.hpp"
+#include "akmi_refine_ops.hpp"
 
 namespace akmi {
 
-struct SGeo {
+struct SGeo {                     // what the kernels need of Geo and CGeo
   int N1, N2, N3, cN1, cN2, cN3;
   int is, ie, js, je, ks, ke, cis, cjs, cks;
   int multi_d, three_d;
 };
 static SGeo make_sgeo(const akmi_pack *p) {
-  Geo g = make_geo(p);
-  SGeo s;
-  s.N1 = g.N1; s.N2 = g.N2; s.N3 = g.N3;
-  const int cnx1 = g.nx1/2, cnx2 = g.multi_d ? g.nx2/2 : 1, cnx3 = g.three_d ? g.nx3/2 : 1;
-  s.cN1 = cnx1 + 2*g.ng; s.cN2 = g.multi_d ? cnx2 + 2*g.ng : 1; s.cN3 = g.three_d ? cnx3 + 2*g.ng : 1;
-  s.is = g.is; s.ie = g.ie; s.js = g.js; s.je = g.je; s.ks = g.ks; s.ke = g.ke;
-  s.cis = g.ng; s.cjs = g.multi_d ? g.ng : 0; s.cks = g.three_d ? g.ng : 0;
-  s.multi_d = g.multi_d; s.three_d = g.three_d;
-  return s;
+  const Geo g = make_geo(p);
+  const CGeo c = make_cgeo(g);
+  return SGeo{g.N1, g.N2, g.N3, c.cN1, c.cN2, c.cN3, g.is, g.ie, g.js, g.je, g.ks, g.ke, c.cis, c.cjs, c.cks,
+              g.multi_d, g.three_d};
 }
 
-struct Bx { int il, iu, jl, ju, kl, ku; };
 enum { K_SAME = 0, K_COAR = 1, K_FINE = 2, K_PROL = 3, K_FLXS = 4, K_FLXC = 5 };
 enum { T_SEND = 0, T_RECV = 1 };
-__device__ __forceinline__ Bx box_of(const int *tab, int sr, int kind, int n, int v) {
+__device__ __forceinline__ Box box_of(const int *tab, int sr, int kind, int n, int v) {
   const int *q = tab + ((((size_t)sr*6 + kind)*56 + n)*3 + v)*6;
-  return Bx{q[0], q[1], q[2], q[3], q[4], q[5]};
+  return Box{q[0], q[1], q[2], q[3], q[4], q[5]};
 }
-__device__ __forceinline__ int bcount(const Bx &b) {
+__device__ __forceinline__ int bcount(const Box &b) {
   return (b.iu - b.il + 1)*(b.ju - b.jl + 1)*(b.ku - b.kl + 1);
 }
 // element e of a box -> (k,j,i), i fastest
-__device__ __forceinline__ void bdecode(const Bx &b, int e, int &k, int &j, int &i) {
+__device__ __forceinline__ void bdecode(const Box &b, int e, int &k, int &j, int &i) {
   const int ni = b.iu - b.il + 1, nj = b.ju - b.jl + 1;
   i = b.il + e%ni; e /= ni;
   j = b.jl + e%nj;
@@ -127,7 +122,7 @@ k_smr_pack_cc(SGeo s, Tab t, int nvar, const double *__restrict__ a, const doubl
   if (dm < 0) return;
   const int nl = NLEV(t, m, n), ml = t.lev[m];
   if (t.direct && nl == ml && dm < t.nmb) return;          // filled by the caller's direct gather
-  const Bx b = box_of(t.cc, T_SEND, nl < ml ? K_COAR : (nl == ml ? K_SAME : K_FINE), n, 0);
+  const Box b = box_of(t.cc, T_SEND, nl < ml ? K_COAR : (nl == ml ? K_SAME : K_FINE), n, 0);
   const int cnt = bcount(b);
   double *out = buf + seg_w(t, 0, m, n, dm, NDST(t, m, n));
   const int coarse = nl < ml;
@@ -147,7 +142,7 @@ k_smr_unpack_cc(SGeo s, Tab t, int nvar, const double *__restrict__ buf, double 
   if (NGID(t, m, n) < 0) return;
   const int nl = NLEV(t, m, n), ml = t.lev[m];
   if (t.direct && nl == ml && NGID(t, m, n) < t.nmb) return;
-  const Bx b = box_of(t.cc, T_RECV, nl < ml ? K_COAR : (nl == ml ? K_SAME : K_FINE), n, 0);
+  const Box b = box_of(t.cc, T_RECV, nl < ml ? K_COAR : (nl == ml ? K_SAME : K_FINE), n, 0);
   const int cnt = bcount(b);
   const double *in = buf + seg_r(t, 0, m, n);
   const int coarse = nl < ml;
@@ -167,7 +162,7 @@ k_smr_pack_fc(SGeo s, Tab t, CF3 b, CF3 cb, double *__restrict__ buf) {
   if (dm < 0) return;
   const int nl = NLEV(t, m, n), ml = t.lev[m];
   const int q = nl < ml ? 1 : (nl == ml ? 0 : 2);
-  const Bx bx = box_of(t.fc, T_SEND, q == 1 ? K_COAR : (q == 0 ? K_SAME : K_FINE), n, v);
+  const Box bx = box_of(t.fc, T_SEND, q == 1 ? K_COAR : (q == 0 ? K_SAME : K_FINE), n, v);
   const int cnt = bcount(bx);
   const int dn = NDST(t, m, n);
   // the receiver unpacks with ITS ndat of slot dn and the matching level relation
@@ -191,7 +186,7 @@ __device__ __forceinline__ bool active_face(const SGeo &s, int v, int k, int j, 
 // later one wins), so a workgroup walks them with a barrier in between.  What a slot needs from the tables -- its box,
 // where its segment starts, which array it goes to -- is fetched for all slots at once into LDS first: inside the
 // walk those three dependent global look-ups per slot were most of the kernel's time (27 slots x ~2 us for a few KB).
-struct SlotMeta { Bx b; long long in; int q; };     // q: -1 no neighbour, 0 same level, 1 coarser, 2 finer
+struct SlotMeta { Box b; long long in; int q; };     // q: -1 no neighbour, 0 same level, 1 coarser, 2 finer
 __global__ void __launch_bounds__(256)
 k_smr_unpack_fc(SGeo s, Tab t, const double *__restrict__ buf, F3 b, F3 cb) {
   const int v = blockIdx.x%3, m = blockIdx.x/3;
@@ -200,7 +195,7 @@ k_smr_unpack_fc(SGeo s, Tab t, const double *__restrict__ buf, F3 b, F3 cb) {
   if ((int)threadIdx.x < t.nnghbr) {
     const int n = threadIdx.x;
     SlotMeta x;
-    x.q = -1; x.in = 0; x.b = Bx{0, -1, 0, -1, 0, -1};
+    x.q = -1; x.in = 0; x.b = Box{0, -1, 0, -1, 0, -1};
     if (NGID(t, m, n) >= 0) {
       const int nl = NLEV(t, m, n);
       x.q = nl < ml ? 1 : (nl == ml ? 0 : 2);
@@ -216,7 +211,7 @@ k_smr_unpack_fc(SGeo s, Tab t, const double *__restrict__ buf, F3 b, F3 cb) {
   for (int n = 0; n < t.nnghbr; ++n) {
     const int q = sm[n].q;
     if (q < 0) continue;                                   // uniform over the workgroup
-    const Bx bx = sm[n].b;
+    const Box bx = sm[n].b;
     const int cnt = bcount(bx);
     const double *in = buf + sm[n].in;
     const int coarse = q == 1;
@@ -236,20 +231,17 @@ __global__ void __launch_bounds__(256)
 k_smr_fill_coarse_cc(SGeo s, Tab t, int nvar, const double *__restrict__ a, double *__restrict__ ca) {
   int m, n, v; wg_slot(t, L_SAME_NEEDS, nvar, m, n, v); (void)v;
   if (NGID(t, m, n) < 0 || NLEV(t, m, n) != t.lev[m] || (t.needs && !t.needs[m])) return;
-  const Bx r = box_of(t.cc, T_RECV, K_SAME, n, 0);
-  const Bx b{(r.il + s.cis)/2, (r.iu + s.cis)/2, (r.jl + s.cjs)/2, (r.ju + s.cjs)/2, (r.kl + s.cks)/2,
+  const Box r = box_of(t.cc, T_RECV, K_SAME, n, 0);
+  const Box b{(r.il + s.cis)/2, (r.iu + s.cis)/2, (r.jl + s.cjs)/2, (r.ju + s.cjs)/2, (r.kl + s.cks)/2,
              (r.ku + s.cks)/2};
   const int cnt = bcount(b);
   for (int e = threadIdx.x; e < cnt; e += blockDim.x) {
     int k, j, i;
     bdecode(b, e, k, j, i);
-    const int fi = (i - s.cis)*2 + s.is, fj = (j - s.cjs)*2 + s.js, fk = (k - s.cks)*2 + s.ks;
+    // 2-D: the one plane of the box, in both arrays
+    const int fi = (i - s.cis)*2 + s.is, fj = (j - s.cjs)*2 + s.js, fk = s.three_d ? (k - s.cks)*2 + s.ks : b.kl;
     auto A = [&](int kk, int jj, int ii) { return a[c5(s, 0, nvar, m, v, kk, jj, ii)]; };
-    if (!s.three_d)
-      ca[c5(s, 1, nvar, m, v, b.kl, j, i)] = 0.25*(A(b.kl, fj, fi) + A(b.kl, fj, fi + 1) + A(b.kl, fj + 1, fi) + A(b.kl, fj + 1, fi + 1));
-    else
-      ca[c5(s, 1, nvar, m, v, k, j, i)] = 0.125*(A(fk, fj, fi) + A(fk, fj, fi + 1) + A(fk, fj + 1, fi) + A(fk, fj + 1, fi + 1)
-                                               + A(fk + 1, fj, fi) + A(fk + 1, fj, fi + 1) + A(fk + 1, fj + 1, fi) + A(fk + 1, fj + 1, fi + 1));
+    ca[c5(s, 1, nvar, m, v, s.three_d ? k : b.kl, j, i)] = restrict_cc_cell(s.multi_d, s.three_d, A, fk, fj, fi);
   }
 }
 
@@ -258,37 +250,23 @@ __global__ void __launch_bounds__(256)
 k_smr_fill_coarse_fc(SGeo s, Tab t, CF3 b, F3 cb) {
   int m, n, v; wg_slot(t, L_SAME_NEEDS, 3, m, n, v); (void)v;
   if (NGID(t, m, n) < 0 || NLEV(t, m, n) != t.lev[m] || (t.needs && !t.needs[m])) return;
-  const Bx r = box_of(t.fc, T_RECV, K_SAME, n, v);
-  const Bx bx{(r.il + s.cis)/2, (r.iu + s.cis)/2, (r.jl + s.cjs)/2, (r.ju + s.cjs)/2, (r.kl + s.cks)/2,
+  const Box r = box_of(t.fc, T_RECV, K_SAME, n, v);
+  const Box bx{(r.il + s.cis)/2, (r.iu + s.cis)/2, (r.jl + s.cjs)/2, (r.ju + s.cjs)/2, (r.kl + s.cks)/2,
               (r.ku + s.cks)/2};
   const int cnt = bcount(bx);
   auto B = [&](int kk, int jj, int ii) { return b.b[v][f4(s, 0, v, m, kk, jj, ii)]; };
   for (int e = threadIdx.x; e < cnt; e += blockDim.x) {
     int k, j, i;
     bdecode(bx, e, k, j, i);
-    const int fi = (i - s.cis)*2 + s.is, fj = (j - s.cjs)*2 + s.js, fk = (k - s.cks)*2 + s.ks;
-    const int kl = bx.kl;
-    if (!s.three_d) {
-      if (v == 0) cb.b[0][f4(s, 1, 0, m, kl, j, i)] = 0.5*(B(kl, fj, fi) + B(kl, fj + 1, fi));
-      else if (v == 1) cb.b[1][f4(s, 1, 1, m, kl, j, i)] = 0.5*(B(kl, fj, fi) + B(kl, fj, fi + 1));
-      else {
-        const double b3c = 0.25*(B(kl, fj, fi) + B(kl, fj, fi + 1) + B(kl, fj + 1, fi) + B(kl, fj + 1, fi + 1));
-        cb.b[2][f4(s, 1, 2, m, kl, j, i)] = b3c;
-        cb.b[2][f4(s, 1, 2, m, kl + 1, j, i)] = b3c;
-      }
-    } else {
-      double r4;
-      if (v == 0) r4 = 0.25*(B(fk, fj, fi) + B(fk, fj + 1, fi) + B(fk + 1, fj, fi) + B(fk + 1, fj + 1, fi));
-      else if (v == 1) r4 = 0.25*(B(fk, fj, fi) + B(fk, fj, fi + 1) + B(fk + 1, fj, fi) + B(fk + 1, fj, fi + 1));
-      else r4 = 0.25*(B(fk, fj, fi) + B(fk, fj, fi + 1) + B(fk, fj + 1, fi) + B(fk, fj + 1, fi + 1));
-      cb.b[v][f4(s, 1, v, m, k, j, i)] = r4;
-    }
+    // 2-D: the one plane of the box, and an x3 face on both of its planes
+    const int fi = (i - s.cis)*2 + s.is, fj = (j - s.cjs)*2 + s.js, fk = s.three_d ? (k - s.cks)*2 + s.ks : bx.kl;
+    const int ck = s.three_d ? k : bx.kl;
+    const double r = v == 0 ? restrict_fc_face<0>(s.multi_d, s.three_d, B, fk, fj, fi)
+                   : v == 1 ? restrict_fc_face<1>(s.multi_d, s.three_d, B, fk, fj, fi)
+                            : restrict_fc_face<2>(s.multi_d, s.three_d, B, fk, fj, fi);
+    cb.b[v][f4(s, 1, v, m, ck, j, i)] = r;
+    if (v == 2 && !s.three_d) cb.b[2][f4(s, 1, 2, m, ck + 1, j, i)] = r;
   }
-}
-
-__device__ __forceinline__ double s_sgn(double x) { return (x < 0.0) ? -1.0 : 1.0; }        // SIGN, athena.hpp:52
-__device__ __forceinline__ double s_mm8(double dl, double dr) {
-  return 0.125*(s_sgn(dl) + s_sgn(dr))*fmin(fabs(dl), fabs(dr));
 }
 
 // ---- ProlongateCC (ProlongCC, src/mesh/prolongation.hpp:19-63) -----------------------------------
@@ -296,7 +274,7 @@ __global__ void __launch_bounds__(256)
 k_smr_prolong_cc(SGeo s, Tab t, int nvar, const double *__restrict__ ca, double *__restrict__ a) {
   int m, n, v; wg_slot(t, L_COARSER, 1, m, n, v); (void)v;
   if (NGID(t, m, n) < 0 || !(NLEV(t, m, n) < t.lev[m])) return;
-  const Bx b = box_of(t.cc, T_RECV, K_PROL, n, 0);
+  const Box b = box_of(t.cc, T_RECV, K_PROL, n, 0);
   const int cnt = bcount(b);
   for (int ev = threadIdx.x; ev < cnt*nvar; ev += blockDim.x) {
     const int v = ev/cnt, e = ev - v*cnt;
@@ -305,23 +283,7 @@ k_smr_prolong_cc(SGeo s, Tab t, int nvar, const double *__restrict__ ca, double 
     int k, j, i;
     bdecode(b, e, k, j, i);
     const int fi = (i - s.cis)*2 + s.is, fj = (j - s.cjs)*2 + s.js, fk = (k - s.cks)*2 + s.ks;
-    const double q = CA(k, j, i);
-    const double dvar1 = s_mm8(q - CA(k, j, i - 1), CA(k, j, i + 1) - q);
-    double dvar2 = 0.0, dvar3 = 0.0;
-    if (s.multi_d) dvar2 = s_mm8(q - CA(k, j - 1, i), CA(k, j + 1, i) - q);
-    if (s.three_d) dvar3 = s_mm8(q - CA(k - 1, j, i), CA(k + 1, j, i) - q);
-    A(fk, fj, fi) = q - dvar1 - dvar2 - dvar3;
-    A(fk, fj, fi + 1) = q + dvar1 - dvar2 - dvar3;
-    if (s.multi_d) {
-      A(fk, fj + 1, fi) = q - dvar1 + dvar2 - dvar3;
-      A(fk, fj + 1, fi + 1) = q + dvar1 + dvar2 - dvar3;
-    }
-    if (s.three_d) {
-      A(fk + 1, fj, fi) = q - dvar1 - dvar2 + dvar3;
-      A(fk + 1, fj, fi + 1) = q + dvar1 - dvar2 + dvar3;
-      A(fk + 1, fj + 1, fi) = q - dvar1 + dvar2 + dvar3;
-      A(fk + 1, fj + 1, fi + 1) = q + dvar1 + dvar2 + dvar3;
-    }
+    prolong_cc_cell(s.multi_d, s.three_d, CA, A, k, j, i, fk, fj, fi);
   }
 }
 
@@ -335,7 +297,7 @@ __global__ void __launch_bounds__(256)
 k_smr_c2p_coarse(SGeo s, Tab t, Eos eos, int nvar, int mhd, double *__restrict__ cu, CF3 cb, double *__restrict__ cw) {
   int m, n, v; wg_slot(t, L_COARSER, 1, m, n, v); (void)v;
   if (NGID(t, m, n) < 0 || !(NLEV(t, m, n) < t.lev[m])) return;
-  Bx b = box_of(t.cc, T_RECV, K_PROL, n, 0);
+  Box b = box_of(t.cc, T_RECV, K_PROL, n, 0);
   // (widened by one cell, as the reference does: the boxes of different slots of a block then overlap, and several
   //  workgroups convert the same coarse cells concurrently -- every one of them writes the SAME values (cw, and cu
   //  where a floor or a negative scalar was reset: functions of that cell's cu alone), so the race is benign)
@@ -379,8 +341,8 @@ __global__ void __launch_bounds__(256)
 k_smr_p2c_fine(SGeo s, Tab t, int nvar, int mhd, const double *__restrict__ w, CF3 fb, double *__restrict__ u) {
   int m, n, v; wg_slot(t, L_COARSER, 1, m, n, v); (void)v;
   if (NGID(t, m, n) < 0 || !(NLEV(t, m, n) < t.lev[m])) return;
-  const Bx c = box_of(t.cc, T_RECV, K_PROL, n, 0);
-  Bx b;
+  const Box c = box_of(t.cc, T_RECV, K_PROL, n, 0);
+  Box b;
   b.il = (c.il - s.cis)*2 + s.is; b.iu = (c.iu - s.cis)*2 + s.is + 1;
   b.jl = (c.jl - s.cjs)*2 + s.js; b.ju = (c.ju - s.cjs)*2 + s.js + (s.multi_d ? 1 : 0);
   b.kl = (c.kl - s.cks)*2 + s.ks; b.ku = (c.ku - s.cks)*2 + s.ks + (s.three_d ? 1 : 0);
@@ -388,23 +350,12 @@ k_smr_p2c_fine(SGeo s, Tab t, int nvar, int mhd, const double *__restrict__ w, C
   for (int e = threadIdx.x; e < cnt; e += blockDim.x) {
     int k, j, i;
     bdecode(b, e, k, j, i);
-    const double d = w[c5(s, 0, nvar, m, 0, k, j, i)], vx = w[c5(s, 0, nvar, m, 1, k, j, i)],
-                 vy = w[c5(s, 0, nvar, m, 2, k, j, i)], vz = w[c5(s, 0, nvar, m, 3, k, j, i)],
-                 ei = w[c5(s, 0, nvar, m, 4, k, j, i)];
-    u[c5(s, 0, nvar, m, 0, k, j, i)] = d;
-    u[c5(s, 0, nvar, m, 1, k, j, i)] = d*vx;
-    u[c5(s, 0, nvar, m, 2, k, j, i)] = d*vy;
-    u[c5(s, 0, nvar, m, 3, k, j, i)] = d*vz;
-    if (mhd) {
-      double bx, by, bz;
+    double bx = 0.0, by = 0.0, bz = 0.0;
+    if (mhd)
       cell_bcc(fb.b[0][f4(s, 0, 0, m, k, j, i)], fb.b[0][f4(s, 0, 0, m, k, j, i + 1)], fb.b[1][f4(s, 0, 1, m, k, j, i)],
                fb.b[1][f4(s, 0, 1, m, k, j + 1, i)], fb.b[2][f4(s, 0, 2, m, k, j, i)], fb.b[2][f4(s, 0, 2, m, k + 1, j, i)],
                bx, by, bz);
-      u[c5(s, 0, nvar, m, 4, k, j, i)] = ei + 0.5*(d*(sqr(vx) + sqr(vy) + sqr(vz)) + (sqr(bx) + sqr(by) + sqr(bz)));
-    } else {
-      u[c5(s, 0, nvar, m, 4, k, j, i)] = ei + 0.5*d*(sqr(vx) + sqr(vy) + sqr(vz));
-    }
-    for (int v = 5; v < nvar; ++v) u[c5(s, 0, nvar, m, v, k, j, i)] = d*w[c5(s, 0, nvar, m, v, k, j, i)];
+    p2c_at(nvar, true, mhd, w, u, c5(s, 0, nvar, m, 0, k, j, i), (size_t)s.N3*s.N2*s.N1, bx, by, bz);
   }
 }
 
@@ -437,6 +388,14 @@ struct Owned {
     return ox1 == 0 && ox2 == 0 && ox3 == nox && maxlev(0, 0, nox) < mylev;
   }
 };
+// Face (k, j, i) of component v as the operators of akmi_refine_ops.hpp see it: read as a double (through r);
+// assigned (through w, the same place) only where this slot may prolongate it.  can() walks the neighbour table for
+// faces on the block surface: it runs in the assignment alone.
+struct OwnedFace {
+  const Owned &own; const double *r; double *w; int v, k, j, i;
+  __device__ __forceinline__ operator double() const { return *r; }
+  __device__ __forceinline__ void operator=(double val) const { if (own.can(v, k, j, i)) *w = val; }
+};
 
 // ---- ProlongateFC, shared faces (ProlongFCSharedX1/2/3FaceOwned, prolongation.cpp:149-258) -------
 __global__ void __launch_bounds__(256)
@@ -444,11 +403,12 @@ k_smr_prolong_fc_shared(SGeo s, Tab t, const int *__restrict__ slot_ox, CF3 cb, 
   int m, n, v; wg_slot(t, L_COARSER, 3, m, n, v); (void)v;
   if (NGID(t, m, n) < 0 || !(NLEV(t, m, n) < t.lev[m])) return;
   const Owned own{s, t, m, slot_ox[3*n], slot_ox[3*n + 1], slot_ox[3*n + 2], t.lev[m]};
-  const Bx bx = box_of(t.fc, T_RECV, K_PROL, n, v);
+  const Box bx = box_of(t.fc, T_RECV, K_PROL, n, v);
   const int cnt = bcount(bx);
   auto C = [&](int kk, int jj, int ii) { return cb.b[v][f4(s, 1, v, m, kk, jj, ii)]; };
-  auto ST = [&](int kk, int jj, int ii, double val) {
-    if (own.can(v, kk, jj, ii)) b.b[v][f4(s, 0, v, m, kk, jj, ii)] = val;
+  auto B = [&](int kk, int jj, int ii) {
+    double *p = &b.b[v][f4(s, 0, v, m, kk, jj, ii)];
+    return OwnedFace{own, p, p, v, kk, jj, ii};
   };
   for (int e = threadIdx.x; e < cnt; e += blockDim.x) {
     int k, j, i;
@@ -456,101 +416,43 @@ k_smr_prolong_fc_shared(SGeo s, Tab t, const int *__restrict__ slot_ox, CF3 cb, 
     const int fi = (i - s.cis)*2 + s.is;
     const int fj = s.multi_d ? (j - s.cjs)*2 + s.js : j;
     const int fk = s.three_d ? (k - s.cks)*2 + s.ks : k;
-    const double q = C(k, j, i);
-    if (v == 0) {
-      double dvar2 = 0.0, dvar3 = 0.0;
-      if (s.multi_d) dvar2 = s_mm8(q - C(k, j - 1, i), C(k, j + 1, i) - q);
-      if (s.three_d) dvar3 = s_mm8(q - C(k - 1, j, i), C(k + 1, j, i) - q);
-      ST(fk, fj, fi, q - dvar2 - dvar3);
-      if (s.multi_d) ST(fk, fj + 1, fi, q + dvar2 - dvar3);
-      if (s.three_d) { ST(fk + 1, fj, fi, q - dvar2 + dvar3); ST(fk + 1, fj + 1, fi, q + dvar2 + dvar3); }
-    } else if (v == 1) {
-      const double dvar1 = s_mm8(q - C(k, j, i - 1), C(k, j, i + 1) - q);
-      double dvar3 = 0.0;
-      if (s.three_d) dvar3 = s_mm8(q - C(k - 1, j, i), C(k + 1, j, i) - q);
-      ST(fk, fj, fi, q - dvar1 - dvar3);
-      ST(fk, fj, fi + 1, q + dvar1 - dvar3);
-      if (s.three_d) { ST(fk + 1, fj, fi, q - dvar1 + dvar3); ST(fk + 1, fj, fi + 1, q + dvar1 + dvar3); }
-    } else {
-      const double dvar1 = s_mm8(q - C(k, j, i - 1), C(k, j, i + 1) - q);
-      double dvar2 = 0.0;
-      if (s.multi_d) dvar2 = s_mm8(q - C(k, j - 1, i), C(k, j + 1, i) - q);
-      ST(fk, fj, fi, q - dvar1 - dvar2);
-      ST(fk, fj, fi + 1, q + dvar1 - dvar2);
-      if (s.multi_d) { ST(fk, fj + 1, fi, q - dvar1 + dvar2); ST(fk, fj + 1, fi + 1, q + dvar1 + dvar2); }
-    }
+    if (v == 0) prolong_fc_shared_face<0>(s.multi_d, s.three_d, C, B, k, j, i, fk, fj, fi);
+    else if (v == 1) prolong_fc_shared_face<1>(s.multi_d, s.three_d, C, B, k, j, i, fk, fj, fi);
+    else prolong_fc_shared_face<2>(s.multi_d, s.three_d, C, B, k, j, i, fk, fj, fi);
   }
 }
 
 // ---- ProlongateFC, faces inside the coarse cells (ProlongFCInternalOwned, :260-359) ---------------
+// The cells of one slot.  r1..r3 are b's three arrays once more: the operator reads shared faces (even fine indices
+// from the block's first cell) and assigns the faces inside the coarse cells (odd ones), so no face that is read here
+// is written here, and read through pointers of their own the operands need not be fetched again after every
+// guarded store (24 more loads per cell, 64 -> 77 us at 960 blocks of 32^3; profiles/smr_shared_ops.txt).
+__device__ __forceinline__ void prolong_fc_internal_slot(const SGeo &s, const Owned &own, const Box &bx,
+                                                         const double *__restrict__ r1, const double *__restrict__ r2,
+                                                         const double *__restrict__ r3, const F3 &b) {
+  const int m = own.m, cnt = bcount(bx);
+  auto face = [&](const double *r, int v, int kk, int jj, int ii) {
+    const size_t o = f4(s, 0, v, m, kk, jj, ii);
+    return OwnedFace{own, r + o, b.b[v] + o, v, kk, jj, ii};
+  };
+  auto B1 = [&](int kk, int jj, int ii) { return face(r1, 0, kk, jj, ii); };
+  auto B2 = [&](int kk, int jj, int ii) { return face(r2, 1, kk, jj, ii); };
+  auto B3 = [&](int kk, int jj, int ii) { return face(r3, 2, kk, jj, ii); };
+  for (int e = threadIdx.x; e < cnt; e += blockDim.x) {
+    int k, j, i;
+    bdecode(bx, e, k, j, i);
+    const int fi = (i - s.cis)*2 + s.is, fj = (j - s.cjs)*2 + s.js, fk = (k - s.cks)*2 + s.ks;
+    prolong_fc_internal_cell(s.multi_d, s.three_d, B1, B2, B3, fk, fj, fi);
+  }
+}
 __global__ void __launch_bounds__(256)
 k_smr_prolong_fc_internal(SGeo s, Tab t, const int *__restrict__ slot_ox, F3 b) {
   int m, n, v; wg_slot(t, L_COARSER, 1, m, n, v); (void)v;
   if (NGID(t, m, n) < 0 || !(NLEV(t, m, n) < t.lev[m])) return;
   const Owned own{s, t, m, slot_ox[3*n], slot_ox[3*n + 1], slot_ox[3*n + 2], t.lev[m]};
-  const Bx p0 = box_of(t.fc, T_RECV, K_PROL, n, 0), p1 = box_of(t.fc, T_RECV, K_PROL, n, 1),
-           p2 = box_of(t.fc, T_RECV, K_PROL, n, 2);
-  const Bx bx{p2.il, p2.iu, p0.jl, p0.ju, p1.kl, p1.ku};
-  const int cnt = bcount(bx);
-  auto B1 = [&](int kk, int jj, int ii) { return b.b[0][f4(s, 0, 0, m, kk, jj, ii)]; };
-  auto B2 = [&](int kk, int jj, int ii) { return b.b[1][f4(s, 0, 1, m, kk, jj, ii)]; };
-  auto B3 = [&](int kk, int jj, int ii) { return b.b[2][f4(s, 0, 2, m, kk, jj, ii)]; };
-  auto ST = [&](int v, int kk, int jj, int ii, double val) {
-    if (own.can(v, kk, jj, ii)) b.b[v][f4(s, 0, v, m, kk, jj, ii)] = val;
-  };
-  for (int e = threadIdx.x; e < cnt; e += blockDim.x) {
-    int k, j, i;
-    bdecode(bx, e, k, j, i);
-    const int fi = (i - s.cis)*2 + s.is, fj = (j - s.cjs)*2 + s.js, fk = (k - s.cks)*2 + s.ks;
-    if (!s.multi_d) {
-      ST(0, fk, fj, fi + 1, 0.5*(B1(fk, fj, fi) + B1(fk, fj, fi + 2)));
-    } else if (s.three_d) {
-      double Uxx = 0.0, Vyy = 0.0, Wzz = 0.0, Uxyz = 0.0, Vxyz = 0.0, Wxyz = 0.0;
-      for (int jj = 0; jj < 2; jj++) {
-        const int jsgn = 2*jj - 1, fjj = fj + jj, fjp = fj + 2*jj;
-        for (int ii = 0; ii < 2; ii++) {
-          const int isgn = 2*ii - 1, fii = fi + ii, fip = fi + 2*ii;
-          Uxx += isgn*(jsgn*(B2(fk, fjp, fii) + B2(fk + 1, fjp, fii)) + (B3(fk + 2, fjj, fii) - B3(fk, fjj, fii)));
-          Vyy += jsgn*((B3(fk + 2, fjj, fii) - B3(fk, fjj, fii)) + isgn*(B1(fk, fjj, fip) + B1(fk + 1, fjj, fip)));
-          Wzz += isgn*(B1(fk + 1, fjj, fip) - B1(fk, fjj, fip)) + jsgn*(B2(fk + 1, fjp, fii) - B2(fk, fjp, fii));
-          Uxyz += isgn*jsgn*(B1(fk + 1, fjj, fip) - B1(fk, fjj, fip));
-          Vxyz += isgn*jsgn*(B2(fk + 1, fjp, fii) - B2(fk, fjp, fii));
-          Wxyz += isgn*jsgn*(B3(fk + 2, fjj, fii) - B3(fk, fjj, fii));
-        }
-      }
-      Uxx *= 0.125; Vyy *= 0.125; Wzz *= 0.125;
-      Uxyz *= 0.0625; Vxyz *= 0.0625; Wxyz *= 0.0625;
-      // all operands are read before any store of this cell (the stores touch only faces strictly
-      // inside the coarse cell, which no other cell reads)
-      const double a00 = 0.5*(B1(fk, fj, fi) + B1(fk, fj, fi + 2)), a01 = 0.5*(B1(fk, fj + 1, fi) + B1(fk, fj + 1, fi + 2)),
-                   a10 = 0.5*(B1(fk + 1, fj, fi) + B1(fk + 1, fj, fi + 2)), a11 = 0.5*(B1(fk + 1, fj + 1, fi) + B1(fk + 1, fj + 1, fi + 2));
-      const double c00 = 0.5*(B2(fk, fj, fi) + B2(fk, fj + 2, fi)), c01 = 0.5*(B2(fk, fj, fi + 1) + B2(fk, fj + 2, fi + 1)),
-                   c10 = 0.5*(B2(fk + 1, fj, fi) + B2(fk + 1, fj + 2, fi)), c11 = 0.5*(B2(fk + 1, fj, fi + 1) + B2(fk + 1, fj + 2, fi + 1));
-      const double d00 = 0.5*(B3(fk + 2, fj, fi) + B3(fk, fj, fi)), d01 = 0.5*(B3(fk + 2, fj, fi + 1) + B3(fk, fj, fi + 1)),
-                   d10 = 0.5*(B3(fk + 2, fj + 1, fi) + B3(fk, fj + 1, fi)), d11 = 0.5*(B3(fk + 2, fj + 1, fi + 1) + B3(fk, fj + 1, fi + 1));
-      ST(0, fk, fj, fi + 1, a00 + Uxx - Vxyz - Wxyz);
-      ST(0, fk, fj + 1, fi + 1, a01 + Uxx - Vxyz + Wxyz);
-      ST(0, fk + 1, fj, fi + 1, a10 + Uxx + Vxyz - Wxyz);
-      ST(0, fk + 1, fj + 1, fi + 1, a11 + Uxx + Vxyz + Wxyz);
-      ST(1, fk, fj + 1, fi, c00 + Vyy - Uxyz - Wxyz);
-      ST(1, fk, fj + 1, fi + 1, c01 + Vyy - Uxyz + Wxyz);
-      ST(1, fk + 1, fj + 1, fi, c10 + Vyy + Uxyz - Wxyz);
-      ST(1, fk + 1, fj + 1, fi + 1, c11 + Vyy + Uxyz + Wxyz);
-      ST(2, fk + 1, fj, fi, d00 + Wzz - Uxyz - Vxyz);
-      ST(2, fk + 1, fj, fi + 1, d01 + Wzz - Uxyz + Vxyz);
-      ST(2, fk + 1, fj + 1, fi, d10 + Wzz + Uxyz - Vxyz);
-      ST(2, fk + 1, fj + 1, fi + 1, d11 + Wzz + Uxyz + Vxyz);
-    } else {
-      const double tmp1 = 0.25*(B2(fk, fj + 2, fi + 1) - B2(fk, fj, fi + 1) - B2(fk, fj + 2, fi) + B2(fk, fj, fi));
-      const double tmp2 = 0.25*(B1(fk, fj, fi) - B1(fk, fj, fi + 2) - B1(fk, fj + 1, fi) + B1(fk, fj + 1, fi + 2));
-      const double a0 = 0.5*(B1(fk, fj, fi) + B1(fk, fj, fi + 2)), a1 = 0.5*(B1(fk, fj + 1, fi) + B1(fk, fj + 1, fi + 2));
-      const double c0 = 0.5*(B2(fk, fj, fi) + B2(fk, fj + 2, fi)), c1 = 0.5*(B2(fk, fj, fi + 1) + B2(fk, fj + 2, fi + 1));
-      ST(0, fk, fj, fi + 1, a0 + tmp1);
-      ST(0, fk, fj + 1, fi + 1, a1 + tmp1);
-      ST(1, fk, fj + 1, fi, c0 + tmp2);
-      ST(1, fk, fj + 1, fi + 1, c1 + tmp2);
-    }
-  }
+  const Box p0 = box_of(t.fc, T_RECV, K_PROL, n, 0), p1 = box_of(t.fc, T_RECV, K_PROL, n, 1),
+            p2 = box_of(t.fc, T_RECV, K_PROL, n, 2);
+  prolong_fc_internal_slot(s, own, Box{p2.il, p2.iu, p0.jl, p0.ju, p1.kl, p1.ku}, b.b[0], b.b[1], b.b[2], b);
 }
 
 // ---- PackAndSendFluxCC: restricted fluxes of a finer block into the coarser neighbour's buffer ----
@@ -562,7 +464,7 @@ k_smr_pack_flux_cc(SGeo s, Tab t, int nvar, int fs, Flx3 flx, double *__restrict
   if (dm < 0 || !(NLEV(t, m, n) < t.lev[m])) return;
   int dir;
   if (n < 8) dir = 0; else if (n < 16) dir = 1; else if (n >= 24 && n < 32) dir = 2; else return;
-  const Bx b = box_of(t.cc, T_SEND, K_FLXC, n, 0);
+  const Box b = box_of(t.cc, T_SEND, K_FLXC, n, 0);
   const int cnt = bcount(b);
   double *out = buf + seg_w(t, 1, m, n, dm, NDST(t, m, n)) + (size_t)cnt*v;
   const double *f = flx.f[dir];
@@ -572,19 +474,11 @@ k_smr_pack_flux_cc(SGeo s, Tab t, int nvar, int fs, Flx3 flx, double *__restrict
   for (int e = threadIdx.x; e < cnt; e += blockDim.x) {
     int k, j, i;
     bdecode(b, e, k, j, i);
-    const int fi = 2*i - s.cis, fj = 2*j - s.cjs, fk = 2*k - s.cks;
-    double r;
-    if (dir == 0) {
-      if (!s.multi_d) r = X(0, 0, fi);
-      else if (!s.three_d) r = 0.5*(X(0, fj, fi) + X(0, fj + 1, fi));
-      else r = 0.25*(X(fk, fj, fi) + X(fk, fj + 1, fi) + X(fk + 1, fj, fi) + X(fk + 1, fj + 1, fi));
-    } else if (dir == 1) {
-      if (!s.three_d) r = 0.5*(X(0, fj, fi) + X(0, fj, fi + 1));
-      else r = 0.25*(X(fk, fj, fi) + X(fk, fj, fi + 1) + X(fk + 1, fj, fi) + X(fk + 1, fj, fi + 1));
-    } else {
-      r = 0.25*(X(fk, fj, fi) + X(fk, fj, fi + 1) + X(fk, fj + 1, fi) + X(fk, fj + 1, fi + 1));
-    }
-    out[e] = r;       // box order (i fastest) == the reference's (j,k)/(i,k)/(i,j) order: one extent is 1
+    const int fi = 2*i - s.cis, fj = s.multi_d ? 2*j - s.cjs : 0, fk = s.three_d ? 2*k - s.cks : 0;
+    // box order (i fastest) == the reference's (j,k)/(i,k)/(i,j) order: one extent is 1
+    out[e] = dir == 0 ? restrict_fc_face<0>(s.multi_d, s.three_d, X, fk, fj, fi)
+           : dir == 1 ? restrict_fc_face<1>(s.multi_d, s.three_d, X, fk, fj, fi)
+                      : restrict_fc_face<2>(s.multi_d, s.three_d, X, fk, fj, fi);
   }
 }
 
@@ -594,7 +488,7 @@ k_smr_unpack_flux_cc(SGeo s, Tab t, int nvar, int fs, const double *__restrict__
   if (NGID(t, m, n) < 0 || !(NLEV(t, m, n) > t.lev[m])) return;
   int dir;
   if (n < 8) dir = 0; else if (n < 16) dir = 1; else if (n >= 24 && n < 32) dir = 2; else return;
-  const Bx b = box_of(t.cc, T_RECV, K_FLXC, n, 0);
+  const Box b = box_of(t.cc, T_RECV, K_FLXC, n, 0);
   const int cnt = bcount(b);
   const double *in = buf + seg_r(t, 1, m, n) + (size_t)cnt*v;
   double *f = flx.f[dir];
@@ -629,7 +523,7 @@ k_smr_pack_flux_fc(SGeo s, Tab t, E3 ef, double *__restrict__ buf) {
   const int dm = NGID(t, m, n);
   if (dm < 0 || !(NLEV(t, m, n) <= t.lev[m]) || !slot_has(n, v)) return;
   const bool same = NLEV(t, m, n) == t.lev[m];
-  const Bx b = box_of(t.fc, T_SEND, same ? K_FLXS : K_FLXC, n, v);
+  const Box b = box_of(t.fc, T_SEND, same ? K_FLXS : K_FLXC, n, v);
   const int cnt = bcount(b);
   const int dn = NDST(t, m, n);
   double *out = buf + seg_w(t, 3, m, n, dm, dn) + (size_t)ndat_of(t, 1, dn, T_RECV, same ? 3 : 4)*v;
@@ -643,41 +537,36 @@ k_smr_pack_flux_fc(SGeo s, Tab t, E3 ef, double *__restrict__ buf) {
       r = E(k, j, i);
     } else {
       const int fi = 2*i - s.cis, fj = s.multi_d ? 2*j - s.cjs : 0, fk = s.three_d ? 2*k - s.cks : 0;
-      // a coarse edge of component v is the average of the two fine edges along direction v; in
-      // collapsed directions there is one (flux_correct_fc.cpp:88-101,136-148,...)
-      if (v == 0) r = 0.5*(E(fk, fj, fi) + E(fk, fj, fi + 1));
-      else if (v == 1) r = s.multi_d ? 0.5*(E(fk, fj, fi) + E(fk, fj + 1, fi)) : E(0, 0, fi);
-      else r = s.three_d ? 0.5*(E(fk, fj, fi) + E(fk + 1, fj, fi)) : E(0, fj, fi);
+      // (component 0 travels through no slot of a 1-D mesh: slot_has)
+      r = v == 0 ? restrict_edge<0>(s.multi_d, s.three_d, E, fk, fj, fi)
+        : v == 1 ? restrict_edge<1>(s.multi_d, s.three_d, E, fk, fj, fi)
+                 : restrict_edge<2>(s.multi_d, s.three_d, E, fk, fj, fi);
     }
     out[q] = r;
   }
 }
 
-// SumBoundaryFluxes: slots of a (block, component) one after the other
-__global__ void __launch_bounds__(256)
-k_smr_sum_flux_fc(SGeo s, Tab t, int same_level, const double *__restrict__ buf, E3 ef) {
-  const int v = blockIdx.x%3, m = blockIdx.x/3;
-  const int ml = t.lev[m];
-  double *e = ef.e[v];
-  __shared__ SlotMeta sm[48];                 // table look-ups of all slots first (see k_smr_unpack_fc)
-  if ((int)threadIdx.x < 48) {
-    const int n = threadIdx.x;
-    SlotMeta x;
-    x.q = -1; x.in = 0; x.b = Bx{0, -1, 0, -1, 0, -1};
-    if (n < t.nnghbr && NGID(t, m, n) >= 0) {
-      const int nl = NLEV(t, m, n);
-      if (((same_level && nl == ml) || (!same_level && nl > ml)) && slot_has(n, v)) {
-        x.q = 0;
-        x.b = box_of(t.fc, T_RECV, same_level ? K_FLXS : K_FLXC, n, v);
-        x.in = (long long)seg_r(t, 3, m, n) + (long long)ndat_of(t, 1, n, T_RECV, same_level ? 3 : 4)*v;
-      }
+// ---- RecvAndUnpackFluxFC: the steps on the edges e of component v of block m, each written once ----
+// What slot n adds to them: from a neighbour of the same level (same_level) or from a finer one; q < 0: nothing
+__device__ __forceinline__ SlotMeta emf_slot(const Tab &t, int m, int n, int v, int same_level) {
+  SlotMeta x;
+  x.q = -1; x.in = 0; x.b = Box{0, -1, 0, -1, 0, -1};
+  if (n < t.nnghbr && NGID(t, m, n) >= 0 && slot_has(n, v)) {
+    const int nl = NLEV(t, m, n), ml = t.lev[m];
+    if (same_level ? nl == ml : nl > ml) {
+      x.q = 0;
+      x.b = box_of(t.fc, T_RECV, same_level ? K_FLXS : K_FLXC, n, v);
+      x.in = (long long)seg_r(t, 3, m, n) + (long long)ndat_of(t, 1, n, T_RECV, same_level ? 3 : 4)*v;
     }
-    sm[n] = x;
   }
-  __syncthreads();
+  return x;
+}
+// SumBoundaryFluxes: the slots one after the other (their boxes overlap along the block's edges)
+__device__ __forceinline__ void emf_sum(const SGeo &s, const Tab &t, const SlotMeta *sm, const double *__restrict__ buf,
+                                        double *e, int v, int m) {
   for (int n = 0; n < t.nnghbr && n < 48; ++n) {
-    if (sm[n].q < 0) continue;
-    const Bx b = sm[n].b;
+    if (sm[n].q < 0) continue;                 // (uniform over the workgroup)
+    const Box b = sm[n].b;
     const int cnt = bcount(b);
     const double *in = buf + sm[n].in;
     for (int q = threadIdx.x; q < cnt; q += blockDim.x) {
@@ -688,34 +577,27 @@ k_smr_sum_flux_fc(SGeo s, Tab t, int same_level, const double *__restrict__ buf,
     __syncthreads();
   }
 }
-
-// ZeroFluxesAtBoundaryWithFiner
-__global__ void __launch_bounds__(256)
-k_smr_zero_flux_fc(SGeo s, Tab t, E3 ef) {
-  int m, n, v; wg_slot(t, L_FINER, 3, m, n, v); (void)v;
-  if (n >= 48 || NGID(t, m, n) < 0 || !(NLEV(t, m, n) > t.lev[m]) || !slot_has(n, v)) return;
-  const Bx b = box_of(t.fc, T_RECV, K_FLXC, n, v);
+// ZeroFluxesAtBoundaryWithFiner: the receive box of one slot with a finer neighbour
+__device__ __forceinline__ void emf_zero(const SGeo &s, const Box &b, double *e, int v, int m) {
   const int cnt = bcount(b);
   for (int q = threadIdx.x; q < cnt; q += blockDim.x) {
     int k, j, i;
     bdecode(b, q, k, j, i);
-    ef.e[v][e4(s, v, m, k, j, i)] = 0.0;
+    e[e4(s, v, m, k, j, i)] = 0.0;
   }
 }
-
-// AverageBoundaryFluxes (flux_correct_fc.cpp:801-1034); nflx[nmb][48] from the host (the counting
-// of :470-570 and :676-760 depends on the neighbour table only)
-__global__ void __launch_bounds__(256)
-k_smr_average_flux_fc(SGeo s, Tab t, const int *__restrict__ nflx, E3 ef) {
-  int m, n, v; wg_slot(t, L_AVG, 3, m, n, v); (void)v;
-  if (n >= 48 || !slot_has(n, v)) return;
-  // only the first sub-block slot of a face / edge carries the averaging (n = 0,4,8,12,16,18,...)
-  const bool face = (n == 0 || n == 4 || n == 8 || n == 12 || n == 24 || n == 28);
-  const bool edge = (n >= 16 && n < 24 && n%2 == 0) || (n >= 32 && n < 48 && n%2 == 0);
+// only the first sub-block slot of a face / edge carries the averaging (n = 0,4,8,12,16,18,...)
+__host__ __device__ inline bool avg_face(int n) { return n == 0 || n == 4 || n == 8 || n == 12 || n == 24 || n == 28; }
+__host__ __device__ inline bool avg_edge(int n) { return ((n >= 16 && n < 24) || (n >= 32 && n < 48)) && n%2 == 0; }
+// AverageBoundaryFluxes (flux_correct_fc.cpp:801-1034) of slot n; nflx[nmb][48] from the host (the counting of
+// :470-570 and :676-760 depends on the neighbour table only).  The boxes of different faces / edges are disjoint.
+__device__ __forceinline__ void emf_average(const SGeo &s, const Tab &t, const int *__restrict__ nflx, double *e, int v,
+                                            int m, int n) {
+  if (!slot_has(n, v)) return;
+  const bool face = avg_face(n), edge = avg_edge(n);
   if (!face && !edge) return;
-  Bx b = box_of(t.fc, T_RECV, K_FLXS, n, v);
+  Box b = box_of(t.fc, T_RECV, K_FLXS, n, v);
   if (b.iu < b.il || b.ju < b.jl || b.ku < b.kl) return;
-  double *e = ef.e[v];
   if (edge) {
     const double d = (double)nflx[(size_t)m*48 + n];
     const int cnt = bcount(b);
@@ -752,111 +634,51 @@ k_smr_average_flux_fc(SGeo s, Tab t, const int *__restrict__ nflx, E3 ef) {
   }
 }
 
+// The three steps as kernels of their own (AKMI_SMR_EMF_SPLIT=1): the sum over a (block, component) ...
+__global__ void __launch_bounds__(256)
+k_smr_sum_flux_fc(SGeo s, Tab t, int same_level, const double *__restrict__ buf, E3 ef) {
+  const int v = blockIdx.x%3, m = blockIdx.x/3;
+  __shared__ SlotMeta sm[48];                 // table look-ups of all slots first (see k_smr_unpack_fc)
+  if ((int)threadIdx.x < 48) sm[threadIdx.x] = emf_slot(t, m, threadIdx.x, v, same_level);
+  __syncthreads();
+  emf_sum(s, t, sm, buf, ef.e[v], v, m);
+}
+// ... the zeroing and the average over (block, slot, component)
+__global__ void __launch_bounds__(256)
+k_smr_zero_flux_fc(SGeo s, Tab t, E3 ef) {
+  int m, n, v; wg_slot(t, L_FINER, 3, m, n, v); (void)v;
+  if (n >= 48 || NGID(t, m, n) < 0 || !(NLEV(t, m, n) > t.lev[m]) || !slot_has(n, v)) return;
+  emf_zero(s, box_of(t.fc, T_RECV, K_FLXC, n, v), ef.e[v], v, m);
+}
+__global__ void __launch_bounds__(256)
+k_smr_average_flux_fc(SGeo s, Tab t, const int *__restrict__ nflx, E3 ef) {
+  int m, n, v; wg_slot(t, L_AVG, 3, m, n, v); (void)v;
+  if (n < 48) emf_average(s, t, nflx, ef.e[v], v, m, n);
+}
+
 // RecvAndUnpackFluxFC after the messages are in (flux_correct_fc.cpp:374-1034) for one (MeshBlock, component) per workgroup:
-// the four steps above -- sum of the same-level contributions, zero where finer neighbours contribute, sum of theirs,
+// the steps above -- sum of the same-level contributions, zero where finer neighbours contribute, sum of theirs,
 // average -- touch the edges of block m only and read the buffer, so one workgroup can run them back to back with barriers
 // in between: one launch instead of four (120 blocks of 16^3: 13 + 5 + 13 + 11 us of mostly launch latency).  Same
 // operations on the same operands in the same order per edge as the four kernels.
 __global__ void __launch_bounds__(256)
 k_smr_emf_finish(SGeo s, Tab t, const int *__restrict__ nflx, const double *__restrict__ buf, E3 ef) {
   const int v = blockIdx.x%3, m = blockIdx.x/3;
-  const int ml = t.lev[m];
   double *e = ef.e[v];
-  __shared__ SlotMeta same[48], finer[48];    // receive boxes of the slots (q < 0: the slot contributes nothing)
+  __shared__ SlotMeta same[48], finer[48];
   if ((int)threadIdx.x < 48) {
-    const int n = threadIdx.x;
-    SlotMeta x, y;
-    x.q = -1; x.in = 0; x.b = Bx{0, -1, 0, -1, 0, -1};
-    y = x;
-    if (n < t.nnghbr && NGID(t, m, n) >= 0 && slot_has(n, v)) {
-      const int nl = NLEV(t, m, n);
-      if (nl == ml) {
-        x.q = 0;
-        x.b = box_of(t.fc, T_RECV, K_FLXS, n, v);
-        x.in = (long long)seg_r(t, 3, m, n) + (long long)ndat_of(t, 1, n, T_RECV, 3)*v;
-      } else if (nl > ml) {
-        y.q = 0;
-        y.b = box_of(t.fc, T_RECV, K_FLXC, n, v);
-        y.in = (long long)seg_r(t, 3, m, n) + (long long)ndat_of(t, 1, n, T_RECV, 4)*v;
-      }
-    }
-    same[n] = x; finer[n] = y;
+    same[threadIdx.x] = emf_slot(t, m, threadIdx.x, v, 1);
+    finer[threadIdx.x] = emf_slot(t, m, threadIdx.x, v, 0);
   }
   __syncthreads();
-  auto add = [&](const SlotMeta &sm) {         // SumBoundaryFluxes: the slots one after the other
-    const Bx b = sm.b;
-    const int cnt = bcount(b);
-    const double *in = buf + sm.in;
-    for (int q = threadIdx.x; q < cnt; q += blockDim.x) {
-      int k, j, i;
-      bdecode(b, q, k, j, i);
-      e[e4(s, v, m, k, j, i)] += in[q];
-    }
-  };
-  for (int n = 0; n < t.nnghbr && n < 48; ++n) {
-    if (same[n].q < 0) continue;               // (uniform over the workgroup)
-    add(same[n]);
-    __syncthreads();
-  }
+  emf_sum(s, t, same, buf, e, v, m);
   if (t.multilevel) {
-    for (int n = 0; n < t.nnghbr && n < 48; ++n) {   // ZeroFluxesAtBoundaryWithFiner
-      if (finer[n].q < 0) continue;
-      const Bx b = finer[n].b;
-      const int cnt = bcount(b);
-      for (int q = threadIdx.x; q < cnt; q += blockDim.x) {
-        int k, j, i;
-        bdecode(b, q, k, j, i);
-        e[e4(s, v, m, k, j, i)] = 0.0;
-      }
-    }
+    for (int n = 0; n < t.nnghbr && n < 48; ++n)
+      if (finer[n].q >= 0) emf_zero(s, finer[n].b, e, v, m);
     __syncthreads();
-    for (int n = 0; n < t.nnghbr && n < 48; ++n) {
-      if (finer[n].q < 0) continue;
-      add(finer[n]);
-      __syncthreads();
-    }
+    emf_sum(s, t, finer, buf, e, v, m);
   }
-  // AverageBoundaryFluxes (see k_smr_average_flux_fc): the boxes of different faces / edges are disjoint
-  for (int n = 0; n < t.nnghbr && n < 48; ++n) {               // (1-D: 8 slots, 2-D: 24)
-    if (!slot_has(n, v)) continue;
-    const bool face = (n == 0 || n == 4 || n == 8 || n == 12 || n == 24 || n == 28);
-    const bool edge = (n >= 16 && n < 24 && n%2 == 0) || (n >= 32 && n < 48 && n%2 == 0);
-    if (!face && !edge) continue;
-    Bx b = box_of(t.fc, T_RECV, K_FLXS, n, v);
-    if (b.iu < b.il || b.ju < b.jl || b.ku < b.kl) continue;
-    if (edge) {
-      const double d = (double)nflx[(size_t)m*48 + n];
-      const int cnt = bcount(b);
-      for (int q = threadIdx.x; q < cnt; q += blockDim.x) {
-        int k, j, i;
-        bdecode(b, q, k, j, i);
-        e[e4(s, v, m, k, j, i)] /= d;
-      }
-      continue;
-    }
-    const int nl = NLEV(t, m, n);
-    const int fdir = n < 8 ? 0 : (n < 16 ? 1 : 2);
-    const int tdir = 3 - fdir - v;
-    const bool tact = tdir == 0 ? true : (tdir == 1 ? s.multi_d != 0 : s.three_d != 0);
-    int *lo = tdir == 0 ? &b.il : (tdir == 1 ? &b.jl : &b.kl);
-    int *hi = tdir == 0 ? &b.iu : (tdir == 1 ? &b.ju : &b.ku);
-    if (nl == ml) {
-      if (tact) { *lo += 1; *hi -= 1; }
-    } else if (nl >= ml) {
-      if (!tact) continue;
-      const int mid = *lo + (*hi - *lo + 1)/2;
-      *lo = mid; *hi = mid;
-    } else {
-      continue;
-    }
-    if (*hi < *lo) continue;
-    const int cnt = bcount(b);
-    for (int q = threadIdx.x; q < cnt; q += blockDim.x) {
-      int k, j, i;
-      bdecode(b, q, k, j, i);
-      e[e4(s, v, m, k, j, i)] *= 0.5;
-    }
-  }
+  for (int n = 0; n < t.nnghbr && n < 48; ++n) emf_average(s, t, nflx, e, v, m, n);   // (1-D: 8 slots, 2-D: 24)
 }
 
 // launch over the (block, slot) pairs of work list L (or the full grid without lists), `per` workgroups per pair
@@ -1173,9 +995,7 @@ int akmi_smr_build_lists(const akmi_pack *p, const akmi_smr *t, int *lists, int 
       if (nl == ml && needs[m]) push(L_SAME_NEEDS, m, n);
     }
     // AverageBoundaryFluxes: the first sub-block slot of every face and edge, neighbour or not
-    const bool face = (n == 0 || n == 4 || n == 8 || n == 12 || n == 24 || n == 28);
-    const bool edge = (n >= 16 && n < 24 && n%2 == 0) || (n >= 32 && n < 48 && n%2 == 0);
-    if (face || edge) push(L_AVG, m, n);
+    if (avg_face(n) || avg_edge(n)) push(L_AVG, m, n);
   }
   if (hipMemcpyAsync(lists, out.data(), out.size()*sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess ||
       hipStreamSynchronize(st) != hipSuccess) {

@@ -164,29 +164,58 @@ OPS_MESHES = {
 }
 
 
+P = lambda a: a.ctypes.data_as(C.c_void_p)
+
+
+def _faces(rng, nmb, k, j, i):
+    return [_rand(rng, (nmb, k, j, i + 1)), _rand(rng, (nmb, k, j + 1, i)), _rand(rng, (nmb, k + 1, j, i))]
+
+
+def _dev_faces(nmb, arrs, k, j, i):
+    import torch
+    from athenak_amd.hydro import FaceFld
+    f = FaceFld(nmb, 0, k, j, i, "cuda")
+    for dst, a in zip((f.x1f, f.x2f, f.x3f), arrs):
+        dst.copy_(torch.from_numpy(a))
+    return f
+
+
+def _same(dev, host, what):
+    assert np.array_equal(dev.cpu().numpy(), host), what
+
+
+def _check_emf(pm, smr, L, h, rng):
+    """edge EMFs: sum over same-level owners, zero + sum of finer, average (PackAndSendFluxFC + RecvAndUnpackFluxFC
+    against akref_smr_flux_fc) on random edge fields"""
+    import torch
+    from athenak_amd.hydro import EdgeFld
+    nmb = pm.nmb_total
+    (n3, n2, n1), _ = _shapes(pm, 5)
+    e = [_rand(rng, (nmb, n3 + 1, n2 + 1, n1)), _rand(rng, (nmb, n3 + 1, n2, n1 + 1)), _rand(rng, (nmb, n3, n2 + 1, n1 + 1))]
+    de = EdgeFld(nmb, n3, n2, n1, "cuda")
+    for dst, a in zip((de.x1e, de.x2e, de.x3e), e):
+        dst.copy_(torch.from_numpy(a))
+    smr.PackAndSendFluxFC(de)
+    smr.RecvAndUnpackFluxFC(de)
+    L.akref_smr_flux_fc(h, P(e[0]), P(e[1]), P(e[2]))
+    for q, (x, y) in enumerate(zip((de.x1e, de.x2e, de.x3e), e)):
+        _same(x, y, "emf_exchange e%d" % (q + 1))
+
+
 @pytest.mark.parametrize("mesh", sorted(OPS_MESHES))
 def test_boundary_operators_on_random_data(mesh):
     import torch
-    from athenak_amd.hydro import EdgeFld, FaceFld
+    from athenak_amd.hydro import FaceFld
     nvar = 5
     pm, smr, L, h, keep = _setup(*OPS_MESHES[mesh], nvar=nvar)
     nmb = pm.nmb_total
     (n3, n2, n1), (c3, c2, c1) = _shapes(pm, nvar)
     rng = np.random.default_rng(7)
-    P = lambda a: a.ctypes.data_as(C.c_void_p)
     T = lambda a: torch.from_numpy(a.copy()).cuda()
 
-    def faces(k, j, i):
-        return [_rand(rng, (nmb, k, j, i + 1)), _rand(rng, (nmb, k, j + 1, i)), _rand(rng, (nmb, k + 1, j, i))]
-
-    def dev_faces(arrs, k, j, i):
-        f = FaceFld(nmb, 0, k, j, i, "cuda")
-        for dst, a in zip((f.x1f, f.x2f, f.x3f), arrs):
-            dst.copy_(torch.from_numpy(a))
-        return f
-
-    def same(dev, host, what):
-        assert np.array_equal(dev.cpu().numpy(), host), what
+    faces = lambda k, j, i: _faces(rng, nmb, k, j, i)
+    dev_faces = lambda arrs, k, j, i: _dev_faces(nmb, arrs, k, j, i)
+    same = _same
 
     # --- cell-centred: SendU/RecvU, FillCoarseInBndryCC, ProlongateCC
     u, cu = _rand(rng, (nmb, nvar, n3, n2, n1)), _rand(rng, (nmb, nvar, c3, c2, c1))
@@ -237,17 +266,51 @@ def test_boundary_operators_on_random_data(mesh):
         L.akref_smr_flux_cc(h, P(fl[0]), P(fl[1]), P(fl[2]), fs)
         for q, (x, y) in enumerate(zip((dfl.x1f, dfl.x2f, dfl.x3f), fl)):
             same(x, y, "flux_cc fs=%d dir %d" % (fs, q))
-    # --- edge EMFs: sum over same-level owners, zero + sum of finer, average
-    e = [_rand(rng, (nmb, n3 + 1, n2 + 1, n1)), _rand(rng, (nmb, n3 + 1, n2, n1 + 1)), _rand(rng, (nmb, n3, n2 + 1, n1 + 1))]
-    de = EdgeFld(nmb, n3, n2, n1, "cuda")
-    for dst, a in zip((de.x1e, de.x2e, de.x3e), e):
-        dst.copy_(torch.from_numpy(a))
-    smr.PackAndSendFluxFC(de)
-    smr.RecvAndUnpackFluxFC(de)
-    L.akref_smr_flux_fc(h, P(e[0]), P(e[1]), P(e[2]))
-    for q, (x, y) in enumerate(zip((de.x1e, de.x2e, de.x3e), e)):
-        same(x, y, "emf_exchange e%d" % (q + 1))
+    _check_emf(pm, smr, L, h, rng)
     L.akref_smr_destroy(h)
+
+
+@pytest.mark.parametrize("mesh", sorted(OPS_MESHES))
+def test_boundary_operators_on_random_data_p2c_fine(mesh):
+    """PrimToConsFineBndry (prolong_primitives) on random primitives -- and random fine faces with MHD -- against
+    akref_smr_p2c_fine, the whole conserved array bit for bit: hydro, MHD, and with two passive scalars"""
+    import torch
+    for nvar, mhd in ((5, False), (5, True), (7, True)):
+        pm, smr, L, h, keep = _setup(*OPS_MESHES[mesh], nvar=nvar)
+        nmb = pm.nmb_total
+        (n3, n2, n1), _ = _shapes(pm, nvar)
+        rng = np.random.default_rng(11 + nvar + mhd)
+        w, u = _rand(rng, (nmb, nvar, n3, n2, n1)), _rand(rng, (nmb, nvar, n3, n2, n1))
+        b = _faces(rng, nmb, n3, n2, n1) if mhd else None
+        dw, du = torch.from_numpy(w.copy()).cuda(), torch.from_numpy(u.copy()).cuda()
+        u_before = u.copy()
+        smr.PrimToConsFineBndry(dw, _dev_faces(nmb, b, n3, n2, n1) if mhd else None, du)
+        L.akref_smr_p2c_fine(h, P(w), *((P(x) for x in b) if mhd else (None, None, None)), P(u))
+        assert not np.array_equal(u, u_before)                # the mesh has fine ghost cells next to coarser blocks
+        _same(du, u, "p2c_fine nvar=%d mhd=%d" % (nvar, mhd))
+        L.akref_smr_destroy(h)
+
+
+EMF_SPLIT_SCRIPT = r"""
+import sys
+sys.path.insert(0, %r); sys.path.insert(0, %r)
+import numpy as np
+import test_gpu_smr as t
+pm, smr, L, h, keep = t._setup(*t.OPS_MESHES[sys.argv[1]], nvar=5)
+t._check_emf(pm, smr, L, h, np.random.default_rng(13))
+L.akref_smr_destroy(h)
+print("ok")
+""" % (ROOT, os.path.join(ROOT, "tests"))
+
+
+@pytest.mark.parametrize("mesh", ["3d_3lev_ng4", "2d"])
+def test_boundary_operators_on_random_data_emf_split(mesh):
+    """the EMF block of test_boundary_operators_on_random_data through the four kernels of AKMI_SMR_EMF_SPLIT=1 (the
+    switch is read once per process, hence a child)"""
+    import subprocess
+    r = subprocess.run([sys.executable, "-c", EMF_SPLIT_SCRIPT, mesh], env=dict(os.environ, AKMI_SMR_EMF_SPLIT="1"),
+                       capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0 and "ok" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
 
 
 @pytest.mark.parametrize("mesh", ["3d", "3d_3lev_ng4", "2d"])
