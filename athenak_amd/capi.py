@@ -90,10 +90,15 @@ class MgPlan(C.Structure):
                 ("fmg_ncycle", C.c_int), ("subtract_average", C.c_int), ("show_defect", C.c_int),
                 ("rdx", C.c_double), ("root_dx", C.c_double), ("omega", C.c_double), ("four_pi_G", C.c_double),
                 ("eps", C.c_double), ("vol", C.c_double), ("nghbr", C.c_void_p), ("lloc", C.c_void_p),
-                ("ws", C.c_void_p)]
+                ("ws", C.c_void_p),
+                ("mg_bc", C.c_int), ("periodic", C.c_int*6), ("mporder", C.c_int), ("nodipole", C.c_int),
+                ("auto_mporigin", C.c_int), ("mesh_ext", C.c_double*6), ("mporigin", C.c_double*3),
+                ("mask_radius", C.c_double), ("mask_origin", C.c_double*3), ("xlim", C.c_void_p)]
 
 
 MG_NNORMS = 42                  # AKMI_MG_NNORMS of include/akmi.h
+MGBC = {"none": 0, "zerofixed": 1, "zerograd": 2, "multipole": 3}        # AKMI_MGBC_* of include/akmi.h
+MG_NMPCOEFF = 25                # coefficients of mporder = 4; the origin (x, y, z) follows them in the library's arrays
 
 TURB_NHIST = 11                 # AKMI_TURB_NHIST of include/akmi.h
 TURB_HIST_LABELS = ["Bx", "By", "Bz", "B^2", "B^4", "dB^2", "BdB^2", "|BxJ|^2", "|B.J|^2", "U^2", "dU"]   # turb.cpp:249-259

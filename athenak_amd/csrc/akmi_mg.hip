@@ -11,6 +11,9 @@
 // ascending in j, the planes of a block ascending in k, the blocks ascending in m -- four small launches, each value
 // written once (l_reduce).
 //
+// Physical (non-periodic) faces of the mesh -- mirror and multipole ghosts inside the exchange launch, the multipole
+// moments, the source mask -- are DESIGN section 21; with mg_bc = none the solver runs the periodic kernels alone.
+//
 // akmi_mg_solve enqueues a whole MGGravityDriver::Solve from here through the same launch functions the
 // single-operator entry points use; the host reads defect norms back only where threshold >= 0 asks for them.
 #include <cmath>
@@ -175,6 +178,253 @@ k_exchange(Lv g, const int *__restrict__ nghbr, double *u) {
   const int nb = nghbr ? nghbr[m*27 + (o3 + 1)*9 + (o2 + 1)*3 + (o1 + 1)] : m;
   if (nb < 0 || nb >= g.nmb) return;
   u[at(g, m, k, j, i)] = u[at(g, nb, k - o3*g.nz, j - o2*g.ny, i - o1*g.nx)];
+}
+
+// ---- physical faces: mirror (zerofixed / zerograd) and multipole boundaries, DESIGN section 21 ----------------------
+// CellCenterX, src/coordinates/cell_locations.hpp:35-39
+__device__ __forceinline__ double cell_center_x(int ith, int n, double xmin, double xmax) {
+  const double x = ((double)ith + 0.5)/(double)n;
+  return (x*xmax - x*xmin) - (0.5*xmax - 0.5*xmin) + (0.5*xmin + 0.5*xmax);
+}
+constexpr int MP_NCOEF = 25, MP_ORIGIN = 25, MP_DOUBLES = 28;     // mp[0..24] coefficients, mp[25..27] origin (x, y, z)
+
+// EvalMultipolePhi, multigrid.hpp:680-708
+__device__ __forceinline__ double eval_multipole_phi(double x, double y, double z, const double *mpc, int order) {
+  const double x2 = x*x, y2 = y*y, z2 = z*z;
+  const double xy = x*y, yz = y*z, zx = z*x;
+  const double r2 = x2 + y2 + z2;
+  const double ir2 = 1.0/r2, ir1 = sqrt(ir2);
+  const double ir3 = ir2*ir1, ir5 = ir3*ir2;
+  const double hx2my2 = 0.5*(x2 - y2);
+  double phis = ir1*mpc[0]
+    + ir3*(mpc[1]*y + mpc[2]*z + mpc[3]*x)
+    + ir5*(mpc[4]*xy + mpc[5]*yz + (3.0*z2 - r2)*mpc[6]
+         + mpc[7]*zx + mpc[8]*hx2my2);
+  if (order == 4) {
+    const double ir7 = ir5*ir2, ir9 = ir7*ir2;
+    const double x2mty2 = x2 - 3.0*y2;
+    const double tx2my2 = 3.0*x2 - y2;
+    phis += ir7*(y*tx2my2*mpc[9] + x*x2mty2*mpc[15]
+               + xy*z*mpc[10] + z*hx2my2*mpc[14]
+               + (5.0*z2 - r2)*(y*mpc[11] + x*mpc[13])
+               + z*(z2 - 3.0*r2)*mpc[12])
+         + ir9*(xy*hx2my2*mpc[16]
+               + 0.125*(x2*x2mty2 - y2*tx2my2)*mpc[24]
+               + yz*tx2my2*mpc[17] + zx*x2mty2*mpc[23]
+               + (7.0*z2 - r2)*(xy*mpc[18] + hx2my2*mpc[22])
+               + (7.0*z2 - 3.0*r2)*(yz*mpc[19] + zx*mpc[21])
+               + (35.0*z2*z2 - 30.0*z2*r2 + 3.0*r2*r2)*mpc[20]);
+  }
+  return phis;
+}
+
+struct Bc {
+  int type;              // AKMI_MGBC_*
+  int order;             // mporder
+  int periodic;          // root grid (nghbr == nullptr): bit f set = face f of the mesh (ix1, ox1, ix2, ...) is periodic
+  const double *mp;      // multipole: MP_DOUBLES doubles
+  const double *xlim;    // multipole, block levels: x1min, x1max, x2min, ... of every block
+  double ext[6];         // multipole, root grid: the extents of the mesh
+};
+
+// MultigridBoundaryValues receive + PhysicalBoundary (multigrid_tasks.cpp:129-360) / MGRootBoundary
+// (multigrid_driver.cpp:1835-2026) in one launch.  A direction in which the ghost cell lies beyond a physical face (no
+// face neighbour: table entry < 0; root grid: the face is not periodic) is mirrored, the others take the neighbour's
+// image, and the value is multiplied by -1 per mirrored direction under zerofixed: the composite of the reference's
+// x1, x2, x3 sweeps over the full extent.  Multipole: face ghosts over active cells = 2*phis - interior, edge and
+// corner ghosts that touch a physical face are left alone.  Reads active cells and writes ghost cells only.
+__global__ void __launch_bounds__(TB)
+k_exchange_bc(Lv g, const int *__restrict__ nghbr, Bc b, double *u) {
+  const long long t = tid();
+  if (t >= cells_all(g)) return;
+  int m, k, j, i;
+  all_of(g, t, m, k, j, i);
+  const int n[3] = {g.nx, g.ny, g.nz};
+  const int c[3] = {i, j, k};
+  int o[3], ph[3], nphys = 0, nout = 0;
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    o[d] = (c[d] == 0) ? -1 : (c[d] == n[d] + 1 ? 1 : 0);
+    ph[d] = 0;
+    if (o[d] != 0) {
+      ++nout;
+      const int st = (d == 0) ? 1 : (d == 1 ? 3 : 9);
+      if (nghbr) ph[d] = nghbr[m*27 + 13 + o[d]*st] < 0;
+      else ph[d] = !((b.periodic >> (2*d + (o[d] > 0 ? 1 : 0))) & 1);
+      nphys += ph[d];
+    }
+  }
+  if (nout == 0) return;
+  if (nphys > 0 && b.type == AKMI_MGBC_NONE) return;
+  if (nphys > 0 && b.type == AKMI_MGBC_MULTIPOLE) {
+    if (nout != 1) return;
+    const double *e = nghbr ? b.xlim + 6*(size_t)m : b.ext;
+    double x[3];
+    int s[3];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      const double lo = e[2*d], hi = e[2*d + 1], org = b.mp[MP_ORIGIN + d];
+      if (o[d] != 0) {
+        x[d] = (o[d] < 0 ? lo : hi) - org;
+        s[d] = (o[d] < 0) ? 1 : n[d];
+      } else {
+        const double dxl = (hi - lo)/static_cast<double>(n[d]);
+        x[d] = lo + ((c[d] - 1) + 0.5)*dxl - org;
+        s[d] = c[d];
+      }
+    }
+    const double phis = eval_multipole_phi(x[0], x[1], x[2], b.mp, b.order);
+    u[at(g, m, k, j, i)] = 2.0*phis - u[at(g, m, s[2], s[1], s[0])];
+    return;
+  }
+  int s[3], on[3];
+  double sign = 1.0;
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    if (ph[d]) {
+      on[d] = 0;
+      s[d] = (o[d] < 0) ? 1 : n[d];
+      if (b.type == AKMI_MGBC_ZEROFIXED) sign = -sign;
+    } else {
+      on[d] = o[d];
+      s[d] = c[d] - o[d]*n[d];
+    }
+  }
+  int nb = m;
+  if (nghbr && (on[0] != 0 || on[1] != 0 || on[2] != 0)) nb = nghbr[m*27 + (on[2] + 1)*9 + (on[1] + 1)*3 + (on[0] + 1)];
+  if (nb < 0 || nb >= g.nmb) return;
+  const double v = u[at(g, nb, s[2], s[1], s[0])];
+  u[at(g, m, k, j, i)] = (nphys > 0) ? sign*v : v;
+}
+
+// Multigrid::ApplyMask, multigrid.cpp:360-388: active cells of the finest level
+__global__ void __launch_bounds__(TB)
+k_mask(Lv g, const double *__restrict__ xlim, double mask_r2, double ox, double oy, double oz, double *__restrict__ src) {
+  const long long t = tid();
+  if (t >= cells_act(g)) return;
+  int m, k, j, i;
+  act_of(g, t, m, k, j, i);
+  const double *e = xlim + 6*(size_t)m;
+  const double x = cell_center_x(i - 1, g.nx, e[0], e[1]);
+  const double y = cell_center_x(j - 1, g.ny, e[2], e[3]);
+  const double z = cell_center_x(k - 1, g.nz, e[4], e[5]);
+  const double r2 = (x - ox)*(x - ox) + (y - oy)*(y - oy) + (z - oz)*(z - oz);
+  if (r2 > mask_r2) src[at(g, m, k, j, i)] = 0.0;
+}
+
+// CalculateCenterOfMass (nc = 4, multigrid_driver.cpp:2374-2434) / CalculateMultipoleCoefficients (nc = 9 or 25,
+// :2213-2315): the sums of one row (m, k, j), ascending in i, component c at rows[c*nrows + row]
+template <int NC>
+__global__ void __launch_bounds__(TB)
+k_mp_rows(Lv g, int nodipole, const double *__restrict__ xlim, const double *__restrict__ mpo,
+          const double *__restrict__ src, double *__restrict__ rows) {
+  long long t = tid();
+  const long long nrows = (long long)g.nmb*g.nz*g.ny;
+  if (t >= nrows) return;
+  const long long r = t;
+  const int j = (int)(t % g.ny) + 1; t /= g.ny;
+  const int k = (int)(t % g.nz) + 1;
+  const int m = (int)(t / g.nz);
+  const double *e = xlim + 6*(size_t)m;
+  const double dx1 = (e[1] - e[0])/static_cast<double>(g.nx);
+  const double dx2 = (e[3] - e[2])/static_cast<double>(g.ny);
+  const double dx3 = (e[5] - e[4])/static_cast<double>(g.nz);
+  const double vol = dx1*dx2*dx3;
+  const double *p = src + at(g, m, k, j, 1);
+  double mp[NC];
+#pragma unroll
+  for (int c = 0; c < NC; ++c) mp[c] = 0.0;
+  if constexpr (NC == 4) {
+    const double z = e[4] + ((k - 1) + 0.5)*dx3;
+    const double y = e[2] + ((j - 1) + 0.5)*dx2;
+    for (int ii = 0; ii < g.nx; ++ii) {
+      const double x = e[0] + (ii + 0.5)*dx1;
+      const double s = p[ii]*vol;
+      mp[0] += s;
+      mp[1] += s*y;
+      mp[2] += s*z;
+      mp[3] += s*x;
+    }
+  } else {
+    const double z = e[4] + ((k - 1) + 0.5)*dx3 - mpo[2];
+    const double z2 = z*z;
+    const double y = e[2] + ((j - 1) + 0.5)*dx2 - mpo[1];
+    const double y2 = y*y;
+    const double yz = y*z;
+    for (int ii = 0; ii < g.nx; ++ii) {
+      const double x = e[0] + (ii + 0.5)*dx1 - mpo[0];
+      const double x2 = x*x;
+      const double xy = x*y;
+      const double zx = z*x;
+      const double r2 = x2 + y2 + z2;
+      const double s = p[ii]*vol;
+      mp[0] += s;
+      if (!nodipole) {
+        mp[1] += s*y;
+        mp[2] += s*z;
+        mp[3] += s*x;
+      }
+      const double hx2my2 = 0.5*(x2 - y2);
+      mp[4] += s*xy;
+      mp[5] += s*yz;
+      mp[6] += s*(3.0*z2 - r2);
+      mp[7] += s*zx;
+      mp[8] += s*hx2my2;
+      if constexpr (NC == 25) {
+        const double tx2my2 = 3.0*x2 - y2;
+        const double x2mty2 = x2 - 3.0*y2;
+        const double fz2mr2 = 5.0*z2 - r2;
+        mp[9] += s*y*tx2my2;
+        mp[10] += s*xy*z;
+        mp[11] += s*y*fz2mr2;
+        mp[12] += s*z*(z2 - 3.0*r2);
+        mp[13] += s*x*fz2mr2;
+        mp[14] += s*z*hx2my2;
+        mp[15] += s*x*x2mty2;
+        const double sz2mr2 = 7.0*z2 - r2;
+        const double sz2mtr2 = 7.0*z2 - 3.0*r2;
+        mp[16] += s*xy*hx2my2;
+        mp[17] += s*yz*tx2my2;
+        mp[18] += s*xy*sz2mr2;
+        mp[19] += s*yz*sz2mtr2;
+        mp[20] += s*(35.0*z2*z2 - 30.0*z2*r2 + 3.0*r2*r2);
+        mp[21] += s*zx*sz2mtr2;
+        mp[22] += s*hx2my2*sz2mr2;
+        mp[23] += s*zx*x2mty2;
+        mp[24] += s*0.125*(x2*x2mty2 - y2*tx2my2);
+      }
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < NC; ++c) rows[c*nrows + r] = mp[c];
+}
+
+// the blocks (ascending m) of component c = threadIdx.x, then: nc = 4: the origin 1/m0 * (m3, m1, m2) into
+// mp[MP_ORIGIN..]; otherwise ScaleMultipoleCoefficients (multigrid_driver.cpp:2322-2367) into mp[c]
+__global__ void k_mp_final(int nmb, int nc, const double *__restrict__ in, double *__restrict__ mp) {
+  const int c = threadIdx.x;
+  if (blockIdx.x != 0 || c >= nc) return;
+  double s = 0.0;
+  for (int m = 0; m < nmb; ++m) s += in[(size_t)c*nmb + m];
+  if (nc == 4) {
+    if (c == 0) return;
+    double m0 = 0.0;
+    for (int m = 0; m < nmb; ++m) m0 += in[m];
+    const double im = 1.0/m0;
+    mp[MP_ORIGIN + (c == 3 ? 0 : c)] = im*s;
+    return;
+  }
+  constexpr double c0 = 0.25/M_PI, c1 = 0.25/M_PI, c2 = 0.0625/M_PI, c2a = 0.75/M_PI;
+  constexpr double c30 = 0.0625/M_PI, c31 = 0.0625*1.5/M_PI, c32 = 0.25*15.0/M_PI, c33 = 0.0625*2.5/M_PI;
+  constexpr double c40 = 0.0625*0.0625/M_PI, c41 = 0.0625*2.5/M_PI, c42 = 0.0625*5.0/M_PI, c43 = 0.0625*17.5/M_PI;
+  constexpr double c44 = 0.25*35.0/M_PI;
+  const double scale[MP_NCOEF] = {c0, c1, c1, c1, c2a, c2a, c2, c2a, c2a, c33, c32, c31, c30, c31, c32, c33,
+                                  c44, c43, c42, c41, c40, c41, c42, c43, c44};
+  mp[c] = s*scale[c];
+}
+__global__ void k_mp_set_origin(double x, double y, double z, double *__restrict__ mp) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  mp[MP_ORIGIN] = x; mp[MP_ORIGIN + 1] = y; mp[MP_ORIGIN + 2] = z;
 }
 
 // MultigridDriver::TransferFromBlocksToRoot, multigrid_driver.cpp:479-548: the one cell of every block's coarsest level
@@ -346,6 +596,12 @@ void l_sub_scalar(hipStream_t st, long long n, double *dst, const double *ave) {
 void l_exchange(hipStream_t st, const Lv &g, const int *nghbr, double *u) {
   MG_LAUNCH(k_exchange, cells_all(g), g, nghbr, u);
 }
+void l_exchange_bc(hipStream_t st, const Lv &g, const int *nghbr, const Bc &b, double *u) {
+  MG_LAUNCH(k_exchange_bc, cells_all(g), g, nghbr, b, u);
+}
+void l_mask(hipStream_t st, const Lv &g, const double *xlim, double radius, const double *origin, double *src) {
+  MG_LAUNCH(k_mask, cells_act(g), g, xlim, radius*radius, origin[0], origin[1], origin[2], src);
+}
 // scratch: nmb*nz*ny + nmb*nz + nmb doubles
 long long scratch_doubles(const Lv &g) { return (long long)g.nmb*g.nz*g.ny + (long long)g.nmb*g.nz + g.nmb; }
 void l_reduce(hipStream_t st, const Lv &g, int kind, double dV, double volume, const double *a, double *scratch,
@@ -356,6 +612,30 @@ void l_reduce(hipStream_t st, const Lv &g, int kind, double dV, double volume, c
   MG_LAUNCH(k_sum_axis, (long long)g.nmb, (long long)g.nmb, g.nz, planes, blocks);
   k_sum_final<<<1, 64, 0, st>>>(g.nmb, kind, volume, blocks, out);
   ++g_launches;
+}
+// the sums of nc components in the order of l_reduce; scratch: nc*scratch_doubles(g); mp: MP_DOUBLES doubles
+void l_mp_sums(hipStream_t st, const Lv &g, int nc, int nodipole, const double *xlim, const double *src,
+               double *scratch, double *mp) {
+  const long long nrows = (long long)g.nmb*g.nz*g.ny;
+  double *rows = scratch, *planes = rows + nc*nrows, *blocks = planes + (long long)nc*g.nmb*g.nz;
+  if (nc == 4) MG_LAUNCH(k_mp_rows<4>, nrows, g, 0, xlim, mp + MP_ORIGIN, src, rows);
+  else if (nc == 9) MG_LAUNCH(k_mp_rows<9>, nrows, g, nodipole, xlim, mp + MP_ORIGIN, src, rows);
+  else MG_LAUNCH(k_mp_rows<25>, nrows, g, nodipole, xlim, mp + MP_ORIGIN, src, rows);
+  MG_LAUNCH(k_sum_axis, (long long)nc*g.nmb*g.nz, (long long)nc*g.nmb*g.nz, g.ny, rows, planes);
+  MG_LAUNCH(k_sum_axis, (long long)nc*g.nmb, (long long)nc*g.nmb, g.nz, planes, blocks);
+  k_mp_final<<<1, 64, 0, st>>>(g.nmb, nc, blocks, mp);
+  ++g_launches;
+}
+// CalculateCenterOfMass (auto_origin) or the origin of the deck, then CalculateMultipoleCoefficients with
+// ScaleMultipoleCoefficients: 8 launches with auto_origin, 5 without
+void l_multipole(hipStream_t st, const Lv &g, int order, int nodipole, int auto_origin, const double *origin,
+                 const double *xlim, const double *src, double *scratch, double *mp) {
+  if (auto_origin) l_mp_sums(st, g, 4, 0, xlim, src, scratch, mp);
+  else {
+    k_mp_set_origin<<<1, 64, 0, st>>>(origin[0], origin[1], origin[2], mp);
+    ++g_launches;
+  }
+  l_mp_sums(st, g, order == 4 ? 25 : 9, nodipole, xlim, src, scratch, mp);
 }
 // Multigrid::CalculateAverage, multigrid.cpp:763-818: dV of the level, the volume from nx1 of the FINEST level (len)
 void l_average(hipStream_t st, const Lv &g, double dx, double len, const double *a, double *scratch, double *out) {
@@ -369,6 +649,14 @@ struct Layout {
   int nmbl, nrl;
   long long boff[24], roff[24], bsz[24], rsz[24], scratch, scalars, total;
 };
+bool bc_ok(int type, int order, const void *geometry, const char *who) {
+  if (type < AKMI_MGBC_NONE || type > AKMI_MGBC_MULTIPOLE) { set_error("%s: unknown boundary type %d", who, type); return false; }
+  if (type == AKMI_MGBC_MULTIPOLE && ((order != 2 && order != 4) || !geometry)) {
+    set_error("%s: multipole boundaries need mporder 2 or 4 (%d) and the extents", who, order);
+    return false;
+  }
+  return true;
+}
 bool plan_ok(const akmi_mg_plan *p, const char *who) {
   if (!p) { set_error("%s: null plan", who); return false; }
   if (p->nmb < 1 || p->nxb < 1 || (p->nxb & (p->nxb - 1)) || p->nrx1 < 1 || p->nrx2 < 1 || p->nrx3 < 1) {
@@ -405,10 +693,12 @@ Layout make_layout(const akmi_mg_plan *p) {
   for (int l = 0; l < L.nmbl; ++l) { L.bsz[l] = cells_all(blk_lv(p, l)); L.boff[l] = o; o += 4*L.bsz[l]; }
   for (int l = 0; l < L.nrl; ++l) { L.rsz[l] = cells_all(root_lv(p, l)); L.roff[l] = o; o += 4*L.rsz[l]; }
   L.scratch = o;
-  const long long a = scratch_doubles(blk_lv(p, L.nmbl - 1)), b = scratch_doubles(root_lv(p, L.nrl - 1));
+  long long a = scratch_doubles(blk_lv(p, L.nmbl - 1));
+  const long long b = scratch_doubles(root_lv(p, L.nrl - 1));
+  if (p->mg_bc == AKMI_MGBC_MULTIPOLE) a *= MP_NCOEF;          // the moment sums, l_mp_sums
   o += (a > b ? a : b);
   L.scalars = o;
-  o += 64;
+  o += 64 + MP_DOUBLES;          // average, norms; multipole coefficients and origin
   L.total = o;
   return L;
 }
@@ -430,8 +720,22 @@ struct Solver {
   double rdx(int rl) const { return p->root_dx*static_cast<double>(1 << (p->nrootlevel - 1 - rl)); }
   int bl_of(int lev) const { return lev - nrl + 1; }
 
-  void bex(int bl) { l_exchange(st, blk_lv(p, bl), p->nghbr, B(bl, U)); }
-  void rbnd(int rl) { l_exchange(st, root_lv(p, rl), nullptr, R(rl, U)); }
+  double *mp() const { return ws + L.scalars + 64; }
+  Bc bc() const {
+    Bc b{};
+    b.type = p->mg_bc; b.order = p->mporder; b.mp = mp(); b.xlim = p->xlim;
+    for (int f = 0; f < 6; ++f) { b.periodic |= (p->periodic[f] ? 1 : 0) << f; b.ext[f] = p->mesh_ext[f]; }
+    return b;
+  }
+  // mg_bc = none: the periodic exchange; otherwise the same launch also fills the ghosts beyond physical faces
+  void bex(int bl) {
+    if (p->mg_bc == AKMI_MGBC_NONE) l_exchange(st, blk_lv(p, bl), p->nghbr, B(bl, U));
+    else l_exchange_bc(st, blk_lv(p, bl), p->nghbr, bc(), B(bl, U));
+  }
+  void rbnd(int rl) {
+    if (p->mg_bc == AKMI_MGBC_NONE) l_exchange(st, root_lv(p, rl), nullptr, R(rl, U));
+    else l_exchange_bc(st, root_lv(p, rl), nullptr, bc(), R(rl, U));
+  }
   void bsmooth(int bl, int color) { l_smooth(st, blk_lv(p, bl), bdx(bl), p->omega, color, coffset, B(bl, U), B(bl, SRC)); }
   void rsmooth(int rl, int color) { l_smooth(st, root_lv(p, rl), rdx(rl), p->omega, color, coffset, R(rl, U), R(rl, SRC)); }
 
@@ -729,6 +1033,53 @@ int akmi_mg_root_boundary(int nz, int ny, int nx, double *u, void *stream) {
   return AKMI_COMPLETE;
 }
 
+int akmi_mg_exchange_bc(int nmb, int nz, int ny, int nx, const int *nghbr, int bc_type, int mporder, const double *mp,
+                        const double *xlim, double *u, void *stream) {
+  MG_LV("mg_exchange_bc");
+  if (!nghbr || !u) { set_error("mg_exchange_bc: null argument"); return AKMI_FAIL; }
+  if (!bc_ok(bc_type, mporder, (mp && xlim) ? xlim : nullptr, "mg_exchange_bc")) return AKMI_FAIL;
+  Bc b{};
+  b.type = bc_type; b.order = mporder; b.mp = mp; b.xlim = xlim;
+  l_exchange_bc(st, g, nghbr, b, u);
+  AKMI_CHECK_LAUNCH("mg_exchange_bc");
+  return AKMI_COMPLETE;
+}
+
+int akmi_mg_root_boundary_bc(int nz, int ny, int nx, int bc_type, const int periodic[6], int mporder, const double *mp,
+                             const double mesh_ext[6], double *u, void *stream) {
+  const int nmb = 1;
+  MG_LV("mg_root_boundary_bc");
+  if (!periodic || !u) { set_error("mg_root_boundary_bc: null argument"); return AKMI_FAIL; }
+  if (!bc_ok(bc_type, mporder, (mp && mesh_ext) ? mesh_ext : nullptr, "mg_root_boundary_bc")) return AKMI_FAIL;
+  Bc b{};
+  b.type = bc_type; b.order = mporder; b.mp = mp;
+  for (int f = 0; f < 6; ++f) { b.periodic |= (periodic[f] ? 1 : 0) << f; b.ext[f] = mesh_ext ? mesh_ext[f] : 0.0; }
+  l_exchange_bc(st, g, nullptr, b, u);
+  AKMI_CHECK_LAUNCH("mg_root_boundary_bc");
+  return AKMI_COMPLETE;
+}
+
+int akmi_mg_multipole_moments(int nmb, int nz, int ny, int nx, int mporder, int nodipole, int auto_origin,
+                              const double *xlim, const double *src, double *scratch, double *mp, void *stream) {
+  MG_LV("mg_multipole_moments");
+  if (!src || !scratch || !mp) { set_error("mg_multipole_moments: null argument"); return AKMI_FAIL; }
+  if (!bc_ok(AKMI_MGBC_MULTIPOLE, mporder, xlim, "mg_multipole_moments")) return AKMI_FAIL;
+  if (auto_origin) l_mp_sums(st, g, 4, 0, xlim, src, scratch, mp);
+  l_mp_sums(st, g, mporder == 4 ? 25 : 9, nodipole, xlim, src, scratch, mp);
+  AKMI_CHECK_LAUNCH("mg_multipole_moments");
+  return AKMI_COMPLETE;
+}
+
+int akmi_mg_mask(int nmb, int nz, int ny, int nx, const double *xlim, double mask_radius, double ox, double oy, double oz,
+                 double *src, void *stream) {
+  MG_LV("mg_mask");
+  if (!xlim || !src) { set_error("mg_mask: null argument"); return AKMI_FAIL; }
+  const double origin[3] = {ox, oy, oz};
+  if (mask_radius > 0.0) l_mask(st, g, xlim, mask_radius, origin, src);
+  AKMI_CHECK_LAUNCH("mg_mask");
+  return AKMI_COMPLETE;
+}
+
 int akmi_mg_blocks_to_root(int nmb, int nz, int ny, int nx, const int *lloc, int initflag, const double *bsrc,
                            const double *bu, double *rsrc, double *ru, void *stream) {
   if (nmb < 1 || nz < 1 || ny < 1 || nx < 1) { set_error("mg_blocks_to_root: bad sizes"); return AKMI_FAIL; }
@@ -781,6 +1132,11 @@ long long akmi_mg_level_offset(const akmi_mg_plan *plan, int is_root, int level,
   return is_root ? L.roff[level] + which*L.rsz[level] : L.boff[level] + which*L.bsz[level];
 }
 
+long long akmi_mg_multipole_offset(const akmi_mg_plan *plan) {
+  if (!plan_ok(plan, "mg_multipole_offset")) return -1;
+  return make_layout(plan).scalars + 64;
+}
+
 long long akmi_mg_launch_count(int reset) {
   const long long n = g_launches;
   if (reset) g_launches = 0;
@@ -798,6 +1154,8 @@ int akmi_mg_solve(const akmi_mg_plan *plan, const double *u0, double *phi, int *
     set_error("mg_solve: neither threshold nor niteration is set");
     return AKMI_FAIL;
   }
+  if (!bc_ok(plan->mg_bc, plan->mporder, plan->xlim, "mg_solve")) return AKMI_FAIL;
+  if (plan->mask_radius > 0.0 && !plan->xlim) { set_error("mg_solve: mask_radius > 0 needs xlim"); return AKMI_FAIL; }
   Solver s;
   s.p = plan;
   s.st = (hipStream_t)stream;
@@ -815,8 +1173,12 @@ int akmi_mg_solve(const akmi_mg_plan *plan, const double *u0, double *phi, int *
   // MGGravityDriver::Solve, mg_gravity.cpp:177-245
   MG_LAUNCH(k_load<0>, cells_all(gf), gf, plan->ng, plan->nvar, -plan->four_pi_G, s.B(fb, SRC),
             const_cast<double *>(u0));
+  if (plan->mask_radius > 0.0) l_mask(st, gf, plan->xlim, plan->mask_radius, plan->mask_origin, s.B(fb, SRC));
   if (!plan->full_multigrid) MG_LAUNCH(k_load<1>, cells_act(gf), gf, plan->ng, 1, 1.0, s.B(fb, U), phi);
   if (plan->subtract_average) s.sub_avg_blocks(SRC);          // SetupMultigrid
+  if (plan->mg_bc == AKMI_MGBC_MULTIPOLE)
+    l_multipole(st, gf, plan->mporder, plan->nodipole, plan->auto_mporigin, plan->mporigin, plan->xlim, s.B(fb, SRC),
+                s.scratch(), s.mp());
   s.cl = s.ntotal - 1;
   s.fmglevel = s.cl;
 

@@ -1,8 +1,9 @@
 """Gravity / MGGravityDriver -- self-gravity by a multigrid Poisson solver, <gravity>
 (src/gravity/gravity.cpp, mg_gravity.cpp:39-245; src/multigrid/multigrid.cpp, multigrid_driver.cpp, multigrid_tasks.cpp).
 
-On this path: one rank, a uniform 3-D mesh with six periodic faces, cubic MeshBlocks with a power-of-two edge, cubic
-cells, mg_nghost = 1.  Everything else stops in gravity_deck_checks with the name of the parameter.
+On this path: one rank, a uniform 3-D mesh, cubic MeshBlocks with a power-of-two edge, cubic cells, mg_nghost = 1.  The
+faces of the mesh are periodic or, with <gravity>/mg_bc = zerofixed | zerograd | multipole written in the deck, physical
+(mg_gravity.cpp:66-126).  Everything else stops in gravity_deck_checks with the name of the parameter.
 
 The level structure is the reference's: the MeshBlock levels (edge n, n/2, ... 1) on top of the root-grid levels (the
 grid of MeshBlocks, halved while all three extents stay even); SetupMultigrid, SolveFMG / SolveFMGCoarser /
@@ -65,14 +66,32 @@ def gravity_deck_checks(pin, nranks=1, restart=False):
     for blk in list(pin.blocks):
         if blk.startswith("output") and pin.GetString(blk, "file_type") == "rst":
             _fatal("<gravity> with rst outputs (<%s>/file_type = rst) is not on this path" % blk)
-    for name in ("ix1_bc", "ox1_bc", "ix2_bc", "ox2_bc", "ix3_bc", "ox3_bc"):
-        v = pin.GetOrAddString("mesh", name, "periodic")
-        if v != "periodic":
-            _fatal("<gravity> needs periodic faces on this path: <mesh>/%s = %s" % (name, v))
-    if pin.GetOrAddString(g, "mg_bc", "none") != "none":
-        _fatal("<gravity>/mg_bc = %s is not on this path (none: periodic)" % pin.GetString(g, "mg_bc"))
-    if pin.GetOrAddReal(g, "mask_radius", -1.0) > 0.0:
-        _fatal("<gravity>/mask_radius > 0 is not on this path")
+    faces = [(name, pin.GetOrAddString("mesh", name, "periodic"))
+             for name in ("ix1_bc", "ox1_bc", "ix2_bc", "ox2_bc", "ix3_bc", "ox3_bc")]
+    physical = [(name, v) for name, v in faces if v != "periodic"]
+    mg_bc = pin.GetOrAddString(g, "mg_bc", "none")
+    if physical and mg_bc == "none":
+        # (the reference would silently take zerofixed; here the deck has to say which)
+        _fatal("<gravity> needs periodic faces on this path unless <gravity>/mg_bc = zerofixed | zerograd | multipole "
+               "says what the Poisson solver does at the others: <mesh>/%s = %s" % physical[0])
+    if mg_bc != "none" and mg_bc not in capi.MGBC:
+        _fatal("in MGGravityDriver\nUnknown mg_bc type: %s" % mg_bc)
+    if mg_bc != "none" and not physical:
+        _fatal("<gravity>/mg_bc = %s on a mesh with six periodic faces is not on this path (it would have no effect: "
+               "none)" % mg_bc)
+    if pin.GetOrAddReal(g, "mask_radius", -1.0) > 0.0 and not physical:
+        _fatal("<gravity>/mask_radius > 0 on a strictly periodic mesh is not on this path")
+    if mg_bc == "multipole":
+        # the reference's own fatal errors, mg_gravity.cpp:99-117
+        if pin.GetOrAddInteger(g, "mporder", 4) not in (2, 4):
+            _fatal("in MGGravityDriver\nmporder must be 2 (quadrupole) or 4 (hexadecapole).")
+        if pin.GetOrAddBoolean(g, "auto_mporigin", True):
+            if pin.GetOrAddBoolean(g, "nodipole", False):
+                _fatal("in MGGravityDriver\nauto_mporigin and nodipole cannot be used together.")
+        else:
+            for d in (1, 2, 3):
+                if not pin.DoesParameterExist(g, "mporigin_x%d" % d):
+                    _fatal("Parameter name 'mporigin_x%d' not found in block 'gravity'" % d)
     if pin.GetOrAddInteger(g, "mg_nghost", 1) != 1:
         _fatal("<gravity>/mg_nghost = %d is not on this path (1)" % pin.GetInteger(g, "mg_nghost"))
     if pin.GetOrAddBoolean(g, "root_on_host", False):
@@ -118,8 +137,21 @@ class MGGravityDriver:
         self.mg_verbose_ = pin.GetOrAddInteger(g, "mg_verbose", 0)
         self.fsubtract_average_ = pin.GetOrAddBoolean(g, "subtract_average", True)
         pm = ppack.pmesh
+        # mg_gravity.cpp:66-126: one type for every non-periodic face, the multipole settings, the mask
+        self.mg_bc_ = pin.GetOrAddString(g, "mg_bc", "none")
+        self.periodic_ = [int(b == capi.BC["periodic"]) for b in pm.mesh_bcs[:6]]
         if not pm.strictly_periodic:
             self.fsubtract_average_ = False
+        self.mporder_, self.autompo_, self.nodipole_, self.mpo_ = -1, True, False, [0.0, 0.0, 0.0]
+        if self.mg_bc_ == "multipole":
+            self.mporder_ = pin.GetOrAddInteger(g, "mporder", 4)
+            self.autompo_ = pin.GetOrAddBoolean(g, "auto_mporigin", True)
+            self.nodipole_ = pin.GetOrAddBoolean(g, "nodipole", False)
+            if not self.autompo_:
+                self.mpo_ = [pin.GetReal(g, "mporigin_x%d" % d) for d in (1, 2, 3)]
+            self.fsubtract_average_ = False
+        self.mask_radius_ = pin.GetOrAddReal(g, "mask_radius", -1.0)
+        self.mask_origin_ = [pin.GetOrAddReal(g, "mask_origin_x%d" % d, 0.0) for d in (1, 2, 3)]
         ind, ms = pm.mb_indcs, pm.mesh_size
         self.nrbx = (pm.nmb_rootx1, pm.nmb_rootx2, pm.nmb_rootx3)
         self.nrootlevel_, self.nmblevel_, self.ntotallevel_, self.ni_ = level_counts(
@@ -133,6 +165,9 @@ class MGGravityDriver:
         lloc = np.array([tuple(pm.lloc_eachmb[int(gid)])[:3] for gid in ppack.pmb.mb_gid], dtype=np.int32)
         self.lloc_dev = torch.from_numpy(lloc.reshape(-1).copy()).to(device)
         self.nghbr_dev = torch.from_numpy(np.ascontiguousarray(ppack.pmb.nghbr_gid, dtype=np.int32).reshape(-1)).to(device)
+        xlim = np.array([[s.x1min, s.x1max, s.x2min, s.x2max, s.x3min, s.x3max] for s in ppack.pmb.mb_size])
+        self.xlim_dev = torch.from_numpy(xlim.reshape(-1).copy()).to(device)
+        self.mesh_ext_ = [ms.x1min, ms.x1max, ms.x2min, ms.x2max, ms.x3min, ms.x3max]
         self.L = capi.lib()
         self.plan = capi.MgPlan()
         self.ws = None
@@ -156,6 +191,11 @@ class MGGravityDriver:
         p.rdx, p.root_dx, p.omega = self.rdx_, self.root_rdx_, self.omega_
         p.four_pi_G, p.eps, p.vol = self.four_pi_G_, self.eps_, self.vol_
         p.nghbr, p.lloc = self.nghbr_dev.data_ptr(), self.lloc_dev.data_ptr()
+        p.mg_bc = capi.MGBC[self.mg_bc_]
+        p.periodic[:], p.mesh_ext[:] = self.periodic_, self.mesh_ext_
+        p.mporder, p.nodipole, p.auto_mporigin = max(self.mporder_, 0), int(self.nodipole_), int(self.autompo_)
+        p.mporigin[:], p.mask_radius, p.mask_origin[:] = self.mpo_, self.mask_radius_, self.mask_origin_
+        p.xlim = self.xlim_dev.data_ptr()
         if self.ws is None:
             n = int(self.L.akmi_mg_workspace_doubles(p))
             if n < 0:
@@ -175,6 +215,23 @@ class MGGravityDriver:
             e = (self.plan.nxb >> s) + 2
             sh = (self.nmb, 1, e, e, e)
         return self.ws[off:off + int(np.prod(sh))].view(sh)
+
+    def _multipole(self):
+        """the 28 doubles the last Solve left in the workspace: 25 scaled coefficients, the origin"""
+        if self.mg_bc_ != "multipole" or self.ws is None:
+            raise RuntimeError("### FATAL ERROR the multipole coefficients need <gravity>/mg_bc = multipole and a Solve")
+        off = int(self.L.akmi_mg_multipole_offset(self.plan))
+        if off < 0:
+            raise capi.AkmiError("mg_multipole_offset: %s" % self.L.akmi_last_error().decode())
+        return self.ws[off:off + capi.MG_NMPCOEFF + 3].cpu().numpy()
+
+    def mpcoeff(self):
+        """mpcoeff_ after ScaleMultipoleCoefficients: 9 (mporder = 2) or 25 numbers; read back when asked for only"""
+        return self._multipole()[:9 if self.mporder_ == 2 else capi.MG_NMPCOEFF].copy()
+
+    def mporigin(self):
+        """mpo_: the centre of mass under auto_mporigin, the deck's origin otherwise"""
+        return self._multipole()[capi.MG_NMPCOEFF:].copy()
 
     def Solve(self, stage=0, pdriver=None):
         """MGGravityDriver::Solve, mg_gravity.cpp:177-245"""

@@ -96,6 +96,15 @@ class Simulation:
         """pgen_name = gravity: the frequency / growth rate its final function measured (None before it has run)"""
         return getattr(self.pmesh.pgen, "omega_measured", None)
 
+    def binary_gravity_errors(self):
+        """pgen_name = binary_gravity: (potential L2, acceleration L2, max potential error, max acceleration error) of
+        the present potential against the analytic two-sphere solution, as the final function prints them"""
+        pgen = self.pmesh.pgen
+        if getattr(pgen, "pgen_name", None) != "binary_gravity":
+            raise RuntimeError("### FATAL ERROR binary_gravity_errors needs <problem>/pgen_name = binary_gravity")
+        pgen.BinaryGravityErrors()
+        return pgen.binary_errors
+
     @property
     def omega_analytical(self):
         return getattr(self.pmesh.pgen, "omega_analytical", None)

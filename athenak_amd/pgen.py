@@ -199,7 +199,8 @@ class ProblemGenerator:
         table = {"linear_wave": self.LinearWave, "shock_tube": self.ShockTube,
                  "orszag_tang": self.OrszagTang, "blast": self.UserProblem, "diffusion": self.Diffusion,
                  "cpaw": self.AlfvenWave, "turb": self.Turb, "rt": self.RayleighTaylor, "cshock": self.CShock,
-                 "gravity": self.SelfGravity, "shwave": self.Shwave}
+                 "gravity": self.SelfGravity, "shwave": self.Shwave,
+                 "binary_gravity": self.BinaryGravity}
         self.user_hist_func = None       # (labels, sums) of the user history file; enrolled by the problem function
         # user-defined boundary conditions (pgen.cpp:57-62): enrolled by the problem function
         self.user_bcs = any(b == capi.BC["user"] for b in pmesh.mesh_bcs)
@@ -1199,6 +1200,138 @@ class ProblemGenerator:
         print("Jeans wave growth (A/amp)  : %.16e" % (A_sin/q["amp"]))
         print("Jeans wave omega measured  : %.16e" % omega_measured)
         print("Jeans wave omega analytical: %.16e" % q["omega"])
+        print("=====================================================")
+        return None
+
+    # ---- two uniform spheres, src/pgen/tests/binary_gravity.cpp -----------------------------
+    def _binary_params(self, pin):
+        q = {k: pin.GetOrAddReal("problem", k, v) for k, v in (
+            ("x1", 6.0/1024.0), ("y1", 0.0), ("z1", 0.0), ("x2", -12.0/1024.0), ("y2", 0.0), ("z2", 0.0),
+            ("radius", 6.0/1024.0), ("m1", 2.0), ("m2", 1.0))}
+        r = q["radius"]
+        q["den1"] = q["m1"]/((4.0*math.pi/3.0)*r*r*r)
+        q["den2"] = q["m2"]/((4.0*math.pi/3.0)*r*r*r)
+        return q
+
+    def BinaryGravity(self, pin, restart):
+        """pgen_name = binary_gravity: two uniform-density spheres of masses m1, m2 and one radius, at rest (the test
+        of the Poisson solver against the analytic two-sphere potential).  Cells within 0.6*sqrt(3)*dx of a surface
+        are sub-sampled 10^3; the density is rescaled so that the total mass is m1 + m2."""
+        self.pgen_final_func = self.BinaryGravityErrors
+        self.binary_errors = None
+        if restart:
+            return
+        pm = self.pmy_mesh_
+        pk = pm.pmb_pack
+        four_pi_G = pin.GetOrAddReal("problem", "four_pi_G", 1.0)
+        pin.SetReal("gravity", "four_pi_G", four_pi_G)
+        if pk.pgrav is not None:
+            pk.pgrav.four_pi_G = four_pi_G
+            pk.pgrav.pmgd.SetFourPiG(four_pi_G)
+        q = self._binary_params(pin)
+        r = q["radius"]
+        floor_den = 1.0e-300
+        phys = self._phys()
+        is_ideal = phys.peos.eos_data.is_ideal
+        n3, n2, n1 = pm.mb_indcs.ncells
+        nmb = pk.nmb_thispack
+        ks, js, is_ = self._active()
+        u = np.zeros((nmb, phys.nvars, n3, n2, n1))
+        total_mass = 0.0
+        for m in range(nmb):
+            x1v, x2v, x3v, x1f, x2f, x3f, sz = self._coords(m)
+            dx = sz.dx1
+            dd, dv, dr = 0.1*dx, 1.0e-3, 0.6*1.7320508075688772*dx
+            Z, Y, X = np.meshgrid(x3v, x2v, x1v, indexing="ij")
+            ZF, YF, XF = np.meshgrid(x3f[:-1], x2f[:-1], x1f[:-1], indexing="ij")
+            sub = (np.arange(10) + 0.5)*dd
+            rho = np.full(X.shape, floor_den)
+            for n, (cx, cy, cz, den) in enumerate(((q["x1"], q["y1"], q["z1"], q["den1"]),
+                                                   (q["x2"], q["y2"], q["z2"], q["den2"]))):
+                rc = np.sqrt((X - cx)**2 + (Y - cy)**2 + (Z - cz)**2)
+                rho[rc < r - dr] = den
+                for k, j, i in zip(*np.nonzero((rc < r + dr) & ~(rc < r - dr))):
+                    zz = (ZF[k, j, i] + sub)[:, None, None]
+                    yy = (YF[k, j, i] + sub)[None, :, None]
+                    xx = (XF[k, j, i] + sub)[None, None, :]
+                    n_in = int(np.count_nonzero(np.sqrt((xx - cx)**2 + (yy - cy)**2 + (zz - cz)**2) < r))
+                    if n == 0:
+                        rho[k, j, i] = floor_den + dv*den*float(n_in)
+                    else:
+                        rho[k, j, i] += dv*den*float(n_in)
+            u[m, IDN][ks, js, is_] = rho
+            if is_ideal:
+                u[m, IEN][ks, js, is_] = rho
+            total_mass += float(np.sum(rho*(sz.dx1*sz.dx2*sz.dx3)))
+        msum = q["m1"] + q["m2"]
+        fac = msum/total_mass if total_mass > 0.0 else 1.0
+        if total_mass < msum*0.7 or total_mass > msum*1.3:
+            print("binary_gravity: total mass %g far from m1+m2=%g; resolution may be too low." % (total_mass, msum))
+        u[:, IDN] *= fac
+        if is_ideal:
+            u[:, IEN] *= fac
+        self._upload_cc(phys.u0, u)
+        if pk.pmhd is not None:
+            b0_val = pin.GetOrAddReal("problem", "b0", 0.0)
+            _, bf = self._alloc_host()
+            bf[0][:, ks, js, is_.start:is_.stop + 1] = b0_val
+            self._upload_cc(phys.b0.x1f, bf[0])
+            self._upload_cc(phys.b0.x2f, bf[1])
+            self._upload_cc(phys.b0.x3f, bf[2])
+
+    def BinaryGravityErrors(self):
+        """binary_gravity.cpp:240-383: relative errors of the potential and of its centred-difference acceleration
+        against the analytic two-sphere solution: (potential L2, acceleration L2, max potential, max acceleration)"""
+        pm = self.pmy_mesh_
+        pk = pm.pmb_pack
+        if pk.pgrav is None:
+            return None
+        pin = self.pin
+        G = pin.GetOrAddReal("gravity", "four_pi_G", 1.0)/(4.0*math.pi)
+        q = self._binary_params(pin)
+        rad = q["radius"]
+        ks, js, is_ = self._active()
+        phi = pk.pgrav.phi[:, 0].cpu().numpy()
+
+        def sh(dk, dj, di):
+            return (slice(ks.start + dk, ks.stop + dk), slice(js.start + dj, js.stop + dj),
+                    slice(is_.start + di, is_.stop + di))
+        pot_l1 = acc_l1 = pot_max = acc_max = 0.0
+        for m in range(pk.nmb_thispack):
+            x1v, x2v, x3v = self._coords(m)[:3]
+            sz = pk.pmb.mb_size[m]
+            vol = sz.dx1*sz.dx2*sz.dx3
+            Z, Y, X = np.meshgrid(x3v, x2v, x1v, indexing="ij")
+            pot0 = ax0 = ay0 = az0 = 0.0
+            for cx, cy, cz, mass, den in ((q["x1"], q["y1"], q["z1"], q["m1"], q["den1"]),
+                                          (q["x2"], q["y2"], q["z2"], q["m2"], q["den2"])):
+                rc = np.sqrt((X - cx)**2 + (Y - cy)**2 + (Z - cz)**2)
+                out = rc > rad
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    pp = np.where(out, -G*mass/rc, -G*math.pi*2.0/3.0*den*(3.0*rad*rad - rc*rc))
+                    f = np.where(out, -G*mass/(rc*rc*rc), -G*math.pi*4.0/3.0*den)
+                pot0 = pot0 + pp
+                ax0, ay0, az0 = ax0 + f*(X - cx), ay0 + f*(Y - cy), az0 + f*(Z - cz)
+            p = phi[m]
+            ax_n = -(p[sh(0, 0, 1)] - p[sh(0, 0, -1)])/(2.0*sz.dx1)
+            ay_n = -(p[sh(0, 1, 0)] - p[sh(0, -1, 0)])/(2.0*sz.dx2)
+            az_n = -(p[sh(1, 0, 0)] - p[sh(-1, 0, 0)])/(2.0*sz.dx3)
+            perr = np.abs((pot0 - p[sh(0, 0, 0)])/pot0)
+            den2 = ax0**2 + ay0**2 + az0**2
+            with np.errstate(divide="ignore", invalid="ignore"):
+                aerr = np.where(den2 > 0.0, np.sqrt(((ax_n - ax0)**2 + (ay_n - ay0)**2 + (az_n - az0)**2)/den2), 0.0)
+            pot_l1 += float(np.sum(perr*vol))
+            acc_l1 += float(np.sum(aerr*vol))
+            pot_max, acc_max = max(pot_max, float(perr.max())), max(acc_max, float(aerr.max()))
+        ms = pm.mesh_size
+        tvol = (ms.x1max - ms.x1min)*(ms.x2max - ms.x2min)*(ms.x3max - ms.x3min)
+        pot_l2, acc_l2 = math.sqrt(pot_l1/tvol), math.sqrt(acc_l1/tvol)
+        self.binary_errors = (pot_l2, acc_l2, pot_max, acc_max)
+        print("=====================================================")
+        print("Potential    L2       : %.16e" % pot_l2)
+        print("Acceleration L2       : %.16e" % acc_l2)
+        print("Max Potential Error    : %.16e" % pot_max)
+        print("Max Acceleration Error : %.16e" % acc_max)
         print("=====================================================")
         return None
 

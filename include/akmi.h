@@ -1046,6 +1046,38 @@ int akmi_mg_defect_norm(int nmb, int nz, int ny, int nx, double vol, const doubl
  * neighbour everywhere (multigrid_driver.cpp:1835-1930). */
 int akmi_mg_exchange(int nmb, int nz, int ny, int nx, const int *nghbr, double *u, void *stream);
 int akmi_mg_root_boundary(int nz, int ny, int nx, double *u, void *stream);
+/* Boundary types of the non-periodic faces of the mesh, <gravity>/mg_bc */
+#define AKMI_MGBC_NONE 0
+#define AKMI_MGBC_ZEROFIXED 1
+#define AKMI_MGBC_ZEROGRAD 2
+#define AKMI_MGBC_MULTIPOLE 3
+/* akmi_mg_exchange plus MultigridDriver::PhysicalBoundary (multigrid_tasks.cpp:129-360) in the same launch.  A block
+ * has a physical face where the FACE entry of its neighbour table is < 0.  zerofixed / zerograd: a ghost cell is
+ * mirrored in every direction in which it lies beyond a physical face, takes the neighbour's image in the others, and
+ * is multiplied by -1 per mirrored direction under zerofixed (the composite of the reference's x1, x2, x3 sweeps over
+ * the full extent).  multipole: a face ghost over active cells = 2*phis - interior, phis = EvalMultipolePhi
+ * (multigrid.hpp:680-708) at the face and the cell centres of THIS level, from the block extents xlim (device,
+ * nmb*6: x1min, x1max, x2min, ...) and mp (device, 28 doubles: 25 scaled coefficients, then the origin x, y, z); edge
+ * and corner ghosts that touch a physical face are left alone.  bc_type none: physical-face ghosts are left alone.
+ * mp and xlim may be NULL for the mirror types.  Reads active cells, writes ghost cells. */
+int akmi_mg_exchange_bc(int nmb, int nz, int ny, int nx, const int *nghbr, int bc_type, int mporder, const double *mp,
+                        const double *xlim, double *u, void *stream);
+/* MGRootBoundary (multigrid_driver.cpp:1835-2026) in one launch: periodic[f] != 0 (host; ix1, ox1, ix2, ox2, ix3, ox3)
+ * = periodic face, the others have bc_type.  The mirror types equal the reference's x1, x2, x3 sequence; multipole
+ * faces use mesh_ext (host: x1min, x1max, ...) and the cell count of this level, and edge and corner ghosts that touch
+ * a multipole face are left alone. */
+int akmi_mg_root_boundary_bc(int nz, int ny, int nx, int bc_type, const int periodic[6], int mporder, const double *mp,
+                             const double mesh_ext[6], double *u, void *stream);
+/* CalculateCenterOfMass (auto_origin != 0: mp[25..27] = 1/m0 * (m3, m1, m2); otherwise mp[25..27] is read) and
+ * CalculateMultipoleCoefficients + ScaleMultipoleCoefficients (multigrid_driver.cpp:2213-2434) of the active cells of
+ * src: mp[0..8] (mporder 2) or mp[0..24] (4).  Sums in the order of akmi_mg_average; scratch: 25 *
+ * akmi_mg_reduce_scratch_doubles() doubles.  4 launches, 8 with auto_origin; nothing is read back. */
+int akmi_mg_multipole_moments(int nmb, int nz, int ny, int nx, int mporder, int nodipole, int auto_origin,
+                              const double *xlim, const double *src, double *scratch, double *mp, void *stream);
+/* Multigrid::ApplyMask (multigrid.cpp:360-388): src = 0 on the active cells with r^2 > mask_radius^2 about
+ * (ox, oy, oz), cell centres by CellCenterX from xlim; mask_radius <= 0 launches nothing */
+int akmi_mg_mask(int nmb, int nz, int ny, int nx, const double *xlim, double mask_radius, double ox, double oy, double oz,
+                 double *src, void *stream);
 /* TransferFromBlocksToRoot (multigrid_driver.cpp:479-548) / SetFromRootGrid (multigrid.cpp:617-676): (nz, ny, nx) the
  * root grid, lloc device ints (lx1, lx2, lx3) per block; the blocks' arrays are those of the 1-cell level (27 doubles
  * per block).  initflag: the source alone; folddata: uold too */
@@ -1060,7 +1092,7 @@ int akmi_mg_selfgravity(const akmi_pack *p, int face_shaped, double bdt, const d
                         const double *flx1, const double *flx2, const double *flx3, double *u0, void *stream);
 
 #define AKMI_MG_NNORMS 42
-/* one rank, uniform mesh, periodic: the MeshBlocks tile the root grid nrx1 x nrx2 x nrx3 */
+/* one rank, uniform mesh: the MeshBlocks tile the root grid nrx1 x nrx2 x nrx3 */
 typedef struct akmi_mg_plan {
   int nmb, nxb;                        /* MeshBlocks of the pack; edge of a MeshBlock (power of two) */
   int nrx1, nrx2, nrx3;                /* root grid */
@@ -1072,18 +1104,30 @@ typedef struct akmi_mg_plan {
   const int *nghbr;                    /* device, nmb*27, as akmi_mg_exchange */
   const int *lloc;                     /* device, nmb*3 */
   double *ws;                          /* device, akmi_mg_workspace_doubles(); keeps u between calls */
+  /* physical faces; all zero: six periodic faces, as before these fields existed */
+  int mg_bc;                           /* AKMI_MGBC_*: the type of every non-periodic face */
+  int periodic[6];                     /* ix1, ox1, ix2, ox2, ix3, ox3: != 0 = periodic face (read when mg_bc != none) */
+  int mporder, nodipole, auto_mporigin;
+  double mesh_ext[6];                  /* x1min, x1max, x2min, x2max, x3min, x3max of the mesh */
+  double mporigin[3];                  /* the origin of the expansion unless auto_mporigin */
+  double mask_radius, mask_origin[3];  /* > 0: the source is zeroed outside this radius */
+  const double *xlim;                  /* device, nmb*6: extents of every MeshBlock (multipole, mask) */
 } akmi_mg_plan;
 long long akmi_mg_workspace_doubles(const akmi_mg_plan *plan);
 /* offset (doubles) into ws of array `which` (0 u, 1 src, 2 def, 3 uold) of MeshBlock level / root level `level` */
 long long akmi_mg_level_offset(const akmi_mg_plan *plan, int is_root, int level, int which);
-/* MGGravityDriver::Solve (mg_gravity.cpp:177-245) enqueued as a whole: LoadSource(-four_pi_G), the initial guess from
- * phi unless full_multigrid, SolveFMG / SolveMG, RetrieveResult into phi.  *coffset: the red-black offset, carried
+/* MGGravityDriver::Solve (mg_gravity.cpp:177-245) enqueued as a whole: LoadSource(-four_pi_G), ApplyMask, the initial
+ * guess from phi unless full_multigrid, SubtractAverage, under multipole the centre of mass and the scaled moments (on
+ * the device, into ws), SolveFMG / SolveMG, RetrieveResult into phi.  With mg_bc != none every exchange and root
+ * boundary is the _bc form, one launch each as before.  *coffset: the red-black offset, carried
  * from call to call.  norms (host, AKMI_MG_NNORMS doubles, -1 = not computed): [0] initial defect, [1 + n] after
  * V-cycle n of SolveMG (threshold >= 0, or show_defect >= 2), [41] final (show_defect >= 1).  *ncycles: V-cycles of
  * SolveMG; 40 with the last norm above eps = the reference's "Failed to converge".  The stream is synchronised only
  * where a norm is read. */
 int akmi_mg_solve(const akmi_mg_plan *plan, const double *u0, double *phi, int *coffset, double *norms, int *ncycles,
                   void *stream);
+/* offset (doubles) into ws of the 28 doubles akmi_mg_solve keeps under multipole: coefficients, then the origin */
+long long akmi_mg_multipole_offset(const akmi_mg_plan *plan);
 /* kernel launches this unit has enqueued since the last reset */
 long long akmi_mg_launch_count(int reset);
 

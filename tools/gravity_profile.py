@@ -8,6 +8,8 @@ python tools/gravity_profile.py cycle [n] [nb] [cycles]    ms per cycle of that 
                                                            both removed (task-granular path both times)
 python tools/gravity_profile.py smooth [n] [nb] [rounds]   one colour of the smoother on the finest level against
                                                            akmi_calib_copy of the same number of doubles (HIP events)
+python tools/gravity_profile.py isolated [n] [nb] [rounds] the same Solve on inputs/binary_gravity.athinput (outflow faces) with
+                                                           mg_bc = zerofixed and multipole, next to the periodic one
 python tools/gravity_profile.py all                        the table of profiles/gravity_mg.txt
 
 Counted traffic of one colour of the smoother: u read, src read, u written, whole cache lines: 24 bytes per cell of
@@ -37,15 +39,27 @@ def _sim(n, nb, gravity=True, init=True):
     return Simulation(pin, initialize=init)
 
 
+def _sim_isolated(n, nb, mg_bc):
+    """the two-sphere deck at n^3 with the solver settings of _sim: FMG + 4 V-cycles, 2+2 sweeps"""
+    from athenak_amd.main import Simulation, load_deck
+    over = ["mesh/nx%d=%d" % (q, n) for q in (1, 2, 3)] + ["meshblock/nx%d=%d" % (q, nb) for q in (1, 2, 3)] + [
+        "gravity/mg_bc=%s" % mg_bc, "gravity/threshold=-1.0", "gravity/npresmooth=2", "gravity/npostsmooth=2"]
+    pin = load_deck("binary_gravity.athinput", over)
+    for blk in [b for b in pin.blocks if b.startswith("output")]:
+        del pin.blocks[blk]
+    pin.blocks["gravity"]["niteration"] = "4"
+    return Simulation(pin)
+
+
 def _median(v):
     v = sorted(v)
     return v[len(v)//2], v[0], v[-1]
 
 
-def run_solve(n, nb, rounds):
+def run_solve(n, nb, rounds, mg_bc=None):
     import torch
     from athenak_amd import capi
-    sim = _sim(n, nb)
+    sim = _sim(n, nb) if mg_bc is None else _sim_isolated(n, nb, mg_bc)
     d = sim.pmesh.pmb_pack.pgrav.pmgd
     L = capi.lib()
     ms = []
@@ -59,9 +73,10 @@ def run_solve(n, nb, rounds):
             ms.append(1e3*(time.perf_counter() - t0))
     launches = int(L.akmi_mg_launch_count(0))
     med, lo, hi = _median(ms)
-    print("Solve %4d^3, blocks %2d^3 (%4d), levels %d+%d-1, FMG + 4 V-cycles, 2+2 sweeps: median %8.3f ms  min %8.3f  "
+    print("Solve %4d^3, blocks %2d^3 (%4d), levels %d+%d-1, FMG + 4 V-cycles, 2+2 sweeps" % (n, nb, d.nmb, d.nrootlevel_, d.nmblevel_)
+          + (", %-9s" % mg_bc if mg_bc else "") + ": median %8.3f ms  min %8.3f  "
           "max %8.3f  (%d rounds)  %5d launches  %6.2f us per launch" % (
-              n, nb, d.nmb, d.nrootlevel_, d.nmblevel_, med, lo, hi, rounds, launches, 1e3*med/launches), flush=True)
+              med, lo, hi, rounds, launches, 1e3*med/launches), flush=True)
 
 
 def run_cycle(n, nb, cycles):
@@ -117,6 +132,10 @@ if __name__ == "__main__":
         run_cycle(*(a + [128, 32, 5][len(a):]))
     elif mode == "smooth":
         run_smooth(*(a + [128, 32, 20][len(a):]))
+    elif mode == "isolated":
+        n, nb, rounds = a + [128, 32, 10][len(a):]
+        for bc in (None, "zerofixed", "multipole"):
+            run_solve(n, nb, rounds, bc)
     elif mode == "all":
         for n, nb in ((128, 64), (128, 32), (256, 64), (256, 32)):
             run_solve(n, nb, 10)
