@@ -136,6 +136,10 @@ class Driver:
             pmhd.RecvB(self, 0)
             pmhd.ClearSend(self, -1)
             pmhd.ClearRecv(self, -1)
+            pmhd.SendU_Shr(self, 0)            # driver.cpp:620-625: the shear-periodic x1 faces at the start time
+            pmhd.SendB_Shr(self, 0)
+            pmhd.RecvU_Shr(self, 0)
+            pmhd.RecvB_Shr(self, 0)
             pmhd.Prolongate(self, 0)
             pmhd.ApplyPhysicalBCs(self, 0)
             pmhd.ConToPrim(self, 0)

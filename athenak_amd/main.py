@@ -83,13 +83,23 @@ class Simulation:
 
     @property
     def psbox_u(self):
-        """the ShearingBoxCC of the hydro fluid (qshear, omega0, yshear); None without a <shearing_box> block"""
-        return getattr(self.pmesh.pmb_pack.phydro, "psbox_u", None)
+        """the ShearingBoxCC of the fluid (qshear, omega0, yshear); None without a <shearing_box> block"""
+        return getattr(self.phys, "psbox_u", None)
 
     @property
     def porb_u(self):
-        """the OrbitalAdvectionCC of the hydro fluid (maxjshift); None without a <shearing_box> block"""
-        return getattr(self.pmesh.pmb_pack.phydro, "porb_u", None)
+        """the OrbitalAdvectionCC of the fluid (maxjshift); None without a <shearing_box> block"""
+        return getattr(self.phys, "porb_u", None)
+
+    @property
+    def psbox_b(self):
+        """the ShearingBoxFC of an MHD fluid; None for hydro or without a <shearing_box> block"""
+        return getattr(self.phys, "psbox_b", None)
+
+    @property
+    def porb_b(self):
+        """the OrbitalAdvectionFC of an MHD fluid; None for hydro or without a <shearing_box> block"""
+        return getattr(self.phys, "porb_b", None)
 
     @property
     def omega_measured(self):

@@ -29,6 +29,15 @@ class MHD(FluidBase):
                                "problems (llf, hlle, hlld on this path)" % rs)
         self.rsolver_method = capi.RSOLVER[rs]
         self.nmhd = self.nfluid
+        # <shearing_box>, mhd.cpp:182-192: the four objects exist iff the block does.  The fused stage kernel cannot place
+        # the source term, the orbital remaps and the shear remaps between its phases: the task-granular chain
+        self.psbox_u = self.porb_u = self.psbox_b = self.porb_b = None
+        has_sbox = pin.DoesBlockExist("shearing_box")
+        if has_sbox:
+            if self.kinematic:
+                raise RuntimeError("### FATAL ERROR <shearing_box> with kinematic MHD (<mhd>/rsolver = advect) is not on "
+                                   "this path")
+            self.fused = False
         n3, n2, n1 = ppack.pmesh.mb_indcs.ncells
         nmb = self.nmb
         z5 = lambda: torch.zeros((nmb, self.nvars, n3, n2, n1), dtype=torch.float64, device=device)
@@ -45,6 +54,16 @@ class MHD(FluidBase):
         self.pbval_u = MeshBoundaryValues(ppack, bvals_kernels, device)
         self.pbval_u.set_pack(self.pack_c, self.nvars)
         self.pbval_b = self.pbval_u       # same neighbour tables; separate FC channel inside
+        if has_sbox:
+            from .shearing_box import OrbitalAdvectionCC, OrbitalAdvectionFC, ShearingBoxCC, ShearingBoxFC
+            self.psbox_u = ShearingBoxCC(ppack, pin, self.nvars, self)
+            self.porb_u = OrbitalAdvectionCC(ppack, pin, self.nvars, self)
+            self.psbox_b = ShearingBoxFC(ppack, pin, self)
+            self.porb_b = OrbitalAdvectionFC(ppack, pin, self)
+            if ppack.pmesh.shear_periodic:
+                # the shear remaps of the x1 ghost slabs sit between the exchange and the boundary functions, as in
+                # the reference's list: the gather must not apply the boundary functions of the other faces itself
+                self.pbval_u.fold_bcs = False
         self.psmr = None
         if self.multilevel:
             # coarse buffers (mhd.cpp:368-380) and the level-aware boundary values
@@ -84,13 +103,72 @@ class MHD(FluidBase):
     def _noop(self, pdrive, stage):
         return TaskStatus.complete
 
-    SaveMHDState = InitRecv = SendU_OA = RecvU_OA = _noop
-    SendU_Shr = RecvU_Shr = SendB_OA = RecvB_OA = _noop
-    SendB_Shr = RecvB_Shr = ClearSend = ClearRecv = _noop
+    # (SendU_OA / SendB_OA: nothing to pack on one rank, the remaps read the x2 neighbours' rows themselves)
+    SaveMHDState = SendU_OA = SendB_OA = ClearSend = ClearRecv = _noop
+
+    def _sbox_3d(self):
+        """the shear tasks run `if (three_d || shearing_box_r_phi)`, and r-phi is never set (mhd_tasks.cpp:127-153)"""
+        return self.psbox_u is not None and self.pmy_pack.pmesh.three_d
+
+    def InitRecv(self, pdrive, stage):
+        """mhd_tasks.cpp:139-153: the distance the x1 boundaries have sheared at the time this stage ends, for U and B;
+        the call of the driver's initialisation has stage = -1, hence the plain time"""
+        if self._sbox_3d():
+            pm = self.pmy_pack.pmesh
+            time = pm.time
+            if stage == pdrive.nexp_stages:
+                time += pm.dt
+            self.psbox_u.InitRecv(time)
+            self.psbox_b.InitRecv(time)
+        return TaskStatus.complete
 
     def MHDSrcTerms(self, pdrive, stage):
-        """mhd_tasks.cpp:254-258: if (psrc != nullptr) psrc->ApplySrcTerms(w0, peos->eos_data, beta_dt, u0)"""
-        return self._srcterms(pdrive, stage)
+        """mhd_tasks.cpp:254-261: psrc->ApplySrcTerms(w0, eos_data, beta_dt, u0), then
+        psbox_u->SourceTermsCC(w0, bcc0, eos_data, beta_dt, u0)"""
+        st = self._srcterms(pdrive, stage)
+        if self.psbox_u is not None:
+            self.psbox_u.SourceTermsCC(self.w0, pdrive.beta[stage - 1]*self.pmy_pack.pmesh.dt, self.u0, bcc0=self.bcc0)
+        return st
+
+    def RecvU_OA(self, pdrive, stage):
+        """mhd_tasks.cpp:299-309: last stage, 3-D.  Out of place into u1: the second register is dead between the last
+        RKUpdate of a cycle (FOFC reads it before that, in Fluxes) and the CopyCons / out-of-place update of the next
+        first stage, which write all of its active cells; its ghost cells are filled by SendU / the boundary functions
+        right after this task"""
+        if self._sbox_3d() and stage == pdrive.nexp_stages:
+            self.porb_u.RecvAndUnpackCC(self.u0, self.u1, self.recon_method)
+            self.u0, self.u1 = self.u1, self.u0
+        return TaskStatus.complete
+
+    def SendU_Shr(self, pdrive, stage):
+        """mhd_tasks.cpp:345-354"""
+        if self._sbox_3d():
+            self.psbox_u.PackAndSendCC(self.u0, self.recon_method)
+        return TaskStatus.complete
+
+    def RecvU_Shr(self, pdrive, stage):
+        """mhd_tasks.cpp:361-370"""
+        if self._sbox_3d():
+            self.psbox_u.RecvAndUnpackCC(self.u0)
+        return TaskStatus.complete
+
+    def RecvB_OA(self, pdrive, stage):
+        """mhd_tasks.cpp:439-449: last stage, 3-D; CT in place on b0 with the effective EMFs of the shift"""
+        if self._sbox_3d() and stage == pdrive.nexp_stages:
+            self.porb_b.RecvAndUnpackFC(self.b0, self.recon_method)
+        return TaskStatus.complete
+
+    def SendB_Shr(self, pdrive, stage):
+        """mhd_tasks.cpp:473-482"""
+        if self._sbox_3d():
+            self.psbox_b.PackAndSendFC(self.b0, self.recon_method)
+        return TaskStatus.complete
+
+    def RecvB_Shr(self, pdrive, stage):
+        """mhd_tasks.cpp:489-498"""
+        if self._sbox_3d():
+            self.psbox_b.RecvAndUnpackFC(self.b0)
+        return TaskStatus.complete
 
     def SendE(self, pdrive, stage):
         """mhd_tasks.cpp:402-417 (PackAndSendFluxFC + RecvAndUnpackFluxFC).  On a uniform mesh every
@@ -252,6 +330,8 @@ class MHD(FluidBase):
                 *self._b(self.uflx), self.efld.x1e, self.efld.x2e, self.efld.x3e, capi._stream()), "mhd_corner_e")
             if self.presist is not None:                 # mhd_tasks.cpp:381-383
                 self.presist.AddResistiveEMFs(self.b0, self.efld)
+            if self.psbox_b is not None and self.pmy_pack.pmesh.two_d:         # mhd_tasks.cpp:386-391
+                self.psbox_b.SourceTermsFC(self.b0, self.efld)
         return TaskStatus.complete
 
     def CT(self, pdrive, stage):

@@ -461,16 +461,25 @@ class HistoryOutput(BaseTypeOutput):
 
 def user_hist_of(pin):
     """<problem>/user_hist (pgen.cpp:49; default false, read without adding it to the deck) and what this path enrols for it:
-    TurbulentHistory of pgen_name = turb on an MHD run (turb.cpp:42), ShwaveHistory of pgen_name = shwave with ipert = 3"""
+    TurbulentHistory of pgen_name = turb on an MHD run (turb.cpp:42), ShwaveHistory of pgen_name = shwave with ipert = 3 (hydro) or
+    ipert = 4 (MHD)"""
     if not (pin.DoesParameterExist("problem", "user_hist") and pin.GetBoolean("problem", "user_hist")):
         return False
     name = pin.GetString("problem", "pgen_name") if pin.DoesParameterExist("problem", "pgen_name") else "none"
     if name == "shwave":
-        # shwave.cpp:144: ShwaveHistory is enrolled for the compressible hydro wave only
+        # shwave.cpp:144: ShwaveHistory is enrolled for the compressible hydro wave, and :186 for the MHD wave (dByc)
         if pin.DoesBlockExist("hydro") and pin.GetInteger("problem", "ipert") == 3:
             return True
+        if pin.DoesBlockExist("mhd") and not pin.DoesBlockExist("hydro"):
+            if pin.GetInteger("problem", "ipert") == 4:
+                return True
+            _fatal("<problem>/user_hist = true with pgen_name = shwave: the user history function of an MHD run (dByc) is "
+                   "enrolled for ipert = 4, the only MHD perturbation")
         _fatal("<problem>/user_hist = true with pgen_name = shwave: the user history function (dVyc) is enrolled for "
                "ipert = 3 of a hydro run only")
+    if name == "mri3d":
+        # mri3d.cpp:58: MRIHistory is enrolled whatever the deck holds; the generator itself needs an MHD run
+        return True
     if name != "turb":
         # pgen.cpp:86-92 exits with "user history function not enrolled"; the other generators' functions are not on this path
         _fatal("<problem>/user_hist = true, but the user history function of pgen_name = '%s' is not enrolled on this "

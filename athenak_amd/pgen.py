@@ -199,12 +199,14 @@ class ProblemGenerator:
         table = {"linear_wave": self.LinearWave, "shock_tube": self.ShockTube,
                  "orszag_tang": self.OrszagTang, "blast": self.UserProblem, "diffusion": self.Diffusion,
                  "cpaw": self.AlfvenWave, "turb": self.Turb, "rt": self.RayleighTaylor, "cshock": self.CShock,
-                 "gravity": self.SelfGravity, "shwave": self.Shwave,
+                 "gravity": self.SelfGravity, "shwave": self.Shwave, "mri3d": self.MRI3d,
                  "binary_gravity": self.BinaryGravity}
         self.user_hist_func = None       # (labels, sums) of the user history file; enrolled by the problem function
         # user-defined boundary conditions (pgen.cpp:57-62): enrolled by the problem function
         self.user_bcs = any(b == capi.BC["user"] for b in pmesh.mesh_bcs)
         self.user_bcs_func = None
+        if name == "mri2d":
+            raise RuntimeError("### FATAL ERROR problem/pgen_name = mri2d is not on this path (the 3-D unstratified mri3d is)")
         if name not in table:
             raise RuntimeError("### FATAL ERROR problem/pgen_name = '%s' is not one of the "
                                "decks on this build's path %s" % (name, sorted(table)))
@@ -1463,8 +1465,8 @@ class ProblemGenerator:
     # ---- shearing waves, src/pgen/tests/shwave.cpp:59-168 (hydro), :346-428 ---------------
     def Shwave(self, pin, restart):
         """pgen_name = shwave: ipert = 1 epicyclic oscillation, 2 incompressible and 3 compressible shearing wave of
-        Johnson & Gammie (2005).  The MHD perturbations (ipert = 4) belong to the face-centred half of the shearing box,
-        which is not on this path."""
+        Johnson & Gammie (2005) for a hydro deck; ipert = 4, the compressible MHD shearing wave, for an MHD deck
+        (_shwave_mhd).  Each fluid refuses the other's perturbations with the reference's message."""
         if restart:
             return
         pm = self.pmy_mesh_
@@ -1478,6 +1480,8 @@ class ProblemGenerator:
         kx = (2.0*math.pi/Lx)*float(pin.GetInteger("problem", "nwx"))
         ky = (2.0*math.pi/Ly)*float(pin.GetInteger("problem", "nwy"))
         kz = (2.0*math.pi/Lz)*float(pin.GetInteger("problem", "nwz"))
+        if pk.phydro is None and pk.pmhd is not None:
+            return self._shwave_mhd(pin, d0, p0, amp, ipert, kx, ky, kz)
         if pk.phydro is None or getattr(pk.phydro, "psbox_u", None) is None:
             raise RuntimeError("### FATAL ERROR shwave problem generator only works in shearing box.\nLikely missing "
                                "<shearing_box> block in input file")
@@ -1511,14 +1515,196 @@ class ProblemGenerator:
                 w[m, IEN][ks, js, is_] = p0/gm1
         self._store(w, None)
 
+    def _shwave_mhd(self, pin, d0, p0, amp, ipert, kx, ky, kz):
+        """shwave.cpp:170-341, ipert = 4: the compressible MHD shearing wave of Johnson (2007), the field from the
+        differences of three vector potentials at their edges.  The conserved variables are written as the reference
+        writes them (not through primitives).  Its ideal-gas energy line reads b0.x1f for all three components (and
+        rows / planes of x1f beyond the active ones, which are still zero): kept as it is."""
+        pm = self.pmy_mesh_
+        pk = pm.pmb_pack
+        phys = pk.pmhd
+        if getattr(phys, "psbox_u", None) is None:
+            raise RuntimeError("### FATAL ERROR shwave problem generator only works in shearing box\nLikely missing "
+                               "<shearing_box> block in input file")
+        if ipert != 4:
+            raise RuntimeError("### FATAL ERROR MHD shwave test requires ipert = 4.")
+        self.user_hist_func = self.ShwaveHistory           # shwave.cpp:186
+        qshear, omega0 = phys.psbox_u.qshear, phys.psbox_u.omega0
+        self._shw = dict(kx=kx, ky=ky, kz=kz, qshear=qshear, omega0=omega0)
+        eos = phys.peos.eos_data
+        gm1 = eos.gamma - 1.0
+        beta = pin.GetReal("problem", "beta")
+        B02 = p0/beta
+        k2 = kx*kx + ky*ky + kz*kz
+        rbx = ky*math.sqrt(B02/(kx*kx + ky*ky))
+        rby = -kx*math.sqrt(B02/(kx*kx + ky*ky))
+        rbz = 0.0
+        sch = eos.iso_cs/omega0
+        cf1 = math.sqrt(B02*(1.0 + beta))
+        cf2 = amp*math.sqrt(sch*math.sqrt(k2*beta/(1.0 + beta)))
+        vd = cf1/math.sqrt(k2)*cf2
+        w, (b1, b2, b3) = self._alloc_host()
+        u = np.zeros_like(w)
+        ks, js, is_ = self._active()
+        k0, j0, i0 = ks.start, js.start, is_.start
+        ind = pm.mb_indcs
+        nx1, nx2, nx3 = ind.nx1, ind.nx2, ind.nx3
+        g3 = lambda a, b, c: np.meshgrid(a, b, c, indexing="ij")
+        for m in range(pk.nmb_thispack):
+            x1v, x2v, x3v, x1f, x2f, x3f, sz = self._coords(m)
+            X3, X2, X1 = g3(x3v, x2v, x1v)
+            csk = np.cos(kx*X1 + ky*X2 + kz*X3)
+            rd = d0*(1.0 + cf2*csk)
+            u[m, IDN][ks, js, is_] = rd
+            u[m, 1][ks, js, is_] = rd*vd*kx*csk
+            u[m, 2][ks, js, is_] = rd*vd*ky*csk
+            u[m, 3][ks, js, is_] = rd*vd*kz*csk
+            if eos.is_ideal:
+                u[m, IEN][ks, js, is_] = p0/gm1 + 0.5*rd*((vd*csk)*(vd*csk))*k2
+            # vector potentials: a1 at (x1v, x2f, x3f), a2 at (x1f, x2v, x3f), a3 at (x1f, x2f, x3v)
+            X3, X2, X1 = g3(x3f, x2f, x1v)
+            a1 = (cf2/k2*np.sin(kx*X1 + ky*X2 + kz*X3))*(rby*kz - rbz*ky)
+            X3, X2, X1 = g3(x3f, x2v, x1f)
+            a2 = (cf2/k2*np.sin(kx*X1 + ky*X2 + kz*X3))*(rbz*kx - rbx*kz)
+            X3, X2, X1 = g3(x3v, x2f, x1f)
+            a3 = (cf2/k2*np.sin(kx*X1 + ky*X2 + kz*X3))*(rbx*ky - rby*kx)
+            b1[m][k0:k0 + nx3, j0:j0 + nx2, i0:i0 + nx1 + 1] = (rbx + (a3[:, 1:, :] - a3[:, :-1, :])/sz.dx2
+                                                               - (a2[1:, :, :] - a2[:-1, :, :])/sz.dx3)
+            b2[m][k0:k0 + nx3, j0:j0 + nx2 + 1, i0:i0 + nx1] = (rby + (a1[1:, :, :] - a1[:-1, :, :])/sz.dx3
+                                                               - (a3[:, :, 1:] - a3[:, :, :-1])/sz.dx1)
+            b3[m][k0:k0 + nx3 + 1, j0:j0 + nx2, i0:i0 + nx1] = (rbz + (a2[:, :, 1:] - a2[:, :, :-1])/sz.dx1
+                                                               - (a1[:, 1:, :] - a1[:, :-1, :])/sz.dx2)
+            if eos.is_ideal:
+                x = b1[m]
+                c = x[k0:k0 + nx3, j0:j0 + nx2, i0:i0 + nx1]
+                b1p = x[k0:k0 + nx3, j0:j0 + nx2, i0 + 1:i0 + nx1 + 1]
+                b2p = x[k0:k0 + nx3, j0 + 1:j0 + nx2 + 1, i0:i0 + nx1]
+                b3p = x[k0 + 1:k0 + nx3 + 1, j0:j0 + nx2, i0:i0 + nx1] if nx3 > 1 else c
+                u[m, IEN][ks, js, is_] += 0.125*((c + b1p)*(c + b1p) + (c + b2p)*(c + b2p) + (c + b3p)*(c + b3p))
+        self._upload_cc(phys.u0, u)
+        self._upload_cc(phys.b0.x1f, b1)
+        self._upload_cc(phys.b0.x2f, b2)
+        self._upload_cc(phys.b0.x3f, b3)
+
+    # ---- magnetorotational instability, src/pgen/tests/mri3d.cpp (unstratified) -------------
+    MRI_LABELS = ["1-KE", "2-KE", "3-KE", "1-ME", "2-ME", "3-ME", "1-bcc", "2-bcc", "3-bcc", "dVxVy", "dBxBy"]
+
+    def MRI3d(self, pin, restart):
+        """pgen_name = mri3d, the unstratified box of Hawley, Gammie & Balbus (1995): ifield = 1 zero-net-flux
+        Bz = B0 sin(kx x), 2 uniform Bz, 3 uniform By, B0 = sqrt(2 p0/beta); random perturbations of amplitude amp in the
+        density (isothermal) or the pressure (ideal gas) and in the three velocities.  The random numbers come from
+        numpy.random.default_rng(<problem>/rseed), by default seeded with the first gid of the pack as the reference seeds
+        its pool; the stream is not the reference's (Kokkos hands the states of its pool to threads), only its
+        distribution is.  The stratified disk (user x3 boundaries) is not on this path."""
+        pm = self.pmy_mesh_
+        pk = pm.pmb_pack
+        if pk.pmhd is None:
+            raise RuntimeError("### FATAL ERROR mri3d problem generator only works in mhd")
+        phys = pk.pmhd
+        if getattr(phys, "psbox_u", None) is None:
+            raise RuntimeError("### FATAL ERROR Shearing box not enabled for mri3d problem, likely missing <shearing_box> "
+                               "block in input file")
+        if phys.psbox_u.is_stratified:
+            raise RuntimeError("### FATAL ERROR pgen_name = mri3d with <shearing_box>/stratified = true is not on this path "
+                               "(the stratified disk needs the user x3 boundaries of mri3d.cpp:343-440)")
+        if self.user_bcs:
+            raise RuntimeError("### FATAL ERROR pgen_name = mri3d with user boundaries is not on this path (they belong to "
+                               "the stratified disk)")
+        self.user_hist_func = self.MRIHistory              # mri3d.cpp:58
+        if restart:
+            return
+        if not pm.three_d:
+            raise RuntimeError("### FATAL ERROR mri3d problem generator only works in 3D")
+        eos = phys.peos.eos_data
+        gm1 = eos.gamma - 1.0
+        amp = pin.GetReal("problem", "amp")
+        beta = pin.GetReal("problem", "beta")
+        nwx = pin.GetOrAddInteger("problem", "nwx", 1)
+        ifield = pin.GetOrAddInteger("problem", "ifield", 1)
+        d0 = pin.GetOrAddReal("problem", "dens", 1.0)
+        p0 = pin.GetReal("problem", "pres") if eos.is_ideal else d0*(eos.iso_cs*eos.iso_cs)
+        binit = math.sqrt(2.0*p0/beta)
+        ms = pm.mesh_size
+        kx = 2.0*(math.pi/(ms.x1max - ms.x1min))*float(nwx)
+        zlimit = pin.GetOrAddReal("problem", "zlimit", max(abs(ms.x3max), abs(ms.x3min)))
+        rseed = pin.GetInteger("problem", "rseed") if pin.DoesParameterExist("problem", "rseed") else pk.gids
+        rng = np.random.default_rng(rseed)
+        w, (b1, b2, b3) = self._alloc_host()
+        u = np.zeros_like(w)
+        ks, js, is_ = self._active()
+        k0, j0, i0 = ks.start, js.start, is_.start
+        ind = pm.mb_indcs
+        nx1, nx2, nx3 = ind.nx1, ind.nx2, ind.nx3
+        for m in range(pk.nmb_thispack):
+            x1v, x2v, x3v = self._coords(m)[:3]
+            # faces i in [is, ie], plus ie+1 / je+1 / ke+1 with the value of the last cell (mri3d.cpp:146-176)
+            if ifield == 1:
+                bz = np.broadcast_to((binit*np.sin(kx*x1v))[None, None, :], (nx3 + 1, nx2, nx1))
+                b3[m][k0:k0 + nx3 + 1, js, is_] = bz
+            elif ifield == 2:
+                b3[m][k0:k0 + nx3 + 1, js, is_] = binit
+            elif ifield == 3:
+                inside = np.abs(x3v) < zlimit
+                b2[m][ks, j0:j0 + nx2 + 1, is_] = np.where(inside[:, None, None], binit, 0.0)
+            # the draws of a cell, in the order of mri3d.cpp:199-217
+            r = amp*2.0*(rng.random((nx3, nx2, nx1, 4)) - 0.5)
+            rd = np.full((nx3, nx2, nx1), d0)
+            if not eos.is_ideal:
+                rd = rd*(1.0 + r[..., 0])
+                rv = (r[..., 1], r[..., 2], r[..., 3])
+            else:
+                rv = (r[..., 0], r[..., 1], r[..., 2])
+            u[m, IDN][ks, js, is_] = rd
+            for n in range(3):
+                u[m, 1 + n][ks, js, is_] = rd*rv[n]
+            if eos.is_ideal:
+                rp = p0*(1.0 + r[..., 3])
+                by = 0.5*(b2[m][ks, j0:j0 + nx2, is_] + b2[m][ks, j0 + 1:j0 + nx2 + 1, is_])
+                bz = 0.5*(b3[m][k0:k0 + nx3, js, is_] + b3[m][k0 + 1:k0 + nx3 + 1, js, is_])
+                u[m, IEN][ks, js, is_] = rp/gm1 + 0.5*(by*by) + 0.5*(bz*bz)
+        self._upload_cc(phys.u0, u)
+        self._upload_cc(phys.b0.x1f, b1)
+        self._upload_cc(phys.b0.x2f, b2)
+        self._upload_cc(phys.b0.x3f, b3)
+
+    def MRIHistory(self, pm):
+        """mri3d.cpp:233-336: (labels, sums) of the user history file: the conserved variables, the kinetic and magnetic
+        energies per direction, the net fluxes, the Reynolds stress dVxVy and the Maxwell stress dBxBy.  Per-MeshBlock
+        partials of akmi_mri_history, added in gid order."""
+        from .turb_driver import gid_ordered_sums
+        pk = pm.pmb_pack
+        phys = pk.pmhd
+        ideal = phys.peos.eos_data.is_ideal
+        labels = ["mass", "1-mom", "2-mom", "3-mom"] + (["tot-E"] if ideal else []) + self.MRI_LABELS
+        L = capi.lib()
+        partial = torch.zeros((phys.nmb, len(labels)), dtype=torch.float64, device=phys.u0.device)
+        work = torch.empty(int(L.akmi_mri_history_workspace_bytes(phys.pack_c))//8 + 1, dtype=torch.float64,
+                           device=phys.u0.device)
+        capi.check(L.akmi_mri_history(phys.pack_c, phys.u0, phys.bcc0, phys.b0.x1f, phys.b0.x2f, phys.b0.x3f, partial, work,
+                                      capi._stream()), "mri_history")
+        return labels, np.array(gid_ordered_sums(partial.cpu().numpy(), pk))
+
     def ShwaveHistory(self, pm):
         """shwave.cpp:346-428: (labels, sums) of the user history file of the compressible shearing wave,
-        dVyc = sum of vol*2*vy*cos(kx(t) x + ky y) with kx(t) = kx + qshear*omega0*t*ky.  A diagnostic written at the
-        cadence of the history file: summed on the host from the primitive velocity."""
+        dVyc = sum of vol*2*vy*cos(kx(t) x + ky y) with kx(t) = kx + qshear*omega0*t*ky; for an MHD run
+        dByc = sum of vol*2*(bcc0(IBY) - (0.2 - 0.15*omega0*t))*cos(kx(t) x + ky y + kz z).  A diagnostic written at the
+        cadence of the history file: summed on the host from the primitive velocity / the cell-centred field."""
         sv = self._shw
         pk = pm.pmb_pack
         kx = sv["kx"] + sv["qshear"]*sv["omega0"]*pm.time*sv["ky"]
         ks, js, is_ = self._active()
+        if pk.phydro is None:
+            omega_t = sv["omega0"]*pm.time
+            by = pk.pmhd.bcc0[:, 1].cpu().numpy()
+            total = 0.0
+            for m in range(pk.nmb_thispack):
+                x1v, x2v, x3v = self._coords(m)[:3]
+                sz = pk.pmb.mb_size[m]
+                vol = sz.dx1*sz.dx2*sz.dx3
+                X3, X2, X1 = np.meshgrid(x3v, x2v, x1v, indexing="ij")
+                term = vol*2.0*(by[m][ks, js, is_] - (0.2 - 0.15*omega_t))
+                total += float(np.sum(term*np.cos(kx*X1 + sv["ky"]*X2 + sv["kz"]*X3)))
+            return ["dByc"], np.array([total])
         vy = pk.phydro.w0[:, 2].cpu().numpy()
         total = 0.0
         for m in range(pk.nmb_thispack):

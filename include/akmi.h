@@ -1132,7 +1132,8 @@ long long akmi_mg_multipole_offset(const akmi_mg_plan *plan);
 long long akmi_mg_launch_count(int reset);
 
 /* ---- shearing box, cell-centred half (src/shearing_box/) ------------------------------------------------- *
- * csrc/akmi_sbox.hip.  Hydro only; every entry reproduces the reference's roundings in the written order.
+ * csrc/akmi_sbox.hip.  The entries a hydro fluid uses (an MHD fluid uses them for its cell-centred variables); every entry
+ * reproduces the reference's roundings in the written order.
  * xlim = device double[nmb][6]: x1min, x1max, x2min, x2max, x3min, x3max of every MeshBlock (mb_size).
  *
  * ShearingBoxCC::SourceTermsCC (shearing_box_srcterms.cpp:27-84) on the active cells: the 3-D branch when nx3 > 1, the
@@ -1162,6 +1163,45 @@ int akmi_sbox_shift_x1(const akmi_pack *p, int nb_in, int nb_out, int nslot, con
  * the arrays if it does not hold; the result is then wrong). */
 int akmi_sbox_orbital_cc(const akmi_pack *p, int recon, int maxjshift, double qo, double dt, const int *nghbr,
                          const double *xlim, const double *u0, double *out, void *stream);
+
+/* ---- shearing box, MHD and the face-centred half ---------------------------------------------------------- *
+ * The MHD form of SourceTermsCC (shearing_box_srcterms.cpp:92-150): as akmi_sbox_srcterms, with the energy term
+ * bdt*(mom1*mom2/den - bcc(IBX)*bcc(IBY))*qo (IBZ in the r-z branch); bcc0 = double[nmb][3][N3][N2][N1], read only for an
+ * ideal gas. */
+int akmi_sbox_srcterms_mhd(const akmi_pack *p, double coef1, double coef2, double coef3, double bdt, double qo,
+                           int stratified, const double *xlim, const double *w0, const double *bcc0, double *u0,
+                           void *stream);
+/* ShearingBoxFC::SourceTermsFC (shearing_box_srcterms.cpp:159-200), 2-D meshes only: for j in [js, je+1], i in [is, ie+1]
+ * e1 -= qo*x1v*b2 and e2 += qo*x1f*b1 at k = ks and ke+1, both from b at ks; x1v = CellCenterX, x1f = LeftEdgeX. */
+int akmi_sbox_efield_2d(const akmi_pack *p, double qo, const double *xlim, const double *bx1f, const double *bx2f,
+                        double *e1, double *e2, void *stream);
+/* The shear-periodic x1 boundary of the face-centred field, ShearingBoxFC::PackAndSendFC / RecvAndUnpackFC
+ * (shearing_box_fc.cpp) on one rank; tab as for akmi_sbox_remap_x1, buf = device double[2][nslot][3][N3][nx2][ng].
+ * Inner face: all three components at ghost index i; outer face: x1f at (ie+2)+i, x2f and x3f at (ie+1)+i.  Planes
+ * k in [0, N3) and, in shift_x1_fc, rows j in [0, N2): the last x2f row and the last x3f plane are not touched. */
+int akmi_sbox_remap_x1_fc(const akmi_pack *p, int recon, int nb_in, int nb_out, int nslot, const int *tab, int tab_stride,
+                          double yshear, const double *bx1f, const double *bx2f, const double *bx3f, double *buf,
+                          void *stream);
+int akmi_sbox_shift_x1_fc(const akmi_pack *p, int nb_in, int nb_out, int nslot, const int *tab, int tab_stride, int nmbx2,
+                          int joffset, const double *buf, double *bx1f, double *bx2f, double *bx3f, void *stream);
+/* OrbitalAdvectionFC::RecvAndUnpackFC (orbital_advection_fc.cpp:223-358) on one rank, 3-D meshes, two launches.
+ * orbital_emf: emfx (from x3f, x1 = cell centre) and emfz (from x1f, x1 = left edge), double[nmb][N3][N2][N1], for
+ * k in [ks, ke+1], j in [js, je+1], i in [is, ie+1]: the remap flux at face j - joffset and the whole cells of the integer
+ * shift, yshear = -qo*x1*dt.  Rows beyond an x2 edge are the x2 neighbour's active rows (nghbr as for orbital_cc); the
+ * same guarantees on maxjshift.  orbital_ct: the three CT differences, in place on the field. */
+int akmi_sbox_orbital_emf(const akmi_pack *p, int recon, int maxjshift, double qo, double dt, const int *nghbr,
+                          const double *xlim, const double *bx1f, const double *bx3f, double *emfx, double *emfz,
+                          void *stream);
+int akmi_sbox_orbital_ct(const akmi_pack *p, const double *emfx, const double *emfz, double *bx1f, double *bx2f,
+                         double *bx3f, void *stream);
+/* MRIHistory (src/pgen/tests/mri3d.cpp:233-336) over the active cells of a 3-D MHD pack: nhist = 15 (isothermal) or 16
+ * (ideal gas) sums, nmhd = 4 or 5 conserved variables first, then 1-KE 2-KE 3-KE 1-ME 2-ME 3-ME 1-bcc 2-bcc 3-bcc dVxVy dBxBy.
+ * partial = device double[nmb][nhist]: per-MeshBlock sums by fixed-shape trees (the same bits on every call); the host
+ * adds them in gid order.  work: akmi_mri_history_workspace_bytes() of device memory. */
+#define AKMI_MRI_NHIST_MAX 16
+long long akmi_mri_history_workspace_bytes(const akmi_pack *p);
+int akmi_mri_history(const akmi_pack *p, const double *u0, const double *bcc0, const double *bx1f, const double *bx2f,
+                     const double *bx3f, double *partial, double *work, void *stream);
 
 #ifdef __cplusplus
 }

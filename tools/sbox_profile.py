@@ -3,7 +3,11 @@
 Device events round 20 launches after 5 of warm-up: the orbital-advection kernel at 128^3 and 256^3 (five variables)
 next to akmi_calib_copy over the same bytes on the same arrays, the two launches of the shear-periodic boundary, and one
 cycle of the hydro_shwave scheme at 128^3 with and without <shearing_box> on the task-granular chain (host clock round 20
-cycles ending in a synchronise, two windows each, alternating).  --cycle: the last part alone."""
+cycles ending in a synchronise, two windows each, alternating).  --cycle: the last part alone.
+
+--mhd: the timings of profiles/sbox_mhd.txt instead: at 128^3 the two launches of the orbital
+advection of the face-centred field (akmi_sbox_orbital_emf, akmi_sbox_orbital_ct) for DC, PLM and PPMX, each next to
+akmi_calib_copy moving the same bytes, and the two launches of the shear-periodic boundary of the field."""
 import os
 import sys
 import time
@@ -47,6 +51,47 @@ def cycles(sim, n=20):
     return (time.perf_counter() - t0)/n*1e3
 
 
+def mhd_part(say):
+    """orbital advection and the shear-periodic boundary of b0 at 128^3"""
+    from test_gpu_sbox_mhd import deck_text as mhd_deck
+    n = 128
+    for recon, ng in (("ppmx", 3), ("plm", 2), ("dc", 2)):
+        sim = make_sim(mhd_deck((n, n, n), (1, 1, 1), ng, BOX[0], BOX[1], recon=recon))
+        ph, orb = sim.phys, sim.phys.porb_b
+        for t in (ph.b0.x1f, ph.b0.x2f, ph.b0.x3f):
+            t.normal_()
+        sim.pmesh.dt = dt = 0.3*(0.5/n)
+        L, pc, qo = ph.L, ph.pack_c, orb.qshear*orb.omega0
+        b = ph.b0
+        t_emf = ev_time(lambda: capi.check(L.akmi_sbox_orbital_emf(pc, ph.recon_method, orb.maxjshift, qo, dt, ph.pbval_u.nghbr,
+                                                                   orb.xlim, b.x1f, b.x3f, orb.emfx, orb.emfz, capi._stream()),
+                                           "sbox_orbital_emf"))
+        t_ct = ev_time(lambda: capi.check(L.akmi_sbox_orbital_ct(pc, orb.emfx, orb.emfz, b.x1f, b.x2f, b.x3f, capi._stream()),
+                                          "sbox_orbital_ct"))
+        # bytes: emf reads two face arrays and writes two EMF arrays (4 doubles per cell); CT reads the two EMF arrays and
+        # reads and writes three face arrays (8 doubles per cell)
+        src, dst = ph.u0.view(-1), ph.u1.view(-1)
+        c_emf, c_ct = 2*n**3, 4*n**3
+        t_c1 = ev_time(lambda: capi.check(L.akmi_calib_copy(dst, src, c_emf, capi._stream()), "calib_copy"))
+        t_c2 = ev_time(lambda: capi.check(L.akmi_calib_copy(dst, src, c_ct, capi._stream()), "calib_copy"))
+        say("orbital_emf %d^3 %-4s ng=%d: %7.1f us = %5.0f GB/s (32 B per cell) | akmi_calib_copy, same bytes: %6.1f us | ratio %.2f"
+            % (n, recon, ng, t_emf, 32.0*n**3/t_emf/1e3, t_c1, t_c1/t_emf))
+        say("orbital_ct  %d^3 %-4s ng=%d: %7.1f us = %5.0f GB/s (64 B per cell) | akmi_calib_copy, same bytes: %6.1f us | ratio %.2f"
+            % (n, recon, ng, t_ct, 64.0*n**3/t_ct/1e3, t_c2, t_c2/t_ct))
+        del sim, ph, orb, b, src, dst
+        torch.cuda.empty_cache()
+    sim = make_sim(mhd_deck((64, 64, 128), (2, 2, 1), 3, BOX[0], BOX[1], recon="ppmx", tlim=100.0))
+    ph, sb = sim.phys, sim.phys.psbox_b
+    sb.yshear = 0.1234
+    t_re = ev_time(lambda: sb.PackAndSendFC(ph.b0, ph.recon_method))
+    t_sh = ev_time(lambda: sb.RecvAndUnpackFC(ph.b0))
+    nb = sb.buf.numel()
+    src, dst = ph.u0.view(-1), ph.u1.view(-1)
+    t_c = ev_time(lambda: capi.check(ph.L.akmi_calib_copy(dst, src, nb, capi._stream()), "calib_copy"))
+    say("shear boundary of b0 128^3 (2 x 2 x 1 blocks, ng = 3, both faces): remap_x1_fc %.1f us, shift_x1_fc %.1f us | "
+        "akmi_calib_copy of the buffer's %d doubles: %.1f us" % (t_re, t_sh, nb, t_c))
+
+
 def main(argv):
     only_cycle = "--cycle" in argv
     files = [a for a in argv if not a.startswith("--")]
@@ -60,6 +105,8 @@ def main(argv):
 
     assert torch.cuda.is_available(), "needs a GPU"
     say(torch.cuda.get_device_name(0))
+    if "--mhd" in argv:
+        return mhd_part(say)
     for n in (() if only_cycle else (128, 256)):
         for recon, ng in (("ppmx", 3), ("plm", 2), ("dc", 2)):
             sim = make_sim(deck_text((n, n, n), (1, 1, 1), ng, BOX[0], BOX[1], recon=recon, eos="ideal", rsolver="hllc"))
