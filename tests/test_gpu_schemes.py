@@ -14,6 +14,7 @@ pytestmark = pytest.mark.gpu
 
 import parity_util as pu  # noqa: E402
 from oracle import akref  # noqa: E402
+from stage_cases import wild_prims as _wild_states  # noqa: E402
 
 RECONS = ["dc", "plm", "ppm4", "ppmx", "wenoz", "teno"]
 RS = {"hydro": ["llf", "hlle", "hllc", "roe"], "mhd": ["llf", "hlle", "hlld"]}
@@ -327,17 +328,6 @@ def test_diode_and_vacuum_boundaries(case, fused):
     res = pu.compare_run(problem, n, dims, mb, cycles, fused=(fused is not False), native=(fused == "cpp"), **kw)
     assert res["cycles"] == cycles and res["time"][0] == res["time"][1]
     assert res["bitwise_equal"], res["diffs"]
-
-
-def _wild_states(shape5, rng, mhd):
-    """primitive states with jumps of many decades between neighbouring cells: exercises the
-    supersonic branches, the HLLE/HLLC pressure estimates, Roe's negative-density fallback and
-    the L/R floors of ppmx/wenoz/teno"""
-    w = np.empty(shape5)
-    w[:, 0] = 10.0**rng.uniform(-4, 2, size=w[:, 0].shape)
-    w[:, 1:4] = rng.normal(0, 3.0, size=w[:, 1:4].shape)
-    w[:, 4] = 10.0**rng.uniform(-5, 2, size=w[:, 4].shape)
-    return w
 
 
 @pytest.mark.parametrize("recon", RECONS)
